@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rays/sec (fwd+bwd) of the MI355X-native DIST sphere tracer on BASELINE.json's headline config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): one 512x512 view per GPU, 50 march steps,
@@ -10,22 +10,28 @@ ray_marching_ratio 1.5 ("aggressive"), finite-difference normal channel (use_dep
 image loss + backward to the latent/camera gradients (+ for N>1 the RCCL all-reduce of the packed latent gradient).
 Inputs are resident in HBM before the timed region. Views shard over ranks (view-parallel, weak scaling).
 
+A plain run sets up, warms up (W steps), times exactly K steps and prints ONE JSON line: metric, value (rays/s), unit,
+higher_is_better, dtype, ms_per_step (one timed step) and the configuration. `--dump-outputs DIR` then also writes what the last
+timed step computed (render outputs, camera and shape-code gradients, loss) as DIR/<name>.npy; the inputs are seed-defined, so two
+builds run with the same arguments can be compared array by array. Everything else below -- the median pass, the extra objects,
+and at N > 1 the serial check and the per-rank diagnostics -- runs only with `--full`.
+
 `--workload c5` runs BASELINE.json configs[4] instead (not the headline metric; the strong-scaling curve of SURVEY.md 8e):
 4 shapes (latent seeds 1234..1237) x one 1024x1024 view x 100 march steps, a FIXED total amount of work split over the
 ranks shape-major then into row bands (distr.parallel.shard_rows, distr.functions.render_band_call); "scaling": "strong".
 
-N > 1 (one rank per GPU over RCCL; nothing of this runs at N = 1, whose line is unchanged): the run validates itself.
+N > 1 (one rank per GPU over RCCL; nothing of this runs at N = 1, whose line is unchanged): with --full the run validates itself.
   * two timed regions with the same protocol (W warm-up + exactly K steps between barrier + synchronize): first UNBALANCED (one whole
     view per GPU), then -- after five untimed calibration steps -- BALANCED (slow views hand row bands to fast ranks); `value` is the
     better one, config.unbalanced_ms_per_step / balanced_ms_per_step / value_is report both;
-  * config.serial_check: rank 0 renders all N views itself and the all-reduced loss / latent gradients of both regions must equal
+  * config.serial_check (--full): rank 0 renders all N views itself and the all-reduced loss / latent gradients of both regions must equal
     that serial sum (1e-5 / 1e-4 relative) -- `ok: false` and a non-zero exit otherwise;
   * config.rccl: backend (anything but RCCL is refused unless DISTR_DIST_BACKEND overrides it for one-GPU test rigs, which the line
     then flags with scaling_measurement: false), world size, RCCL version, and rank / device / PCI bus id / pid of every rank;
-  * config.per_rank: every rank's own GPU milliseconds per step and its all-reduce + wait, per timed mode;
+  * config.per_rank (--full): every rank's own GPU milliseconds per step and its all-reduce + wait, per timed mode;
   * the opt-in arithmetic passes and the CPU baselines are skipped.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only; median_ms_per_step / value_at_median: the median of a second pass of K steps):
   roofline     the dominant kernel (fused march/MLP kernel k_march): algorithmic FLOP (3 146 752 per decoder
                evaluation, latent hoisted) / summed hipEvent kernel time on the launch stream, vs the 157.3 TFLOP/s
                f32-MFMA peak (the instruction the kernel uses: v_mfma_f32_32x32x2_f32); `traffic` = fabric-side bytes per march launch,
@@ -63,6 +69,7 @@ ROW_BAND_FIXED = 0.05            # c5 cost-weighted cut: cost of opening one mor
 ROW_FEEDBACK_ROUNDS = 3          # ... and how many measure-and-refine rounds the calibration may take (the best measured cut is kept)
 BALANCE_MARGIN = 0.02            # N > 1: the balanced timing becomes `value` only when it beats the unbalanced one by more than this
 PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md "Peak FP32 (matrix)"
+DUMP_BUDGET_BYTES = 60 * 10**6   # --dump-outputs: all ranks' files together
 
 H = W = 512
 MARCH_STEP, BUFFER_SIZE, RATIO = 50, 3, 1.5
@@ -91,6 +98,22 @@ def cpu_baseline(fixture, Ws, bs, latent, size, march_step, marcher):
             'sample': 'one fwd+bwd of the bench workload itself: %dx%d image of view 0, %d steps, %s, dense loss; %.1f s wall, OpenMP over rays'
                       % (size, size, march_step, marcher, t),
             'host': host_description()}
+
+
+def dump_outputs(out_dir, arrays, budget):
+    """--dump-outputs: every array (name -> tensor or number) as out_dir/<name>.npy in float32. When they hold more than `budget` bytes,
+    every array of more than 4096 elements keeps the same fraction of its elements: a fixed, seeded sample of flat indices (sorted), so
+    that two runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: np.asarray(v.detach().float().cpu().numpy() if torch.is_tensor(v) else v, np.float32) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in host.values() if a.size <= 4096)
+    big = sum(a.nbytes for a in host.values() if a.size > 4096)
+    frac = min(1.0, max(0, budget - small) / big) if big else 1.0
+    for name, a in host.items():
+        if frac < 1.0 and a.size > 4096:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * frac)), replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return frac
 
 
 def collective_info(world, local):
@@ -258,8 +281,8 @@ def live_traffic(timeout_s=150.0):
         return None, 'rocprofv3 not found'
     if any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ) or 'rocprof' in os.environ.get('LD_PRELOAD', ''):
         return None, 'this run is itself being profiled (no nested rocprofv3)'
-    child = [sys.executable, os.path.abspath(__file__), '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-split-bf16-pass', '--no-small-renders',
-             '--no-live-traffic']
+    child = [sys.executable, os.path.abspath(__file__), '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-split-bf16-pass',
+             '--no-small-renders', '--no-live-traffic']
     env = dict(os.environ, TMPDIR='/tmp')
     got, launches, t0 = {}, {}, time.time()
     for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
@@ -405,6 +428,15 @@ def main():
                     help='do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc, ~1 min at N = 1 on the headline '
                          'configuration); the committed PMC summary of the same kernels is reported instead')
     ap.add_argument('--no-small-renders', action='store_true', help='skip extra.small_renders (C2, C1 and 137^2 / 100 steps timed beside the headline at N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline (off by default: a plain run sets up, warms up, times the K '
+                         'steps and prints the line): the median pass, the split-bf16 / split-f16 passes, the roofline pass and live traffic, '
+                         'the forward / backward split and render counters, extra.small_renders, the CPU baselines, and at N > 1 the '
+                         'per-rank diagnostics and the serial check; the --no-* options above skip parts of it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (render outputs of every work item, camera and '
+                         'shape-code gradients, loss) as DIR/<name>.npy in float32; at most %d MB per run, larger outputs as a fixed, '
+                         'seeded sample of their elements' % (DUMP_BUDGET_BYTES // 10**6))
     args = ap.parse_args()
     if args.plan_only:
         sys.exit(plan_only(args))
@@ -515,12 +547,16 @@ def main():
         if (r0, r1) == (0, H):
             last_mask[v] = outs[1]
         band_mask[(shape, r0, r1)] = outs[1]
+        if keep_outs:
+            last_outs[(shape, v, r0, r1)] = outs
         return image_loss(outs, r0, r1, (shape, v))
 
     last = {}              # gradients of the most recent step (reported as a norm: lets two runs be compared)
     last_mask = {}         # rendered mask of every whole view of the most recent step (row cost profile of the balancer)
     band_mask = {}         # rendered mask of every piece of the most recent step (c5: row weights of the cost-weighted cut)
     local_ms = []          # (calibration only) GPU milliseconds of this rank's own work of a step, without the wait in the all-reduce
+    keep_outs = args.dump_outputs is not None
+    last_outs = {}         # (--dump-outputs) render outputs of every work item of the most recent step
 
     def step(measure=False):
         if measure:
@@ -531,6 +567,7 @@ def main():
         for (Rt, Tt) in cams.values():
             Rt.grad = None
             Tt.grad = None
+        last_outs.clear()
         whole = [it for it in items if (it[2], it[3]) == (0, H)]
         if len(whole) >= 2 and not args.no_batch:
             # a batch of whole images (C5: a batch of shapes): every march step is ONE launch over the live rays of all of them
@@ -541,6 +578,8 @@ def main():
             for b, it in enumerate(whole):
                 last_mask[it[1]] = outs[1][b]
                 band_mask[(it[0], 0, H)] = outs[1][b]
+                if keep_outs:
+                    last_outs[(it[0], it[1], 0, H)] = tuple(o[b] for o in outs)
                 losses.append(image_loss(tuple(o[b] for o in outs), 0, H, (it[0], it[1])))
             rest = [it for it in items if (it[2], it[3]) != (0, H)]
             more = [pool.run(i, lambda it=it: render_item(*it)) for i, it in enumerate(rest)]
@@ -563,6 +602,8 @@ def main():
                 l.grad = zero_grad.clone()
         parallel.allreduce_packed([l.grad for l in lats] + [loss_buf])   # one RCCL all-reduce: [latent grads | loss]
         last['grads'] = [l.grad for l in lats]
+        if keep_outs:
+            last['cam_grads'] = {v: (Rt.grad, Tt.grad) for v, (Rt, Tt) in cams.items() if Rt.grad is not None}
         return total
 
     def timed_region():
@@ -578,7 +619,10 @@ def main():
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         parallel.barrier()
-        return parallel.allreduce_max_scalar(el, device=dev), {'loss': float(loss_buf.item()), 'grads': [g.detach().clone() for g in last['grads']]}
+        snap = {'loss': float(loss_buf.item()), 'grads': [g.detach().clone() for g in last['grads']]}
+        if keep_outs:      # (the next step allocates new output and gradient tensors: references stay what this step computed)
+            snap.update(outs=dict(last_outs), cam_grads=last['cam_grads'])
+        return parallel.allreduce_max_scalar(el, device=dev), snap
 
     def rank_diagnostics(n=3):
         """(N > 1, outside the timed regions) what every rank spends on ITS OWN work of a step (hipEvents around render + loss +
@@ -625,7 +669,7 @@ def main():
     timing = {'unbalanced': None, 'balanced': None}
     diag = {}
     snaps = {'chosen': snap}
-    if world > 1:
+    if world > 1 and args.full:
         diag['unbalanced' if not c5 else 'row_bands'] = rank_diagnostics()
     if balance:
         timing['unbalanced'] = elapsed
@@ -656,7 +700,8 @@ def main():
             el_b, snap_b = timed_region()
             timing['balanced'] = el_b
             snaps['balanced'] = snap_b
-            diag['balanced'] = rank_diagnostics()
+            if args.full:
+                diag['balanced'] = rank_diagnostics()
             # `value` switches to the balanced region only when it wins by more than the run-to-run noise (2 %): a plain best-of-two
             # would bias the headline upward by that noise
             if el_b < (1.0 - BALANCE_MARGIN) * elapsed or fake:      # (forced times: the tests want to see the plan's run)
@@ -727,19 +772,41 @@ def main():
             el_w, snap_w = timed_region()
             timing['weighted'] = el_w
             snaps['weighted'] = snap_w
-            diag['weighted_rows'] = rank_diagnostics()
+            if args.full:
+                diag['weighted_rows'] = rank_diagnostics()
             if el_w < (1.0 - BALANCE_MARGIN) * elapsed or fake:
                 elapsed, snaps['chosen'] = el_w, snap_w
             else:
                 timing['row_plan_tried'], row_plan = row_plan, None
                 apply_rows(plan_u)
 
+    # ---- --dump-outputs: what the last step of the timed region that gave `value` computed -- every work item's render outputs
+    # (zdepth, mask, min_sdf, depth, normal), the camera gradients of this rank's views and, from rank 0, the all-reduced shape-code
+    # gradients and loss. Names carry the rank and the work item only where there is more than one.
+    if args.dump_outputs is not None:
+        sn = snaps['chosen']
+        arrays = {}
+        pre_rank = 'rank%d_' % rank if world > 1 else ''
+        for (shape, v, r0, r1), o in sn['outs'].items():
+            pre = pre_rank + ('' if len(sn['outs']) == 1 and (r0, r1) == (0, H) else 's%d_v%d_rows%d-%d_' % (shape, v, r0, r1))
+            for name, t in zip(('zdepth', 'mask', 'min_sdf', 'depth', 'normal'), o):
+                if t.numel():
+                    arrays[pre + name] = t
+        for v, (gR, gT) in sn['cam_grads'].items():
+            pre = pre_rank + ('' if len(sn['cam_grads']) == 1 else 'v%d_' % v)
+            arrays[pre + 'R_grad'], arrays[pre + 'T_grad'] = gR, gT
+        if rank == 0:
+            for i, g in enumerate(sn['grads']):
+                arrays['latent_grad' + ('' if len(sn['grads']) == 1 else '_shape%d' % i)] = g
+            arrays['loss'] = np.float32(sn['loss'])
+        dump_outputs(args.dump_outputs, arrays, DUMP_BUDGET_BYTES // world)
+
     # ---- serial check (N > 1, outside the timed regions): rank 0 renders ALL the job's images itself, one whole image after the
     # other (the sum the reference accumulates serially before its single backward(), core/inv_optimizer/optimize_multi.py:62-81),
     # and compares loss and shape-code gradients with what the all-reduce left after the timed steps. A sharded run that dropped a
     # band, double-counted a view or reduced over the wrong ranks fails here, in the run that produces the number.
     serial_check = None
-    if world > 1:
+    if world > 1 and args.full:
         serial_check = {'images': (n_shapes if c5 else args.gpus), 'tolerance': {'loss_rel': 1e-5, 'grad_rel': 1e-4}}
         if rank == 0:
             for l in lats:
@@ -772,140 +839,140 @@ def main():
                 Tt.grad = None
         parallel.barrier()
 
-    # ---- second pass (not part of `value`): per-step wall times -> median (SURVEY.md 8d asks for the median of >= 20 iterations)
-    per_step = []
-    for _ in range(max(args.steps, 1)):
-        torch.cuda.synchronize()
-        ts = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        per_step.append(time.perf_counter() - ts)
-    median_s = parallel.allreduce_max_scalar(float(np.median(per_step)), device=dev)
-
-    def forward_stats(cfg0):
-        """counters of one forward of every work item of this rank (identical every step: same inputs)"""
-        import ctypes as C
-        p = binding.ptr
-        stats = None
-        for (shape, v, r0, r1) in items:
-            icfg = cfg0 if (r0, r1) == (0, H) else functions.band_cfg(cfg0, r0, r1)[0]
-            n = icfg.band_rows * W
-            fwd_bytes, _ = eng.ctx.workspace_bytes(icfg)
-            ws = torch.empty(fwd_bytes, dtype=torch.uint8, device=dev)
-            outs = [torch.empty(n, device=dev), torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, device=dev),
-                    torch.empty(n, device=dev), torch.empty(n, 3, device=dev)]
-            Rt, Tt = cams[v]
-            eng.ctx.check(eng.ctx.L.distr_render_forward(eng.ctx.h, C.byref(icfg), p(lats[shape].detach().reshape(-1).contiguous()),
-                                                       p(Rt.detach().reshape(-1).contiguous()), p(Tt.detach().contiguous()),
-                                                       p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), p(outs[4]), p(ws), ws.numel(),
-                                                       eng.ctx.stream()))
-            st = eng.ctx.render_stats(icfg, ws)
-            stats = st if stats is None else {k: stats[k] + st[k] for k in st}
-        return stats
-
-    # ---- extra passes (not part of `value`, reported under their own keys): the same K steps with the OPT-IN split-bf16 and split-f16
-    # march tiles (distr_render_cfg.arith = DISTR_ARITH_BF16X6 / _F16X3: six bf16 / three f16 products per f32 product, f32 accumulation;
-    # values within ~1e-6 of the exact ones, parity against the reference's goldens at the 1e-4 bar: tests). Same protocol: warm-up,
-    # barrier + synchronize on both sides, max over ranks. The headline stays the exact-f32 number above.
-    split_modes = {}
-    if args.arith == 'f32' and not args.no_split_bf16_pass and world == 1:     # (N > 1: the scaling run times the exact path only)
-        for mode in ('bf16x6', 'f16x3'):
-            cfg_m = cfg.clone()
-            cfg_m.arith = binding.ARITH[mode]
-            cur['cfg'] = cfg_m
-            for _ in range(max(2, min(args.warmup, 5))):
-                step()
-            torch.cuda.synchronize()
-            parallel.barrier()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                tot_m = step()
-            torch.cuda.synchronize()
-            el_m = time.perf_counter() - t0
-            parallel.barrier()
-            el_m = parallel.allreduce_max_scalar(el_m, device=dev)
-            g_m = float(sum(float(g.norm()) for g in last['grads']))
-            split_modes[mode] = {'ms_per_step': 1e3 * el_m / args.steps, 'loss_rank0': float(tot_m.detach()), 'latent_grad_norm_all_ranks': g_m, 'elapsed_s': el_m}
-            if mode == 'f16x3':
-                split_modes[mode]['f16_overflows'] = forward_stats(cfg_m)['f16_overflows']
-        cur['cfg'] = cfg
-        tot_f32 = step()                                   # back on the exact path (also what the passes below measure)
-        for m in split_modes.values():
-            m['loss_rank0_exact_f32'] = float(tot_f32.detach())
-
-    # ---- third pass: roofline of the march kernels. Every march launch is bracketed by hipEvents on the launch stream (the
-    # brackets serialise a little, which is why they are not in the timed region); algorithmic FLOP / summed kernel time
-    ROOF_STEPS = min(5, max(args.steps, 1))
-    saved_streams, pool.streams = pool.streams, []       # one stream: brackets of concurrent streams would overlap and double count
-    eng.ctx.profile_enable(True)
-    for _ in range(ROOF_STEPS):
-        step()
-    launches, kernel_ms = eng.ctx.profile_read()
-    eng.ctx.profile_enable(False)
-    pool.streams = saved_streams
-
-    grad_norm = float(sum(float(g.norm()) for g in last['grads']))
-
-    # forward / backward split of one step (outside the timed region; hipEvents on the current stream)
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return r, e0.elapsed_time(e1)
-    shape0, v0, r00, r01 = items[0]
-    Rt0, Tt0 = cams[v0]
-    one = (lambda: functions.render_call(eng, cfg, lats[shape0], Rt0, Tt0)) if (r00, r01) == (0, H) else \
-        (lambda: functions.render_band_call(eng, cfg, lats[shape0], Rt0, Tt0, r00, r01))
-    outs0, fwd_ms = timed(one)
-    Lsplit = image_loss(outs0, r00, r01, (shape0, v0))
-    _, bwd_ms = timed(lambda: Lsplit.backward())
-
-    stats = forward_stats(cfg)
-
-    traffic = traffic_hbm = None
-    import glob
-    cands = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_traffic.json')))   # newest round's PMC pass (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)
-    tpath = cands[-1] if cands else os.path.join(ROOT, 'profiles', 'r02_traffic.json')
-    traffic_digest, traffic_stale = None, None
-    from distr import binding as _binding
-    built_from = _binding.source_digest()
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic_digest = tj.get('csrc_sha256')
-            # the PMC pass describes the kernels it ran: if csrc/ has changed since, the number is not this library's (VERDICT r4 item 5)
-            traffic_stale = traffic_digest != built_from
-            traffic = None if traffic_stale else tj['bytes_per_launch']
-            traffic_hbm = tj.get('hbm_bytes_per_launch')
-        except Exception:
-            traffic = None
-    traffic_static, traffic_live_info = traffic, None
-    if world == 1 and not args.no_live_traffic and not c5 and not args.items and args.arith == 'f32' and (H, MARCH_STEP) == (512, 50) \
-            and args.marcher == 'pyramid_recursive' and args.loss == 'dense' and args.fixture == 'f1':
-        torch.cuda.synchronize()
-        live, traffic_live_info = live_traffic()
-        if live is not None:
-            traffic = live
+    grad_norm = float(sum(float(g.norm()) for g in snaps['chosen']['grads']))
     rccl_info = collective_info(world, local)           # (collective: every rank takes part in the all-gather)
     partition = None
     if world > 1:
         partition = [None] * world
         torch.distributed.all_gather_object(partition, [list(it) for it in items])
-    small = None
-    if world == 1 and not args.no_small_renders and not c5 and not args.items and args.arith == 'f32' and (H, MARCH_STEP) == (512, 50):
-        small = small_renders(eng, functions, binding, fixture, latent_np, dev, args.marcher)
+
+    # ---- everything below is not part of `value` and runs only with --full
+    median_s = stats = traffic = traffic_live_info = small = None
+    split_modes = {}
+    if args.full:
+        # ---- second pass (not part of `value`): per-step wall times -> median (SURVEY.md 8d asks for the median of >= 20 iterations)
+        per_step = []
+        for _ in range(max(args.steps, 1)):
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            per_step.append(time.perf_counter() - ts)
+        median_s = parallel.allreduce_max_scalar(float(np.median(per_step)), device=dev)
+
+        def forward_stats(cfg0):
+            """counters of one forward of every work item of this rank (identical every step: same inputs)"""
+            import ctypes as C
+            p = binding.ptr
+            stats = None
+            for (shape, v, r0, r1) in items:
+                icfg = cfg0 if (r0, r1) == (0, H) else functions.band_cfg(cfg0, r0, r1)[0]
+                n = icfg.band_rows * W
+                fwd_bytes, _ = eng.ctx.workspace_bytes(icfg)
+                ws = torch.empty(fwd_bytes, dtype=torch.uint8, device=dev)
+                outs = [torch.empty(n, device=dev), torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, device=dev),
+                        torch.empty(n, device=dev), torch.empty(n, 3, device=dev)]
+                Rt, Tt = cams[v]
+                eng.ctx.check(eng.ctx.L.distr_render_forward(eng.ctx.h, C.byref(icfg), p(lats[shape].detach().reshape(-1).contiguous()),
+                                                           p(Rt.detach().reshape(-1).contiguous()), p(Tt.detach().contiguous()),
+                                                           p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), p(outs[4]), p(ws), ws.numel(),
+                                                           eng.ctx.stream()))
+                st = eng.ctx.render_stats(icfg, ws)
+                stats = st if stats is None else {k: stats[k] + st[k] for k in st}
+            return stats
+
+        # ---- extra passes (not part of `value`, reported under their own keys): the same K steps with the OPT-IN split-bf16 and split-f16
+        # march tiles (distr_render_cfg.arith = DISTR_ARITH_BF16X6 / _F16X3: six bf16 / three f16 products per f32 product, f32 accumulation;
+        # values within ~1e-6 of the exact ones, parity against the reference's goldens at the 1e-4 bar: tests). Same protocol: warm-up,
+        # barrier + synchronize on both sides, max over ranks. The headline stays the exact-f32 number above.
+        split_modes = {}
+        if args.arith == 'f32' and not args.no_split_bf16_pass and world == 1:     # (N > 1: the scaling run times the exact path only)
+            for mode in ('bf16x6', 'f16x3'):
+                cfg_m = cfg.clone()
+                cfg_m.arith = binding.ARITH[mode]
+                cur['cfg'] = cfg_m
+                for _ in range(max(2, min(args.warmup, 5))):
+                    step()
+                torch.cuda.synchronize()
+                parallel.barrier()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    tot_m = step()
+                torch.cuda.synchronize()
+                el_m = time.perf_counter() - t0
+                parallel.barrier()
+                el_m = parallel.allreduce_max_scalar(el_m, device=dev)
+                g_m = float(sum(float(g.norm()) for g in last['grads']))
+                split_modes[mode] = {'ms_per_step': 1e3 * el_m / args.steps, 'loss_rank0': float(tot_m.detach()), 'latent_grad_norm_all_ranks': g_m, 'elapsed_s': el_m}
+                if mode == 'f16x3':
+                    split_modes[mode]['f16_overflows'] = forward_stats(cfg_m)['f16_overflows']
+            cur['cfg'] = cfg
+            tot_f32 = step()                                   # back on the exact path (also what the passes below measure)
+            for m in split_modes.values():
+                m['loss_rank0_exact_f32'] = float(tot_f32.detach())
+
+        # ---- third pass: roofline of the march kernels. Every march launch is bracketed by hipEvents on the launch stream (the
+        # brackets serialise a little, which is why they are not in the timed region); algorithmic FLOP / summed kernel time
+        ROOF_STEPS = min(5, max(args.steps, 1))
+        saved_streams, pool.streams = pool.streams, []       # one stream: brackets of concurrent streams would overlap and double count
+        eng.ctx.profile_enable(True)
+        for _ in range(ROOF_STEPS):
+            step()
+        launches, kernel_ms = eng.ctx.profile_read()
+        eng.ctx.profile_enable(False)
+        pool.streams = saved_streams
+
+        # forward / backward split of one step (outside the timed region; hipEvents on the current stream)
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return r, e0.elapsed_time(e1)
+        shape0, v0, r00, r01 = items[0]
+        Rt0, Tt0 = cams[v0]
+        one = (lambda: functions.render_call(eng, cfg, lats[shape0], Rt0, Tt0)) if (r00, r01) == (0, H) else \
+            (lambda: functions.render_band_call(eng, cfg, lats[shape0], Rt0, Tt0, r00, r01))
+        outs0, fwd_ms = timed(one)
+        Lsplit = image_loss(outs0, r00, r01, (shape0, v0))
+        _, bwd_ms = timed(lambda: Lsplit.backward())
+
+        stats = forward_stats(cfg)
+
+        traffic = traffic_hbm = None
+        import glob
+        cands = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_traffic.json')))   # newest round's PMC pass (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)
+        tpath = cands[-1] if cands else os.path.join(ROOT, 'profiles', 'r02_traffic.json')
+        traffic_digest, traffic_stale = None, None
+        from distr import binding as _binding
+        built_from = _binding.source_digest()
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                traffic_digest = tj.get('csrc_sha256')
+                # the PMC pass describes the kernels it ran: if csrc/ has changed since, the number is not this library's (VERDICT r4 item 5)
+                traffic_stale = traffic_digest != built_from
+                traffic = None if traffic_stale else tj['bytes_per_launch']
+                traffic_hbm = tj.get('hbm_bytes_per_launch')
+            except Exception:
+                traffic = None
+        traffic_static, traffic_live_info = traffic, None
+        if world == 1 and not args.no_live_traffic and not c5 and not args.items and args.arith == 'f32' and (H, MARCH_STEP) == (512, 50) \
+                and args.marcher == 'pyramid_recursive' and args.loss == 'dense' and args.fixture == 'f1':
+            torch.cuda.synchronize()
+            live, traffic_live_info = live_traffic()
+            if live is not None:
+                traffic = live
+        small = None
+        if world == 1 and not args.no_small_renders and not c5 and not args.items and args.arith == 'f32' and (H, MARCH_STEP) == (512, 50):
+            small = small_renders(eng, functions, binding, fixture, latent_np, dev, args.marcher)
     if rank == 0:
-        evals = stats['num_point_evals'] * ROOF_STEPS
-        flops = FLOP_PER_EVAL * evals
-        achieved = flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
         rays = (4.0 if c5 else float(args.gpus)) * H * W * args.steps     # c5: fixed total work (4 images); c3: one view per GPU
         out = {
             'metric': 'rays/sec (fwd+bwd) at %dx%d, %d march steps, DeepSDF 8x512' % (H, W, MARCH_STEP),
             'value': rays / elapsed, 'unit': 'rays/s', 'n_gpus': args.gpus, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': 1e3 * elapsed / args.steps, 'median_ms_per_step': 1e3 * median_s,
-            'value_at_median': rays / args.steps / median_s, 'higher_is_better': True, 'scaling': 'strong' if c5 else 'weak', 'vs_baseline': None,
+            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'strong' if c5 else 'weak', 'vs_baseline': None,
             'dtype': 'f32' if args.arith == 'f32' else 'f32 emulated by six bf16 products per f32 product (f32 accumulation; opt-in, not the headline)', 'data': 'synthetic (seed-defined geometric-init DeepSDF 8x512 weights, latent seed 1234, synthetic cameras)' if args.fixture == 'f1' else
                                     'synthetic (fixture F2: DeepSDF 8x512 decoder fitted to an analytic torus + thin plate, synthetic cameras)',
             'config': {'workload': '%s%dx%d, %d march steps, %s marcher, buffer_size %d, ratio %.1f, depth2normal normals, '
@@ -919,14 +986,21 @@ def main():
                                       ((' (%s all-reduce of packed latent grad)' % ('RCCL' if rccl_info.get('backend') == 'nccl' else str(rccl_info.get('backend')) + ' [NOT RCCL: test rig]')) if world > 1 else ' (single process, no collective)'),
                        'rccl': rccl_info,
                        'rank0_items': [list(it) for it in items], 'balance_plan': plan, 'calibration_steps_before_warmup': calibration_steps, 'loss_sum_all_ranks': float(loss_buf.item()),
-                       'latent_grad_norm_all_ranks': grad_norm,
-                       'rays_in_sphere': stats['num_in_sphere'], 'valid_px': stats['num_valid'], 'fixture': args.fixture, 'arith': args.arith,
+                       'latent_grad_norm_all_ranks': grad_norm, 'fixture': args.fixture, 'arith': args.arith, 'full': bool(args.full)},
+        }
+        if args.full:
+            evals = stats['num_point_evals'] * ROOF_STEPS
+            flops = FLOP_PER_EVAL * evals
+            achieved = flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
+            out.update(median_ms_per_step=1e3 * median_s, value_at_median=rays / args.steps / median_s)
+            out['config'].update({
+                       'rays_in_sphere': stats['num_in_sphere'], 'valid_px': stats['num_valid'],
                        'decoder_evals_per_image_ray': stats['num_point_evals'] / float(len(items) * H * W) if not c5 else None,
                        'decoder_evals_per_step_rank0': stats['num_point_evals'],
                        'march_launches_per_step_rank0': stats['num_march_launches'],
                        'forward_ms_one_item': fwd_ms, 'backward_ms_one_item': bwd_ms, 'cluster_fallbacks': stats['cluster_fallbacks'],
-                       'decoder_evals_per_s_march': evals / (kernel_ms * 1e-3) if kernel_ms > 0 else 0.0},
-            'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': PEAK_F32_MFMA_TFLOPS if args.arith == 'f32' else 2500.0, 'unit': 'TFLOP/s',
+                       'decoder_evals_per_s_march': evals / (kernel_ms * 1e-3) if kernel_ms > 0 else 0.0})
+            out['roofline'] = {'bound': 'mfma', 'achieved': achieved, 'peak': PEAK_F32_MFMA_TFLOPS if args.arith == 'f32' else 2500.0, 'unit': 'TFLOP/s',
                          'frac': achieved / (PEAK_F32_MFMA_TFLOPS if args.arith == 'f32' else 2500.0), 'traffic': traffic,
                          'peak_note': 'f32-MFMA peak' if args.arith == 'f32' else 'bf16 / f16 MFMA dense peak; algorithmic FLOP counted once (the six bf16 / three f16 products per f32 product are not counted several times)',
                          'traffic_csrc_sha256': traffic_digest, 'csrc_sha256': built_from,
@@ -940,8 +1014,7 @@ def main():
                                              'the render\'s working set (14.5 MB of weights + ray state) is far below the 256 MiB Infinity Cache (profiles/r06_traffic.json: memory_side_reads)',
                          'kernel': 'k_march / k_step / k_tail (fused 9-layer decoder + march update; one hipEvent bracket per march launch, separate pass of %d steps), %d launches, %.3f ms total, avg %.1f us'
                                    % (ROOF_STEPS, launches, kernel_ms, 1e3 * kernel_ms / max(launches, 1)),
-                         'flop_per_eval': FLOP_PER_EVAL, 'evals': evals},
-        }
+                         'flop_per_eval': FLOP_PER_EVAL, 'evals': evals}
         notes = {'bf16x6': 'opt-in arithmetic (distr_render_cfg.arith = 1, `--arith bf16x6`): every f32 product of the seven wide decoder layers '
                            'as six bf16 products with f32 accumulation; same workload, same K steps, same timing protocol; NOT the headline '
                            '(the headline `value` is exact f32, bit-identical to the oracle). Parity of this mode: reference goldens at the 1e-4 '
@@ -961,8 +1034,9 @@ def main():
         if world > 1:
             c = out['config']
             c['partition'] = partition
-            c['serial_check'] = serial_check
-            c['per_rank'] = diag
+            if args.full:
+                c['serial_check'] = serial_check
+                c['per_rank'] = diag
             c['scaling_measurement'] = bool(rccl_info.get('one_gpu_per_rank'))       # false on test rigs whose ranks time-share one GPU over gloo
             if balance:
                 c['unbalanced_ms_per_step'] = 1e3 * timing['unbalanced'] / args.steps
@@ -980,12 +1054,12 @@ def main():
             # which of the timed modes is the N = 1 protocol run on N GPUs (one whole view per GPU, nothing moved between ranks): efficiency
             # against the N = 1 line compares like with like only through this mode's number
             c['n1_protocol_equivalent'] = 'unbalanced' if not c5 else 'row_bands (strong scaling: no N = 1 analogue per rank; compare total ms_per_step)'
-        if not args.no_cpu_baseline and args.gpus == 1:      # reported baselines, rank 0 at N=1 only (~30 s + ~20 s of CPU work)
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:      # reported baselines, rank 0 at N=1 only (~30 s + ~20 s of CPU work)
             out['cpu_baseline'] = cpu_baseline(fixture, Ws, bs, latent_np, H, MARCH_STEP, args.marcher)
             out['cpu_baseline_torch'] = cpu_baseline_torch(fixture, Ws, bs, latent_np, MARCH_STEP, args.marcher)
         print(json.dumps(out), file=json_out, flush=True)
     parallel.barrier()
-    if world > 1:
+    if serial_check is not None:          # (every rank of an N > 1 run with --full: the all-reduce below is collective)
         ok = parallel.allreduce_max_scalar(0.0 if (rank != 0 or serial_check.get('ok')) else 1.0, device=dev) == 0.0
         if not ok:
             raise SystemExit('bench.py: the all-reduced loss / gradients do not match the serial sum over all images (config.serial_check)')

@@ -10,9 +10,9 @@ PART=${2:-abc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$(pwd)
-CMD="python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-split-bf16-pass --no-small-renders --no-live-traffic"      # the headline (exact f32) kernels only
+CMD="python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-split-bf16-pass --no-small-renders --no-live-traffic"      # the headline (exact f32) kernels only
 if [[ $PART == *a* ]]; then
-  python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   ( cd /tmp && rocprofv3 -L > "$R/$OUT/rocprof_counters.txt" 2>&1 )
   ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- bash -c "cd $R && $CMD" > "$R/$OUT/rocprof_kt.log" 2>&1 )
   python profiles/summarize.py /tmp/prof_kt "$OUT/kernel_stats.md" > /dev/null 2>&1
@@ -22,9 +22,9 @@ if [[ $PART == *a* ]]; then
     ( cd /tmp && rocprofv3 --pmc $C --kernel-trace --output-format csv -d /tmp/prof_$N -- bash -c "cd $R && $CMD" > "$R/$OUT/rocprof_$N.log" 2>&1 )
     python profiles/summarize.py /tmp/prof_$N "$OUT/pmc_$N.md" --pmc > /dev/null 2>&1
   done
-  DISTR_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 > "$OUT/bench_n2_gloo.json" 2> "$OUT/bench_n2_gloo.err"
-  DISTR_DIST_BACKEND=gloo python bench.py --gpus 8 --steps 3 --warmup 1 > "$OUT/bench_n8_gloo.json" 2> "$OUT/bench_n8_gloo.err"
-  DISTR_DIST_BACKEND=gloo python bench.py --workload c5 --gpus 2 --steps 2 --warmup 1 > "$OUT/bench_c5_n2_gloo.json" 2> "$OUT/bench_c5_n2_gloo.err"
+  DISTR_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 > "$OUT/bench_n2_gloo.json" 2> "$OUT/bench_n2_gloo.err"
+  DISTR_DIST_BACKEND=gloo python bench.py --full --gpus 8 --steps 3 --warmup 1 > "$OUT/bench_n8_gloo.json" 2> "$OUT/bench_n8_gloo.err"
+  DISTR_DIST_BACKEND=gloo python bench.py --full --workload c5 --gpus 2 --steps 2 --warmup 1 > "$OUT/bench_c5_n2_gloo.json" 2> "$OUT/bench_c5_n2_gloo.err"
 fi
 if [[ $PART == *b* ]]; then
   python tests/gpu_diag_steps.py --out "$OUT/steps_c3.md" > /dev/null 2>&1
@@ -40,15 +40,15 @@ if [[ $PART == *b* ]]; then
   DISTR_TAIL=0 python tests/gpu_diag_loop.py 64 137 224 > "$OUT/loop_notail.log" 2>&1
   python tests/gpu_diag_cluster.py 64 99 2>&1 | grep -v amdgpu.ids > "$OUT/cluster_phases.log"
   python tests/gpu_diag_batch.py 137 8 recursive 2>&1 | grep -v "amdgpu.ids\|Warning\|warn\|Consider\|return Variable" > "$OUT/batch_round.log"
-  python bench.py --loss reference --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_reference_loss.json" 2>/dev/null
-  python bench.py --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c5_n1.json" 2>/dev/null
-  python bench.py --size 256 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c2_256.json" 2>/dev/null
-  python bench.py --size 64 --march-step 20 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c1_64.json" 2>/dev/null
-  python bench.py --size 137 --march-step 100 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_137_100.json" 2>/dev/null
-  python bench.py --marcher recursive --steps 5 --warmup 2 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_recursive.json" 2>/dev/null
-  python bench.py --marcher trivial --steps 3 --warmup 1 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_trivial.json" 2>/dev/null
-  python bench.py --fixture f2 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_f2.json" 2>/dev/null
-  DISTR_TAIL=0 python bench.py --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c3_notail.json" 2>/dev/null
+  python bench.py --full --loss reference --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_reference_loss.json" 2>/dev/null
+  python bench.py --full --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c5_n1.json" 2>/dev/null
+  python bench.py --full --size 256 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c2_256.json" 2>/dev/null
+  python bench.py --full --size 64 --march-step 20 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c1_64.json" 2>/dev/null
+  python bench.py --full --size 137 --march-step 100 --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_137_100.json" 2>/dev/null
+  python bench.py --full --marcher recursive --steps 5 --warmup 2 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_recursive.json" 2>/dev/null
+  python bench.py --full --marcher trivial --steps 3 --warmup 1 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_trivial.json" 2>/dev/null
+  python bench.py --full --fixture f2 --no-cpu-baseline --no-split-bf16-pass --no-small-renders > "$OUT/extra_c3_f2.json" 2>/dev/null
+  DISTR_TAIL=0 python bench.py --full --no-cpu-baseline --no-split-bf16-pass > "$OUT/extra_c3_notail.json" 2>/dev/null
 fi
 if [[ $PART == *c* ]]; then
   # soak (not part of the timed pytest -m gpu): 96 seeded random renderer configurations HIP vs oracle, the 8-stream oversubscription stress at 400

@@ -517,10 +517,10 @@ def test_bench_rccl_multi_gpu():
     for extra in (['--view-offset', '6', '--no-balance'], ['--view-offset', '6']):          # views 6 and 7 differ by 18 %: the plan moves rows
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                '--master-port', str(29790 + (os.getpid() % 40) + len(outs)), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3',
-               '--warmup', '5'] + extra
+               '--warmup', '5', '--full'] + extra
         if not extra[2:]:
             # the balanced run without a launcher and without the IPC variable: bench.py spawns its ranks and sets it itself
-            cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '5'] + extra
+            cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '5', '--full'] + extra
             env = {k: v for k, v in env.items() if k not in ('HSA_ENABLE_IPC_MODE_LEGACY', 'RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-2000:]

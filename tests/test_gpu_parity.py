@@ -1226,8 +1226,9 @@ def test_decode_sdf_autograd_matches_reference_golden(fixture_decoder):
 
 
 def _bench_ranks(n, args, env_extra=None, launcher=True, timeout=600, expect_rc=0):
-    """`bench.py --gpus n` with n ranks time-sharing this one GPU (gloo for the collectives: RCCL ranks cannot share a device). Small
-    images, one timed step: these tests check the multi-rank PROTOCOL of the driver's scaling run, not its speed."""
+    """`bench.py --gpus n --full` with n ranks time-sharing this one GPU (gloo for the collectives: RCCL ranks cannot share a device). Small
+    images, one timed step: these tests check the multi-rank PROTOCOL of the driver's scaling run, not its speed; --full for the serial
+    check, the per-rank diagnostics and the roofline they read."""
     import json
     import subprocess
     from conftest import ROOT
@@ -1237,9 +1238,9 @@ def _bench_ranks(n, args, env_extra=None, launcher=True, timeout=600, expect_rc=
         port = 29700 + (os.getpid() * 7 + _bench_ranks.calls * 13) % 290
         _bench_ranks.calls += 1
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
-               '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', str(n)] + args
+               '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--full'] + args
     else:
-        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n)] + args
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--full'] + args
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     if expect_rc is None:
         return out
@@ -1303,7 +1304,7 @@ def test_bench_spawns_its_own_ranks():
     time-share the device over gloo (DISTR_DIST_BACKEND); without that override a box with fewer GPUs than ranks is refused with a
     clear message instead of an RCCL hang."""
     drop = {k: None for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'HSA_ENABLE_IPC_MODE_LEGACY')}
-    args = ['--steps', '1', '--warmup', '0', '--size', '128', '--march-step', '30', '--no-balance']
+    args = ['--steps', '1', '--warmup', '0', '--size', '128', '--march-step', '30', '--no-balance', '--full']
     import subprocess
     from conftest import ROOT
     env = dict(os.environ, DISTR_DIST_BACKEND='gloo')
@@ -1378,6 +1379,51 @@ def test_bench_view_balancing_eight_ranks():
     assert abs(bal['value'] - 8 * H * H / (bal['ms_per_step'] * 1e-3)) <= 1e-6 * bal['value']      # whole-job rays / max-over-ranks time
     sc = bal['config']['serial_check']
     assert sc['images'] == 8 and sc['balanced']['grad_rel'] <= 1e-4 and sc['unbalanced']['grad_rel'] <= 1e-4, sc
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(engine, fixture_decoder, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full): K timed steps, the headline keys and nothing measured beside them. With --dump-outputs
+    its files hold what the timed step computed: the render of view 0 and the gradients / loss of the dense loss, equal to the same
+    step made here (render bit for bit, gradients and loss at the serial check's bars)."""
+    import json
+    import subprocess
+    import torch
+    import bench
+    from conftest import ROOT
+    from distr import binding, fixture, functions
+    size, march = 128, 30
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--size', str(size),
+                          '--march-step', str(march), '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j['steps'] == 2 and j['warmup'] == 1 and j['unit'] == 'rays/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+    assert j['config']['full'] is False and abs(j['value'] * j['ms_per_step'] * 1e-3 - size * size) <= 1e-6 * size * size
+    for k in ('roofline', 'split_bf16', 'split_f16', 'extra', 'cpu_baseline', 'median_ms_per_step'):
+        assert k not in j, k
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert set(got) == {'zdepth', 'mask', 'min_sdf', 'depth', 'normal', 'R_grad', 'T_grad', 'latent_grad', 'loss'}
+    assert all(a.dtype == np.float32 for a in got.values())
+    _, _, latent = fixture_decoder
+    dev = engine.device
+    R, T = bench.view_camera(fixture, 0)
+    cfg = binding.make_cfg((size, size), fixture.make_intrinsic(size, size), march_step=march, buffer_size=bench.BUFFER_SIZE, ratio=bench.RATIO,
+                           marcher='pyramid_recursive', use_depth2normal=True)
+    lat, Rt, Tt = (torch.from_numpy(np.asarray(x, np.float32)).to(dev).requires_grad_(True) for x in (latent, R, T))
+    rs = np.random.RandomState(5)
+    wd, wq, wn = (torch.from_numpy(rs.rand(*s).astype(np.float32)).to(dev) for s in ((size, size), (size, size), (size, size, 3)))
+    z, mask, q, depth, normal = functions.render_call(engine, cfg, lat, Rt, Tt)
+    mb = mask.reshape(size, size).bool()
+    L = torch.where(mb, depth * wd, torch.zeros_like(depth)).sum() + (q.reshape(size, size) * wq).sum() + (normal * wn).sum()
+    L.backward()
+    for name, t in (('zdepth', z), ('mask', mask), ('min_sdf', q), ('depth', depth), ('normal', normal)):
+        assert np.array_equal(got[name], t.detach().float().cpu().numpy().reshape(got[name].shape)), name
+    for name, t in (('R_grad', Rt.grad), ('T_grad', Tt.grad), ('latent_grad', lat.grad)):
+        b = t.detach().cpu().numpy().reshape(got[name].shape)
+        assert np.abs(got[name] - b).max() <= 1e-4 * np.abs(b).max(), name
+    assert abs(float(got['loss']) - float(L)) <= 1e-5 * abs(float(L))
 
 
 @pytest.mark.gpu
