@@ -44,6 +44,8 @@ struct Consts {
   int32_t cnt_live[MAX_STEPS + 2];  // live rays entering fine step t (compacted list of that step's launch)
   int32_t cnt_sticky[MAX_STEPS + 2]; // rays evaluated at fine step t by sticky tiles (no list: sticky_tile16); statistics only
   int32_t f16_overflow;   // split-f16 arithmetic (cfg.arith = 2): decoder evaluations whose value left the f16 range (non-finite result)
+  int32_t live_end;       // != 0: a ray is still live after the LAST full-resolution step (set by whichever tile evaluated it: mark_live_end).
+                          // cnt_live[fine_steps] cannot say so: a sticky tile keeps its rays and appends to no list (early_dup)
   // persistent tail kernel (k_tail): fine steps [tail_from, fine_steps) run inside ONE launch (tail_from = fine_steps: no tail launch).
     int32_t tail_from;
   int32_t tail_steals;    // tiles a workgroup other than their owner evaluated after waiting too long (owner not resident); statistics
@@ -291,6 +293,14 @@ __device__ __forceinline__ void block_append(bool flag, int32_t id, int32_t* lis
   if (flag) list[base + ballot_rank(ball)] = id;
 }
 
+// after the LAST full-resolution step (step + 1 == fine_steps): one lane of a wave with a ray that stays live records that the march did
+// not break there (Consts::live_end, read by early_dup). Called by the whole wave, by every path that evaluates a fine step
+__device__ __forceinline__ void mark_live_end(Consts* C, bool stay, int step, int fine_steps) {
+  if (step + 1 != fine_steps) return;
+  const unsigned long long ball = __ballot(stay);
+  if (ball != 0ull && (threadIdx.x & 63) == 0) atomicOr(&C->live_end, 1);
+}
+
 // wave-level max, then one atomicMax per wavefront (skipped when the wave has nothing to contribute)
 __device__ __forceinline__ void wave_atomic_max(uint32_t* dst, uint32_t v) {
 #pragma unroll
@@ -341,6 +351,7 @@ DISTR_GLOBAL void __launch_bounds__(256) k_prep(View V0, DecoderDev D, const flo
       C->origin_done = 0;
       C->xchg_err = 0;
       C->f16_overflow = 0;
+      C->live_end = 0;
       C->tail_from = V0.tail_from;
       C->tail_steals = 0;
       C->cnt_valid = 0; C->cnt_normal = 0; C->cnt_samples = 0; C->pad_coef = 0.f;
@@ -556,15 +567,18 @@ __device__ __forceinline__ int topk_slot_pre(const View& V, const RayPre& st, fl
 // were evaluated at that step included -- and the selection (bs smallest |sdf|, earlier row wins ties) then takes copies of a ray's last row
 // where this library's selected-row buffer holds the rows behind it (usually pad rows). Values do not change (top-1 is the original), the
 // GRADIENT does: the copies are evaluated again, each carries the row's coefficient. Emulated on the buffer: with the last row at sorted
-// position p, n = min(bs - L, bs - 1 - p) copies follow it and the last n rows of the buffer drop out. Returns bs - L (0: no early break
-// below buffer_size steps, or not applicable) and L. Not applied to row bands: the break is a property of the WHOLE image's march, which a
-// band cannot see. Found by the random options soak of round 6 (cameras inside the sphere, buffer_size 5..8).
+// position p, n = min(bs - L, bs - 1 - p) copies follow it and the last n rows of the buffer drop out. The break can also come on the LAST step:
+// a pyramid's fine level may be shorter than buffer_size (its coarse rows fill the buffer), and when no ray is live after step fine_steps - 1
+// the reference pads there too -- L = fine_steps. That is Consts::live_end, not cnt_live[fine_steps]: a sticky tile's rays enter no list.
+// Returns bs - L (0: no early break below buffer_size steps, or not applicable) and L. Not applied to row bands: the break is a property of
+// the WHOLE image's march, which a band cannot see. Found by the random options soak of round 6 (cameras inside the sphere, buffer_size 5..8).
 __device__ __forceinline__ int early_dup(const View& V, const Consts* C, int& L) {
   L = 0;
   if (V.cfg.marcher == DISTR_MARCH_TRIVIAL || V.band) return 0;
-  const int bs = V.cfg.buffer_size;
-  for (int t = 0; t < bs && t < V.fine_steps; ++t)
+  const int bs = V.cfg.buffer_size, fs = V.fine_steps;
+  for (int t = 0; t < bs && t < fs; ++t)
     if (C->cnt_live[t] + C->cnt_sticky[t] == 0) { L = t; return t >= 1 ? bs - t : 0; }
+  if (fs >= 1 && fs < bs && C->live_end == 0) { L = fs; return bs - fs; }
   return 0;
 }
 // ... for one pixel: position of the duplicated row in its selected-row buffer (-1: none) and the number of copies selected
@@ -838,8 +852,10 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
           if (A.step == 0) V.first_sdf[(uint32_t)id] = s;
           stay = (za < st.maxbound) && (a >= V.cfg.threshold);
         }
-        if (V.cfg.marcher != DISTR_MARCH_TRIVIAL)
+        if (V.cfg.marcher != DISTR_MARCH_TRIVIAL) {
           wave_append(stay, id, live_sel(V, A.step + 1), &V.C->cnt_live[A.step + 1]);
+          mark_live_end(V.C, stay, A.step, V.fine_steps);
+        }
       }
     }
   }
@@ -1065,6 +1081,7 @@ __device__ __forceinline__ void sticky_tile16(const MarchArgs& A, const DecoderD
         m = mn;
         stay = (za < maxbound) && (a >= Ve.cfg.threshold);
       }
+      if (lead) mark_live_end(Ve.C, tid < TILE && stay, step, Ve.fine_steps);
       if (!TAIL && solo && k == 0 && lead) {
         // the cluster never assembled (its compute units are held by another stream / rank): this tile does NOT turn sticky -- the
         // lead member evaluated the step alone and hands the surviving rays to the next step's live list like a per-step tile
@@ -1273,6 +1290,7 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
         stay = (za < sr.maxbound) && (a >= Ve.cfg.threshold);
       }
       wave_append<false>(stay, id, live_sel(Ve, t.step + 1), &Ve.C->cnt_live[t.step + 1], TAIL ? t.count2 : nullptr);
+      mark_live_end(Ve.C, stay, t.step, Ve.fine_steps);
     }
   }
   if (KEEP && MODE != MODE_EVAL) {

@@ -71,6 +71,7 @@ def lib():
         L.orc_state_num_steps.restype = C.c_int64
         L.orc_state_num_steps.argtypes = [C.c_void_p]
         L.orc_state_live_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.orc_state_march_end.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.orc_state_num_inside.restype = C.c_int64
         L.orc_state_num_inside.argtypes = [C.c_void_p]
         L.orc_state_init_z.argtypes = [C.c_void_p, fp]
@@ -150,6 +151,30 @@ class RenderState(object):
         if n:
             lib().orc_state_live_counts(self.ptr, out.ctypes.data_as(C.POINTER(C.c_int64)))
         return out
+
+    def _march_end(self):
+        out = np.zeros(3, dtype=np.int32)
+        lib().orc_state_march_end(self.ptr, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    @property
+    def fine_rows(self):
+        """Rows the full-resolution march produced before padding (its executed steps)."""
+        return int(self._march_end()[0])
+
+    @property
+    def pad_rows(self):
+        """Copies of the last step's rows appended by the early break (renderer.py:562-567); 0: no padding."""
+        return int(self._march_end()[1])
+
+    @property
+    def padded(self):
+        return self.pad_rows > 0
+
+    @property
+    def live_after_last_step(self):
+        """A ray was still live after the full-resolution march's last step (it ran out of steps, no break on the last one)."""
+        return bool(self._march_end()[2])
 
     @property
     def init_z(self):

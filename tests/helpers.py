@@ -134,6 +134,55 @@ def compare_big_golden(a, g, label, grad_floor_mult=2.0):
     return res
 
 
+
+# ---- the early break of the recursive march (renderer.py:562-567) at its edges: one random draw of the sweep and the class of its march
+EARLY_BREAK_MENU = ([2, 1], [3, 1], [4, 2, 1], [4, 2, 1], [6, 2, 1], [8, 4, 2, 1])
+EARLY_BREAK_CLASSES = ('below', 'last', 'none')
+MAX_BS = 8                     # include/distr.h: largest buffer_size
+
+
+def early_break_class(state, fine_steps):
+    """'below': no ray live after step L - 1 < fine_steps - 1 with L < buffer_size (the lists are padded); 'last': the same on the last step
+    of a fine level shorter than buffer_size (L = fine_steps); 'none': no padding (the march ran out of steps with a live ray, or broke at
+    L >= buffer_size). From the oracle's state (oracle/oracle.py: fine_rows / padded)."""
+    if not state.padded:
+        return 'none'
+    return 'last' if state.fine_rows == fine_steps else 'below'
+
+
+def early_break_draw(seed, O, orc, latent):
+    """Seeded draw of the early-break sweep: a pyramid (menu above) whose fine level has 1 .. buffer_size + 2 steps, buffer_size 2..8, a camera
+    inside the sphere looking at the surface, exact sphere tracing (ratio 1) mostly. seed % 3 aims at one class: 0 'last' -- the scene is
+    probed on the oracle (forward only, 12 fine steps, buffer_size 1), the fine level cut to the step L its march broke on and buffer_size
+    drawn above L (the coarse levels stay and the march does not depend on buffer_size: the same march, ending on its last step);
+    1 'below' (fine level >= buffer_size); 2 'none' (longer steps: the march outlasts the buffer or runs out).
+    Returns (H, W, K, R, T, kw, fine_steps); the class is read from the oracle's render (early_break_class)."""
+    from distr import fixture
+    aim = seed % 3
+    rs = np.random.RandomState(31000 + seed)
+    H, W = int(rs.randint(24, 64)), int(rs.randint(24, 64))
+    bs = int(rs.randint(2, 9))
+    sl = list(EARLY_BREAK_MENU[rs.randint(len(EARLY_BREAK_MENU))])
+    msl = [int(rs.randint(1, 4)) for _ in sl[:-1]]
+    fine = int(rs.randint(bs, bs + 3)) if aim < 2 else int(rs.randint(1, bs + 3))
+    while sum(msl) + fine < bs:         # (check_cfg: coarse rows + fine steps >= buffer_size)
+        msl[int(rs.randint(len(msl)))] += 1
+    kw = dict(march_step=sum(msl) + fine, buffer_size=bs, ratio=1.0 if aim < 2 else float(rs.choice([1.0, 1.5, 2.0])), marcher='pyramid_recursive',
+              use_depth2normal=bool(rs.randint(2)), scale_list=sl, march_step_list=msl + [-1], threshold=float(10 ** rs.uniform(-3.2, -2.5)),
+              radius=float(rs.uniform(1.0, 1.3)), clamp_dist=float(rs.uniform(0.1, 0.3)))
+    cam = (float(rs.uniform(-180, 180)), float(rs.uniform(-60, 60)), float(rs.uniform(0.4, 0.6) if aim < 2 else rs.uniform(0.5, 0.8)), float(rs.uniform(-30, 30)))
+    K = fixture.make_intrinsic(H, W)
+    R, T = fixture.make_camera(*cam)
+    if aim == 0:
+        probe = dict(kw, march_step=sum(msl) + 12, buffer_size=1)
+        st = O.render(orc.make_cfg(H, W, K, **probe), latent, R, T)['state']
+        L = st.fine_rows
+        if not st.live_after_last_step and 1 <= L < 12 and L + 1 <= min(MAX_BS, sum(msl) + L):
+            fine = L
+            kw.update(march_step=sum(msl) + L, buffer_size=int(rs.randint(L + 1, min(MAX_BS, sum(msl) + L) + 1)))
+    return H, W, K, R, T, kw, fine
+
+
 DEEPSDF_SPECS = {       # the layout of facebookresearch/DeepSDF's examples/*/specs.json (what load_decoder reads, decoder_utils.py:7-27)
     'Description': ['synthetic experiment directory written by tests/helpers.py: fixture F1 in DeepSDF checkpoint format'],
     'NetworkArch': 'deep_sdf_decoder', 'CodeLength': 256,

@@ -403,3 +403,45 @@ def test_render_depth_batch_mixed_no_grad_flags_equal_per_view_calls(fixture_dec
                 assert torch.equal(a, b), (v, nm, (a - b).abs().max())
     assert Rs2[1].grad is None or float(Rs2[1].grad.abs().max()) == 0.0           # both flags set: nothing reaches view 1's camera
     assert (lat.grad - lat2.grad).abs().max() <= 2e-6 * lat2.grad.abs().max()      # (a shared code: the sum over views, order differs)
+
+
+def test_batch_mixing_early_break_classes_equals_per_view(engine, cpu_oracle, orc, fixture_decoder):
+    """One configuration (a four-level pyramid with 2 fine steps, buffer_size 8), four cameras inside the sphere whose marches end differently:
+    a break after the first fine step (below buffer_size, before the last step), two breaks ON the last step, and rays that outlive it. Each
+    view's padding comes from ITS march (early_dup reads the view's own Consts): every view byte-identical to its stand-alone render, and the
+    stand-alone render matches the oracle."""
+    import torch
+    import helpers
+    from distr import binding, fixture
+    _, _, latent = fixture_decoder
+    H, W = 40, 48
+    kw = dict(march_step=8, buffer_size=8, ratio=1.0, marcher='pyramid_recursive', threshold=5e-4, radius=1.2, clamp_dist=0.2,
+              scale_list=[8, 4, 2, 1], march_step_list=[2, 2, 2, -1], use_depth2normal=False)
+    cams = [(-100.08, 29.66, 0.48, 16.74), (-62.08, -28.47, 0.47, 18.56), (35.97, -18.73, 0.51, -9.86), (-169.52, -33.08, 0.44, -9.95)]
+    want = ['below', 'last', 'none', 'last']
+    K = fixture.make_intrinsic(H, W)
+    B = len(cams)
+    RT = [fixture.make_camera(*c) for c in cams]
+    for (R, T), cls in zip(RT, want):
+        b = helpers.oracle_render(cpu_oracle, orc, H, W, K, R, T, latent, **kw)
+        assert helpers.early_break_class(b['state'], 2) == cls and int(b['mask'].sum()) > 0
+        a = helpers.hip_render(engine, H, W, K, R, T, latent, **kw)
+        res = helpers.compare(a, b, H, W, tol_depth=1e-5, tol_grad=1e-3, normal_p99=1e-4)
+        assert res['flips'] == 0
+        print(cls, res)
+    dev = engine.device
+    cfg = binding.make_cfg((H, W), K, **kw)
+    P = H * W
+    lats = torch.from_numpy(np.asarray(latent, np.float32).reshape(1, -1)).to(dev).contiguous()
+    Rs = torch.from_numpy(np.stack([r for r, _ in RT]).astype(np.float32)).to(dev).reshape(B, 9).contiguous()
+    Ts = torch.from_numpy(np.stack([t for _, t in RT]).astype(np.float32)).to(dev).contiguous()
+    rs = np.random.RandomState(13)
+    gz, gq, gd = (torch.from_numpy(rs.randn(B, P).astype(np.float32)).to(dev) for _ in range(3))
+    gn = torch.from_numpy(rs.randn(B, P, 3).astype(np.float32)).to(dev)
+    got, stats = _raw_batch(engine, cfg, lats, Rs, Ts, None, gz, gq, gd, gn)
+    for b in range(B):
+        ref, st = _raw_single(engine, cfg, lats[0], Rs[b], Ts[b], gz[b], gq[b], gd[b], gn[b])
+        for k in ref:
+            assert got[k][b].tobytes() == ref[k].tobytes(), (b, want[b], k, np.abs(got[k][b].astype(np.float64) - ref[k]).max())
+        for k in ('num_in_sphere', 'num_point_evals', 'num_valid', 'num_grad_samples'):
+            assert stats[b][k] == st[k], (b, k, stats[b][k], st[k])

@@ -667,6 +667,81 @@ def test_early_break_below_buffer_size_steps(engine, cpu_oracle, orc, fixture_de
     assert executed == (1 if marcher == 'pyramid_recursive' else 4)
 
 
+
+@pytest.mark.gpu
+def test_short_fine_break_matches_reference_golden(engine, fixture_decoder):
+    """G30: the reference's own outputs and gradients where a pyramid's fine level is shorter than buffer_size and its march breaks on that
+    level's LAST step -- the lists are padded there too (renderer.py:562-567; oracle/gen_golden_short_fine_break.py) -- and the control whose
+    rays outlive the last step. HIP at G24's bars, like G29."""
+    import test_oracle_vs_golden as tg
+    from distr import fixture
+    g = np.load(os.path.join(GOLDEN, 'g30_short_fine_break.npz'))
+    Ws, bs, latent = fixture_decoder
+    assert fixture.weights_sha256(Ws, bs) == str(g['weights_sha256'])
+    H, W = int(g['H']), int(g['W'])
+    wd, wq, wn = helpers.loss_weights(H, W, 5)
+    for name in sorted(tg.G30_CFG):
+        a = helpers.hip_render(engine, H, W, g['K'], g['R'], g['T'], g['latent'], **tg.g30_kw(g, name))
+        res = tg.check_g24(tg.g29_stable(a, g, name), g, name)
+        # the loss over the pixels both call valid: check_g24 allows one mask flip, and the control has one pixel whose min-sdf sits on the
+        # threshold (the oracle flips it too) -- its depth and normal terms alone move the loss by about 0.6
+        both = a['mask'].reshape(H, W).astype(bool) & g[name + '.mask'].astype(bool)
+        loss = [float((d.reshape(H, W) * wd)[both].sum() + (q.reshape(H, W) * wq).sum() + (n.reshape(H, W, 3) * wn)[both].sum())
+                for d, q, n in ((a['depth'], a['min_sdf'], a['normal']), (g[name + '.depth'], g[name + '.q'], g[name + '.normal']))]
+        assert abs(loss[0] - loss[1]) <= 5e-5 * abs(loss[1]), (name, loss)
+        if both.sum() == int(g[name + '.mask'].sum()) == int(a['mask'].sum()):
+            assert abs(a['loss'] - float(g[name + '.loss'])) <= 5e-5 * abs(float(g[name + '.loss'])), name
+        print('G30', name, {k: '%.1e' % v for k, v in res.items()}, 'flips', int(g[name + '.mask'].sum() + a['mask'].sum() - 2 * both.sum()))
+
+
+KEYS = ('zdepth', 'mask', 'min_sdf', 'depth', 'normal', 'g_latent', 'g_R', 'g_T')
+
+
+@pytest.mark.gpu
+def test_early_break_on_the_last_fine_step(engine, cpu_oracle, orc, fixture_decoder):
+    """The G29 scene as the default pyramid with buffer_size 7: every ray finishes on the fine level's first step. With march_step 7 that
+    step is the level's LAST (6 coarse rows + 1 fine row = buffer_size, check_cfg) and the reference still pads (renderer.py:562-567 runs
+    after every step): the render must be the one of march_step 30, whose break comes before the last step -- byte for byte, outputs and
+    gradients -- and match the oracle. Before Consts::live_end the HIP side looked for an empty live list only BEFORE the last step and
+    applied no copies here."""
+    from distr import fixture
+    H, W = 55, 79
+    _, _, latent = fixture_decoder
+    K = fixture.make_intrinsic(H, W)
+    R, T = fixture.make_camera(-73.8, -7.6, 0.475, 26.75)
+    kw = dict(buffer_size=7, ratio=1.0, marcher='pyramid_recursive', use_depth2normal=True, threshold=1.5e-3, radius=1.2, clamp_dist=0.2)
+    a7 = helpers.hip_render(engine, H, W, K, R, T, latent, march_step=7, **kw)
+    a30 = helpers.hip_render(engine, H, W, K, R, T, latent, march_step=30, **kw)
+    b7 = helpers.oracle_render(cpu_oracle, orc, H, W, K, R, T, latent, march_step=7, **kw)
+    b30 = helpers.oracle_render(cpu_oracle, orc, H, W, K, R, T, latent, march_step=30, **kw)
+    # the premise: both marches break after their first fine step and pad 6 rows; with march_step 7 that step is the last one
+    for b, fine in ((b7, 1), (b30, 24)):
+        st = b['state']
+        assert (st.fine_rows, st.pad_rows, st.live_after_last_step) == (1, 6, False), fine
+        assert helpers.early_break_class(st, fine) == ('last' if fine == 1 else 'below')
+    assert int(b7['mask'].sum()) == H * W
+    same = [k for k in KEYS if np.asarray(a7[k]).tobytes() != np.asarray(a30[k]).tobytes()]
+    assert same == [], same
+    res = helpers.compare(a7, b7, H, W, tol_depth=1e-6, tol_grad=1e-4, normal_p99=1e-5)
+    assert res['flips'] == 0
+    print(res)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('seed', range(int(os.environ.get('DISTR_TEST_RANDOM_EARLY_BREAK', '8'))))      # (soak runs: more seeds)
+def test_random_early_break_matches_oracle(engine, cpu_oracle, orc, fixture_decoder, seed):
+    """Seeded draws at the edges of the early break (helpers.early_break_draw: cameras inside the sphere, pyramids whose fine level has
+    1 .. buffer_size + 2 steps, buffer_size 2..8): breaks below buffer_size before the last step, ON the last step of a fine level shorter
+    than buffer_size, and none -- HIP vs oracle, zero mask flips (test_oracle_vs_golden.py::test_early_break_sweep_covers_every_class keeps
+    the default seeds on every class)."""
+    _, _, latent = fixture_decoder
+    H, W, K, R, T, kw, fine = helpers.early_break_draw(seed, cpu_oracle, orc, latent)
+    a = helpers.hip_render(engine, H, W, K, R, T, latent, **kw)
+    b = helpers.oracle_render(cpu_oracle, orc, H, W, K, R, T, latent, **kw)
+    res = helpers.compare(a, b, H, W, tol_depth=1e-5, tol_grad=1e-3, normal_p99=1e-4)
+    print(seed, helpers.early_break_class(b['state'], fine), (H, W), 'bs', kw['buffer_size'], 'fine', fine, res)
+    assert res['flips'] == 0
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('seed', range(int(os.environ.get('DISTR_TEST_RANDOM_OPTIONS', '6'))))      # (soak runs: more seeds)
 def test_random_options_match_oracle(engine, cpu_oracle, orc, fixture_decoder, seed):

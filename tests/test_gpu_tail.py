@@ -322,3 +322,69 @@ def test_random_configs_through_the_tail_launch(fixture_decoder, per_step_engine
     for name in ('hint', ('from0', 'from4', 'from13')[rs.randint(3)]):
         a = helpers.hip_render(tail_engines[name], H, W, K, R, T, latent, **kw)
         assert _same(a, ref) == [], (seed, name, (H, W), kw, _same(a, ref))
+
+
+# The early break (renderer.py:562-567) through every march path: name -> (H, W, cfg keywords, camera) or a seed of helpers.early_break_draw.
+# sticky_*: 480 rays (<= 496: the first fine step's tiles turn sticky) whose LAST fine step runs inside the sticky tiles, without / with rays
+# that outlive it (Consts::live_end is set there, no list is appended to)
+_EB_SCENE = dict(ratio=1.0, marcher='pyramid_recursive', radius=1.2, clamp_dist=0.2)
+_EB_PYR4 = dict(_EB_SCENE, scale_list=[8, 4, 2, 1], march_step_list=[2, 2, 2, -1], threshold=5e-4, march_step=8, buffer_size=8)
+EARLY_BREAK_PATH_CASES = {
+    'g29_ms7_bs7': (55, 79, dict(_EB_SCENE, march_step=7, buffer_size=7, threshold=1.5e-3, use_depth2normal=True), (-73.8, -7.6, 0.475, 26.75)),
+    'four_level_fine2_bs8': (55, 79, _EB_PYR4, (-73.8, -7.6, 0.475, 26.75)),
+    'sticky_last_no_survivor': (20, 24, _EB_PYR4, (-169.52, -33.08, 0.44, -9.95)),
+    'sticky_last_survivors': (20, 24, dict(_EB_PYR4, use_depth2normal=True), (35.97, -18.73, 0.51, -9.86)),
+    'seed0': 0, 'seed1': 1, 'seed4': 4,
+}
+EARLY_BREAK_PATH_CLASS = {'g29_ms7_bs7': 'last', 'four_level_fine2_bs8': 'last', 'sticky_last_no_survivor': 'last', 'sticky_last_survivors': 'none',
+                          'seed0': 'last', 'seed1': 'none', 'seed4': 'below'}
+
+
+EARLY_BREAK_VARIANTS = ({'DISTR_TAIL_FROM': 0}, {'DISTR_TAIL_FROM': 1}, {'DISTR_STICKY': 0, 'DISTR_TAIL': 0}, {'DISTR_CLUSTER': 0, 'DISTR_TAIL': 0}, {})
+
+
+@pytest.fixture(scope='module')
+def early_break_engines(fixture_decoder):
+    """One context per variant ({}: the default policy, tail launch from the hint of the configuration's previous render)."""
+    return [_engine(fixture_decoder, **v) for v in EARLY_BREAK_VARIANTS]
+
+
+@pytest.mark.parametrize('name', sorted(EARLY_BREAK_PATH_CASES))
+def test_early_break_through_every_march_path(fixture_decoder, cpu_oracle, orc, per_step_engine, early_break_engines, name):
+    """A break on the last fine step, before it, and none, through the launch-per-step path, the tail launch from step 0 and 1, without
+    sticky tiles, without clusters, and a second render that starts its tail launch from the hint of the first: every variant byte-identical
+    to the launch-per-step render (outputs and gradients), which matches the oracle. The sticky cases are checked to really run their last
+    fine step inside sticky tiles (no tail launch; every ray of the first fine step fits one launch's sticky tiles, rays reach the last)."""
+    from distr import binding, fixture
+    _, _, latent = fixture_decoder
+    c = EARLY_BREAK_PATH_CASES[name]
+    if isinstance(c, int):
+        H, W, K, R, T, kw, fine = helpers.early_break_draw(c, cpu_oracle, orc, latent)
+    else:
+        H, W, kw, cam = c
+        K = fixture.make_intrinsic(H, W)
+        R, T = fixture.make_camera(*cam)
+        fine = kw['march_step'] - (sum(kw['march_step_list'][:-1]) if 'march_step_list' in kw else 6)
+    b = helpers.oracle_render(cpu_oracle, orc, H, W, K, R, T, latent, **kw)
+    assert helpers.early_break_class(b['state'], fine) == EARLY_BREAK_PATH_CLASS[name] and int(b['mask'].sum()) > 0
+    a = helpers.hip_render(per_step_engine, H, W, K, R, T, latent, **kw)
+    res = helpers.compare(a, b, H, W, tol_depth=1e-5, tol_grad=1e-3, normal_p99=1e-4)
+    assert res['flips'] == 0
+    cfg = binding.make_cfg((H, W), K, **kw)
+    st, live = _stats(per_step_engine, cfg, latent, R, T)
+    assert st['tail_from'] == fine
+    if name.startswith('sticky'):
+        lf = live[len(live) - fine:]
+        assert fine >= 2 and 0 < lf[0] <= 496 and lf[-1] > 0, lf
+    import torch
+    for variant, eng in zip(EARLY_BREAK_VARIANTS, early_break_engines):
+        v = helpers.hip_render(eng, H, W, K, R, T, latent, **kw)
+        assert _same(v, a) == [], (name, variant, _same(v, a))
+        if 'DISTR_TAIL_FROM' in variant:
+            st, _ = _stats(eng, cfg, latent, R, T)
+            assert st['tail_from'] == min(variant['DISTR_TAIL_FROM'], fine), st
+        if not variant:
+            torch.cuda.synchronize()
+            v = helpers.hip_render(eng, H, W, K, R, T, latent, **kw)     # tail launch from the first render's hint (where it has one)
+            assert _same(v, a) == [], (name, 'hint', _same(v, a))
+    print(name, EARLY_BREAK_PATH_CLASS[name], 'fine', fine, res)

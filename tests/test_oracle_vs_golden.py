@@ -479,6 +479,68 @@ def test_oracle_early_break_matches_reference_golden(cpu_oracle, name):
     print(name, check_g24(g29_stable(b, g, name), g, name))
 
 
+
+# G30 cases as cfg keyword arguments (oracle/gen_golden_short_fine_break.py::CASES); value: (cfg keywords, fine steps, the oracle's march:
+# rows before padding, padded, a ray live after the last step)
+G30_PYR4 = dict(scale_list=[8, 4, 2, 1], march_step_list=[2, 2, 2, -1], threshold=5e-4)
+G30_CFG = {
+    'pyramid_ms7_bs7_d2n': (dict(march_step=7, buffer_size=7, threshold=1.5e-3, use_depth2normal=True), 1, (1, True, False)),
+    'four_level_fine2_bs8': (dict(march_step=8, buffer_size=8, **G30_PYR4), 2, (2, True, False)),
+    'four_level_fine1_bs7': (dict(march_step=7, buffer_size=7, **G30_PYR4), 1, (1, False, True)),
+}
+
+
+def g30_kw(g, name):
+    kw = dict(ratio=float(g['ray_marching_ratio']), radius=float(g['radius']), clamp_dist=0.2, marcher='pyramid_recursive', use_depth2normal=False)
+    kw.update(G30_CFG[name][0])
+    return kw
+
+
+def g30_premise(state, name):
+    """The oracle's march of a G30 case ends where the case says: on the last step of its fine level (padded) or with a ray still live after it."""
+    _, fine, (rows, padded, live) = G30_CFG[name]
+    assert (state.fine_rows, state.padded, state.live_after_last_step) == (rows, padded, live), (name, state.fine_rows, state.pad_rows)
+    assert len(list(state.live_counts)) == 6 + rows == 6 + fine          # 6 coarse steps, every fine step executed
+
+
+@pytest.mark.parametrize('name', sorted(G30_CFG))
+def test_oracle_short_fine_break_matches_reference_golden(cpu_oracle, name):
+    """G30 (oracle/gen_golden_short_fine_break.py): a pyramid whose fine level is shorter than buffer_size and whose march breaks on that
+    level's LAST step -- the reference pads there too (renderer.py:562-567) and selects copies of a ray's last row; the control keeps 121 rays
+    live after its last step (no padding). Outputs and gradients of the reference itself, G24's bars."""
+    import helpers
+    g = np.load(os.path.join(GOLDEN, 'g30_short_fine_break.npz'))
+    H, W = int(g['H']), int(g['W'])
+    b = helpers.oracle_render(cpu_oracle, orc, H, W, g['K'], g['R'], g['T'], g['latent'], **g30_kw(g, name))
+    g30_premise(b['state'], name)
+    assert int(b['mask'].sum()) > 4000
+    print(name, check_g24(g29_stable(b, g, name), g, name))
+
+
+EARLY_BREAK_SEEDS = 8       # the GPU sweep's default (tests/test_gpu_parity.py::test_random_early_break_matches_oracle, DISTR_TEST_RANDOM_EARLY_BREAK)
+
+
+def test_early_break_sweep_covers_every_class(cpu_oracle, fixture_decoder):
+    """The early-break sweep's generator (helpers.early_break_draw) reaches every class of the march's end within the suite's default seeds
+    -- a break below buffer_size before the last step, a break ON the last step of a fine level shorter than buffer_size, no break below
+    buffer_size -- at least twice each, with a non-empty mask, so the GPU sweep cannot drift into testing nothing."""
+    import helpers
+    _, _, latent = fixture_decoder
+    seen = {c: [] for c in helpers.EARLY_BREAK_CLASSES}
+    for seed in range(EARLY_BREAK_SEEDS):
+        H, W, K, R, T, kw, fine = helpers.early_break_draw(seed, cpu_oracle, orc, latent)
+        assert kw['march_step'] - sum(kw['march_step_list'][:-1]) == fine and 2 <= kw['buffer_size'] <= 8
+        out = cpu_oracle.render(orc.make_cfg(H, W, K, **kw), latent, R, T)
+        st = out['state']
+        c = helpers.early_break_class(st, fine)
+        if c == 'last':
+            assert fine < kw['buffer_size'] and not st.live_after_last_step
+        if int(out['mask'].sum()) > 0:
+            seen[c].append(seed)
+    print(seen)
+    assert all(len(v) >= 2 for v in seen.values()), seen
+
+
 G25_RUNS = [(n, m, d) for n in ('away', 'far', 'inside', 'nosurf') for (m, d) in (('recursive', False), ('pyramid_recursive', False), ('pyramid_recursive', True))]
 
 
