@@ -4,10 +4,12 @@ The reference evaluates the N^3 grid in 32^3-point batches with a host<->device 
 (`.cuda()` / `.cpu()` inside the loop, create_mesh.py:46-52). Here the grid lives on the GPU and one
 `distr_mlp_eval` launch (fused MFMA decoder, 64 points per workgroup) evaluates all of it; the coarse-to-fine
 variant only evaluates the full-resolution points within 1.5 coarse voxels of the surface, like
-`create_mesh_speedup`. Mesh extraction (skimage marching cubes + plyfile) is CPU tooling outside the hot path:
-`create_mesh*` call it when those packages are importable and raise otherwise.
+`create_mesh_speedup`. The mesh is extracted on the GPU too (distr.mesh.marching_cubes) and written by a plain-numpy PLY
+writer; mesher='skimage' keeps the reference's scikit-image + plyfile path where those packages are installed.
 """
 import torch
+
+from distr import mesh as _mesh
 
 from core.utils.decoder_utils import decode_sdf
 
@@ -55,14 +57,27 @@ def create_sdf_grid_speedup(decoder, latent_vec, N=256, transform=False, relaxat
     return grid.reshape(N, N, N)
 
 
-def _to_ply(sdf_grid, filename, N):
+def _to_ply(sdf_grid, filename, N, mesher='gpu'):
+    """convert_sdf_samples_to_ply (create_mesh.py:144-201): False (and no file) when the grid does not cross 0. Vertices at
+    origin + voxel_size * index with origin (-1, -1, -1), voxel_size 2 / (N - 1)."""
+    if mesher == 'skimage':
+        return _to_ply_skimage(sdf_grid, filename, N)
+    if mesher != 'gpu':
+        raise ValueError("mesher must be 'gpu' or 'skimage', got %r" % (mesher,))
+    verts, faces = _mesh.marching_cubes(sdf_grid, 0.0, origin=(-1.0, -1.0, -1.0), voxel_size=2.0 / (N - 1))
+    if faces.shape[0] == 0:
+        return False
+    _mesh.write_ply(filename, verts, faces)
+    return True
+
+
+def _to_ply_skimage(sdf_grid, filename, N):
     try:
         import plyfile
         import numpy as np
         from skimage import measure
     except Exception as e:      # noqa: BLE001
-        raise RuntimeError('mesh extraction needs scikit-image and plyfile (CPU tooling outside the rendering hot path); '
-                           'use create_sdf_grid / create_sdf_grid_speedup for the SDF volume') from e
+        raise RuntimeError("mesher='skimage' needs scikit-image and plyfile; the default mesher='gpu' needs neither") from e
     vol = sdf_grid.detach().cpu().numpy()
     try:
         verts, faces, _, _ = measure.marching_cubes(vol, level=0.0, spacing=[2.0 / (N - 1)] * 3)
@@ -75,9 +90,9 @@ def _to_ply(sdf_grid, filename, N):
     return True
 
 
-def create_mesh(decoder, latent_vec, filename, N=256, max_batch=32 ** 3, silent=False, transform=False):
-    return _to_ply(create_sdf_grid(decoder, latent_vec, N, transform), filename + '.ply', N)
+def create_mesh(decoder, latent_vec, filename, N=256, max_batch=32 ** 3, silent=False, transform=False, mesher='gpu'):
+    return _to_ply(create_sdf_grid(decoder, latent_vec, N, transform), filename + '.ply', N, mesher)
 
 
-def create_mesh_speedup(decoder, latent_vec, filename, N=256, max_batch=32 ** 3, silent=False, transform=False):
-    return _to_ply(create_sdf_grid_speedup(decoder, latent_vec, N, transform), filename + '.ply', N)
+def create_mesh_speedup(decoder, latent_vec, filename, N=256, max_batch=32 ** 3, silent=False, transform=False, mesher='gpu'):
+    return _to_ply(create_sdf_grid_speedup(decoder, latent_vec, N, transform), filename + '.ply', N, mesher)

@@ -15,6 +15,7 @@
 
 #include "distr_inst.hpp"      // distr_kernels.hpp + the big template kernels as extern templates (their code: distr_inst.hip, per group)
 #include "distr_losses.hpp"
+#include "distr_mesh.hpp"
 #include "distr_mlp_b6.hpp"
 
 using namespace distr;
@@ -1506,6 +1507,196 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
   LAUNCH_CHECK("k_warp_bwd");
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(64), 0, s, (const float*)ws, nblk, 24, g_cam);
   LAUNCH_CHECK("k_sum_partials");
+  return DISTR_OK;
+}
+
+}  // extern "C"
+
+// ---- shape evaluation (include/distr_mesh.h, kernels: distr_mesh.hpp)
+namespace {
+
+bool mc_grid_ok(int32_t nx, int32_t ny, int32_t nz) {
+  return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
+}
+
+// workspace carving: every array on a 256-byte boundary, the base aligned up (the byte counts include that slack)
+struct WsCarve {
+  uintptr_t at;
+  size_t used = 0;
+  explicit WsCarve(void* base) : at(((uintptr_t)base + 255) & ~(uintptr_t)255) {}
+  template <typename T> T* take(size_t n) {
+    T* p = (T*)(at + used);
+    used += (n * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+  size_t bytes() const { return used + 256; }
+};
+
+struct McWs {
+  uint16_t* info;
+  int *vbase, *act, *afb;
+  mesh::C3 *btot, *boff, *totals;
+  size_t bytes;
+};
+
+McWs mc_ws(void* base, int64_t P) {
+  const int64_t nb = (P + mesh::MTILE - 1) / mesh::MTILE;
+  WsCarve c(base);
+  McWs w;
+  w.info = c.take<uint16_t>(P);
+  w.vbase = c.take<int>(P);
+  w.act = c.take<int>(P);
+  w.afb = c.take<int>(P);
+  w.btot = c.take<mesh::C3>(nb);
+  w.boff = c.take<mesh::C3>(nb);
+  w.totals = c.take<mesh::C3>(1);
+  w.bytes = c.bytes();
+  return w;
+}
+
+int mc_args(distr_ctx* ctx, const float* grid, int32_t nx, int32_t ny, int32_t nz, const void* ws, size_t ws_bytes) {
+  if (!mc_grid_ok(nx, ny, nz))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "grid %d x %d x %d: marching cubes needs at least 2 values per axis and fewer than 2^31 values", nx, ny, nz);
+  if (!grid || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < distr_mc_workspace_bytes(nx, ny, nz))
+    return fail(ctx, DISTR_ERR_WORKSPACE, "marching-cubes workspace too small: %zu < %zu", ws_bytes, distr_mc_workspace_bytes(nx, ny, nz));
+  return DISTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t distr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  return mc_grid_ok(nx, ny, nz) ? mc_ws(nullptr, (int64_t)nx * ny * nz).bytes : 0;
+}
+
+int distr_mc_count(distr_ctx* ctx, const float* grid, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* nverts, int64_t* nfaces,
+                   void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = mc_args(ctx, grid, nx, ny, nz, ws, ws_bytes)) return rc;
+  if (!nverts || !nfaces) return fail(ctx, DISTR_ERR_INVALID_ARG, "null count pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const mesh::McGrid g{grid, nx, ny, nz, level, (long long)nx * ny * nz};
+  const McWs w = mc_ws(ws, g.P);
+  const long long nb = (g.P + mesh::MTILE - 1) / mesh::MTILE;
+  hipLaunchKernelGGL(mesh::k_mc_classify, dim3((unsigned)nb), dim3(mesh::MB), 0, s, g, w.info, w.btot);
+  LAUNCH_CHECK("k_mc_classify");
+  hipLaunchKernelGGL(mesh::k_mesh_top_scan<mesh::C3>, dim3(1), dim3(mesh::MB), 0, s, (const mesh::C3*)w.btot, nb, w.boff, w.totals);
+  LAUNCH_CHECK("k_mesh_top_scan");
+  mesh::C3 tot;
+  HIP_TRY(hipMemcpyAsync(&tot, w.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (tot.v > INT32_MAX || tot.f > INT32_MAX)
+    return fail(ctx, DISTR_ERR_UNSUPPORTED, "mesh of %lld vertices / %lld triangles: int32 indices cannot hold it", tot.v, tot.f);
+  *nverts = tot.v;
+  *nfaces = tot.f;
+  return DISTR_OK;
+}
+
+int distr_mc_emit(distr_ctx* ctx, const float* grid, int32_t nx, int32_t ny, int32_t nz, float level, const float* origin,
+                  const float* voxel_size, float* verts, int64_t nverts, int32_t* faces, int64_t nfaces, void* ws, size_t ws_bytes,
+                  void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = mc_args(ctx, grid, nx, ny, nz, ws, ws_bytes)) return rc;
+  if (!origin || !voxel_size) return fail(ctx, DISTR_ERR_INVALID_ARG, "origin / voxel_size (host arrays of 3) are null");
+  if (nverts < 0 || nfaces < 0 || nverts > INT32_MAX || nfaces > INT32_MAX || (nverts > 0 && !verts) || (nfaces > 0 && !faces))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "bad vertex / triangle buffers (%lld, %lld)", (long long)nverts, (long long)nfaces);
+  hipStream_t s = (hipStream_t)stream;
+  const mesh::McGrid g{grid, nx, ny, nz, level, (long long)nx * ny * nz};
+  const McWs w = mc_ws(ws, g.P);
+  const long long nb = (g.P + mesh::MTILE - 1) / mesh::MTILE;
+  const mesh::McOut o{origin[0], origin[1], origin[2], voxel_size[0], voxel_size[1], voxel_size[2], verts, nverts, faces, nfaces};
+  hipLaunchKernelGGL(mesh::k_mc_compact, dim3((unsigned)nb), dim3(mesh::MB), 0, s, g, (const uint16_t*)w.info, (const mesh::C3*)w.boff,
+                     w.act, w.afb, w.vbase, o);
+  LAUNCH_CHECK("k_mc_compact");
+  const long long fblocks = std::min<long long>((g.P + mesh::MB - 1) / mesh::MB, 4096);
+  hipLaunchKernelGGL(mesh::k_mc_faces, dim3((unsigned)fblocks), dim3(mesh::MB), 0, s, g, (const uint16_t*)w.info, (const int*)w.act,
+                     (const int*)w.afb, (const int*)w.vbase, (const mesh::C3*)w.totals, o);
+  LAUNCH_CHECK("k_mc_faces");
+  return DISTR_OK;
+}
+
+size_t distr_sample_workspace_bytes(int64_t nfaces) {
+  if (nfaces < 1) return 0;
+  const int64_t nb = (nfaces + mesh::MTILE - 1) / mesh::MTILE;
+  WsCarve c(nullptr);
+  c.take<double>(nfaces);
+  c.take<double>(nb);
+  c.take<double>(nb);
+  c.take<double>(1);
+  return c.bytes();
+}
+
+int distr_sample_surface(distr_ctx* ctx, const float* verts, int64_t nverts, const int32_t* faces, int64_t nfaces, int64_t n, uint64_t seed,
+                         float* points, int32_t* face_index, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (nverts < 1 || nfaces < 1 || nfaces > INT32_MAX || n < 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "sampling needs a mesh with vertices and triangles (%lld, %lld) and n >= 0", (long long)nverts, (long long)nfaces);
+  if (!verts || !faces || !ws || (n > 0 && (!points || !face_index))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < distr_sample_workspace_bytes(nfaces)) return fail(ctx, DISTR_ERR_WORKSPACE, "sampling workspace too small");
+  if (n == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const long long nb = (nfaces + mesh::MTILE - 1) / mesh::MTILE;
+  WsCarve c(ws);
+  double* cdf = c.take<double>(nfaces);
+  double* btot = c.take<double>(nb);
+  double* boff = c.take<double>(nb);
+  double* total = c.take<double>(1);
+  const mesh::SurfMesh m{verts, nverts, faces, nfaces};
+  hipLaunchKernelGGL(mesh::k_area_scan<false>, dim3((unsigned)nb), dim3(mesh::MB), 0, s, m, btot, (const double*)nullptr, (double*)nullptr);
+  LAUNCH_CHECK("k_area_scan<false>");
+  hipLaunchKernelGGL(mesh::k_mesh_top_scan<double>, dim3(1), dim3(mesh::MB), 0, s, (const double*)btot, nb, boff, total);
+  LAUNCH_CHECK("k_mesh_top_scan");
+  hipLaunchKernelGGL(mesh::k_area_scan<true>, dim3((unsigned)nb), dim3(mesh::MB), 0, s, m, (double*)nullptr, (const double*)boff, cdf);
+  LAUNCH_CHECK("k_area_scan<true>");
+  hipLaunchKernelGGL(mesh::k_sample, dim3((unsigned)((n + mesh::MB - 1) / mesh::MB)), dim3(mesh::MB), 0, s, m, (const double*)cdf, n, seed,
+                     points, face_index);
+  LAUNCH_CHECK("k_sample");
+  return DISTR_OK;
+}
+
+size_t distr_nearest_workspace_bytes(int64_t na) {
+  const int64_t nb = std::max<int64_t>(1, (na + mesh::MTILE - 1) / mesh::MTILE);
+  WsCarve c(nullptr);
+  c.take<mesh::D2>(nb);
+  c.take<mesh::D2>(nb);
+  return c.bytes();
+}
+
+int distr_nearest_sqdist(distr_ctx* ctx, const float* a, int64_t na, const float* b, int64_t nb, float* d2, double* sums, void* ws,
+                         size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (na < 0 || nb < 1 || na > INT32_MAX || nb > INT32_MAX) return fail(ctx, DISTR_ERR_INVALID_ARG, "point counts %lld, %lld (need na >= 0, nb >= 1)", (long long)na, (long long)nb);
+  if (!b || !ws || (na > 0 && (!a || !d2))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < distr_nearest_workspace_bytes(na)) return fail(ctx, DISTR_ERR_WORKSPACE, "nearest-distance workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const long long ablocks = (na + mesh::MB - 1) / mesh::MB;
+  if (na > 0) {
+    hipLaunchKernelGGL(mesh::k_fill_inf, dim3((unsigned)ablocks), dim3(mesh::MB), 0, s, (unsigned*)d2, (long long)na);
+    LAUNCH_CHECK("k_fill_inf");
+    // B is split into chunks (grid.y) until about 2048 workgroups are in flight: 30 000 points of A alone fill only 118
+    const long long tiles = (nb + mesh::NN_TILE - 1) / mesh::NN_TILE;
+    const long long split = std::max<long long>(1, std::min<long long>({tiles, (2048 + ablocks - 1) / ablocks, 1024}));
+    const long long chunk = (tiles + split - 1) / split * mesh::NN_TILE;
+    const long long ysz = (nb + chunk - 1) / chunk;
+    hipLaunchKernelGGL(mesh::k_nearest, dim3((unsigned)ablocks, (unsigned)ysz), dim3(mesh::MB), 0, s, a, (long long)na, b, (long long)nb,
+                       chunk, (unsigned*)d2);
+    LAUNCH_CHECK("k_nearest");
+  }
+  if (sums) {
+    const long long nblk = std::max<long long>(1, (na + mesh::MTILE - 1) / mesh::MTILE);
+    WsCarve c(ws);
+    mesh::D2* btot = c.take<mesh::D2>(nblk);
+    mesh::D2* boff = c.take<mesh::D2>(nblk);
+    hipLaunchKernelGGL(mesh::k_dist_sums, dim3((unsigned)nblk), dim3(mesh::MB), 0, s, (const float*)d2, (long long)na, btot);
+    LAUNCH_CHECK("k_dist_sums");
+    hipLaunchKernelGGL(mesh::k_mesh_top_scan<mesh::D2>, dim3(1), dim3(mesh::MB), 0, s, (const mesh::D2*)btot, nblk, boff, (mesh::D2*)sums);
+    LAUNCH_CHECK("k_mesh_top_scan");
+  }
   return DISTR_OK;
 }
 

@@ -25,6 +25,9 @@ EXPORTS = ['distr_version', 'distr_abi_version', 'distr_create_abi', 'distr_dest
            'distr_warp_loss_forward', 'distr_warp_loss_backward', 'distr_set_color_decoder', 'distr_color_eval', 'distr_debug_xchg_ts', 'distr_mlp_backward_workspace_bytes', 'distr_mlp_backward',
            'distr_profile_read_list', 'distr_get_live_counts', 'distr_color_backward',
            'distr_render_forward_batch', 'distr_render_backward_batch', 'distr_render_normal_batch', 'distr_mlp_eval_bf16x6', 'distr_mlp_eval_f16x3']
+# shape evaluation (include/distr_mesh.h, included by distr.h): marching cubes, surface sampling, nearest-point distances
+MESH_EXPORTS = ['distr_mc_workspace_bytes', 'distr_mc_count', 'distr_mc_emit', 'distr_sample_workspace_bytes', 'distr_sample_surface',
+                'distr_nearest_workspace_bytes', 'distr_nearest_sqdist']
 
 ABI_VERSION = 6                                   # DISTR_ABI_VERSION of include/distr.h this mirror was written against
 MAX_VIEWS = 64                                    # DISTR_MAX_VIEWS
@@ -102,17 +105,18 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp')
+           'distr_dense_asm.hpp', 'distr_mesh.hpp')
+HEADERS = ('distr.h', 'distr_mesh.h')                    # include/: the C ABI
 INST_GROUPS = 6            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
 
 def source_digest():
-    """sha256 over the native sources libdistr.so is built from (csrc/ + include/distr.h, fixed order, name + bytes). Evidence files
+    """sha256 over the native sources libdistr.so is built from (csrc/ + the include/ headers, fixed order, name + bytes). Evidence files
     that describe the kernels (profiles/rNN_traffic.json) record it; bench.py only quotes them for the same digest."""
     import hashlib
     h = hashlib.sha256()
-    for path in [os.path.join(CSRC, f) for f in SOURCES] + [os.path.join(_HERE, '..', '..', 'include', 'distr.h')]:
+    for path in [os.path.join(CSRC, f) for f in SOURCES] + [os.path.join(_HERE, '..', '..', 'include', f) for f in HEADERS]:
         h.update(os.path.basename(path).encode() + b'\0')
         with open(path, 'rb') as f:
             h.update(f.read())
@@ -194,7 +198,7 @@ def build_library(force=False, verbose=False, jobs=None, only=None):
     at a time: default min(cores, 7); DISTR_BUILD_JOBS overrides), then the link. Returns the .so path. only = labels to recompile (the other
     objects are reused as they are: local iteration on one kernel group; never used by build())."""
     srcs = [os.path.join(CSRC, f) for f in SOURCES]
-    srcs.append(os.path.join(_HERE, '..', '..', 'include', 'distr.h'))
+    srcs += [os.path.join(_HERE, '..', '..', 'include', f) for f in HEADERS]
     if not force and not only and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     steps, link = build_commands()
@@ -304,6 +308,17 @@ def lib():
             L.distr_mlp_backward_workspace_bytes.argtypes = [C.c_int64]
             L.distr_mlp_backward_workspace_bytes.restype = C.c_size_t
             L.distr_mlp_backward.argtypes = [vp, fp, fp, C.c_int64, fp, C.c_float, fp, fp, vp, C.c_size_t, vp]
+            i32, i64, i64p, f3 = C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_float)
+            L.distr_mc_workspace_bytes.argtypes = [i32, i32, i32]
+            L.distr_mc_workspace_bytes.restype = C.c_size_t
+            L.distr_mc_count.argtypes = [vp, fp, i32, i32, i32, C.c_float, i64p, i64p, vp, C.c_size_t, vp]
+            L.distr_mc_emit.argtypes = [vp, fp, i32, i32, i32, C.c_float, f3, f3, fp, i64, vp, i64, vp, C.c_size_t, vp]
+            L.distr_sample_workspace_bytes.argtypes = [i64]
+            L.distr_sample_workspace_bytes.restype = C.c_size_t
+            L.distr_sample_surface.argtypes = [vp, fp, i64, vp, i64, i64, C.c_uint64, fp, vp, vp, C.c_size_t, vp]
+            L.distr_nearest_workspace_bytes.argtypes = [i64]
+            L.distr_nearest_workspace_bytes.restype = C.c_size_t
+            L.distr_nearest_sqdist.argtypes = [vp, fp, i64, fp, i64, fp, vp, vp, C.c_size_t, vp]
             _lib = L
     return _lib
 

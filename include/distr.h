@@ -364,4 +364,8 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #ifdef __cplusplus
 }
 #endif
+
+/* shape evaluation after the render path: marching cubes, surface sampling, chamfer distances */
+#include "distr_mesh.h"
+
 #endif /* DISTR_H_ */
