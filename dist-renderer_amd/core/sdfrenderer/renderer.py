@@ -92,7 +92,8 @@ class SDFRenderer(object):
         self.imgmap_init = torch.zeros(h, w, device=tdev)
         self.transform_matrix = torch.from_numpy(self._M_np).float().to(tdev)
         self.calib_map = self.normalize_vectors(self.homo_calib)[2, :]
-        functions.get_engine(decoder, self.device)          # packs + uploads the weights now (fails early on an unsupported decoder)
+        eng = functions.get_engine(decoder, self.device)    # packs + uploads the weights now (fails early on an unsupported decoder)
+        functions.check_split_arith(eng, self.arith)
         self.last_stats = None
 
     @property

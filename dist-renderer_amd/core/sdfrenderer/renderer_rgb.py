@@ -8,7 +8,7 @@ colour image is differentiable like the reference's (golden G26): `render_color`
 code, the shape code and -- through the surface points -- the camera on the tape (ColorDecodeFunction -> distr_color_backward)."""
 import torch
 
-from distr import functions
+from distr import decoder_pack, functions
 
 from .renderer import SDFRenderer
 
@@ -20,6 +20,10 @@ class SDFRenderer_color(SDFRenderer):
         super(SDFRenderer_color, self).__init__(decoder, intrinsic, img_hw=img_hw, march_step=march_step, buffer_size=buffer_size,
                                                 ray_marching_ratio=ray_marching_ratio, max_sample_dist=max_sample_dist,
                                                 threshold=threshold, use_gpu=use_gpu, is_eval=is_eval)
+        nlat = functions.get_engine(decoder, self.device).latent_size
+        if nlat != 256:
+            raise decoder_pack.UnsupportedDecoder('SDFRenderer_color is built for shape decoders of code length 256 only; this decoder '
+                                                  'has code length %d' % nlat)
         self.decoder_color = decoder_color.eval() if is_eval else decoder_color
         functions.get_color_engine(self.decoder_color, self.device)
 

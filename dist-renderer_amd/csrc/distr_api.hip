@@ -271,6 +271,9 @@ int check_cfg(distr_ctx* ctx, const distr_render_cfg* c) {
                 c->buffer_size, coarse_rows + fine, c->march_step);
   if (!(c->radius > 0.f) || !(c->threshold >= 0.f)) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad radius/threshold");
   if (c->arith != DISTR_ARITH_F32 && c->arith != DISTR_ARITH_BF16X6 && c->arith != DISTR_ARITH_F16X3) return fail(ctx, DISTR_ERR_INVALID_ARG, "unknown arith %d", c->arith);
+  if (c->arith != DISTR_ARITH_F32 && ctx->has_decoder && ctx->D.nlat != LAT)
+    return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith %s: the split arithmetics are built for code length %d only (this decoder: %d); use f32",
+                c->arith == DISTR_ARITH_BF16X6 ? "bf16x6" : "f16x3", LAT, ctx->D.nlat);
   if (c->arith == DISTR_ARITH_F16X3 && ctx->has_decoder && !ctx->h3_ok)
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
   if (c->rows != 0) {
@@ -564,12 +567,19 @@ void distr_destroy(distr_ctx* ctx) {
 const char* distr_last_error(const distr_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 // Packs one DeepSDF-8x512-shaped decoder for the tile kernels. nlat = latent length (the latent columns of lin0 / lin4 are
-// folded into per-call constants, so the tile itself never sees them); nout = rows of lin8 (1: SDF, 3: colour).
-static int build_decoder(distr_ctx* ctx, int nlat, int nout, const float* w, size_t n_floats, float** dev_buf, DecoderDev& D,
+// folded into per-call constants, so the tile itself never sees them); rows3 = real rows of lin3 (509 - C for an SDF decoder of code
+// length C, 253 for the colour decoder); nout = rows of lin8 (1: SDF, 3: colour). Narrow layout (rows3 <= 253): the tile's lin3 has
+// 256 rows: the real ones, zero rows up to 253 (ReLU(0) = 0, and they meet zero lin4 columns, so values stay exact), xyz at 253..255 --
+// lin4's K stays 256. Wide layout (rows3 > 253, code length < 256): lin3 has 512 rows the same way (real, zero up to 509, xyz at
+// 509..511) and lin4 K = 512. The split-bf16 / split-f16 planes are packed for C = 256 only (the only decoders they may run).
+static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const float* w, size_t n_floats, float** dev_buf, DecoderDev& D,
                          DecoderDev16* D16, DecoderB6* B6 = nullptr, uint32_t** dev_buf_b6 = nullptr, DecoderH3* H3 = nullptr,
                          bool* h3_ok = nullptr) {
-  const int in0 = nlat + 3, in4 = 256 + nlat;
-  const int OUT[9] = {512, 512, 512, 253, 512, 512, 512, 512, nout};
+  if (rows3 < 1 || rows3 > 509) return fail(ctx, DISTR_ERR_UNSUPPORTED, "lin3 with %d rows does not fit the 509-row tile", rows3);
+  const bool wide = rows3 > 253;
+  const int R3 = wide ? 509 : 253;         // row of lin3's output (and column of lin4) where xyz is carried
+  const int in0 = nlat + 3, in4 = rows3 + nlat + 3;
+  const int OUT[9] = {512, 512, 512, rows3, 512, 512, 512, 512, nout};
   const int IN[9] = {in0, 512, 512, 512, in4, 512, 512, 512, 512};
   size_t need = 0;
   for (int l = 0; l < 9; ++l) need += (size_t)OUT[l] * IN[l] + OUT[l];
@@ -579,16 +589,16 @@ static int build_decoder(distr_ctx* ctx, int nlat, int nout, const float* w, siz
   for (int l = 0; l < 9; ++l) { W[l] = p; p += (size_t)OUT[l] * IN[l]; b[l] = p; p += OUT[l]; }
 
   // padded dense matrices [O][K] of the eight MFMA layers
-  const int Kp[8] = {8, 512, 512, 512, 256, 512, 512, 512};
-  const int Op[8] = {512, 512, 512, 256, 512, 512, 512, 512};
+  const int Kp[8] = {8, 512, 512, 512, wide ? 512 : 256, 512, 512, 512};
+  const int Op[8] = {512, 512, 512, wide ? 512 : 256, 512, 512, 512, 512};
   std::vector<std::vector<float>> Wp(8);
   for (int l = 0; l < 8; ++l) Wp[l].assign((size_t)Op[l] * Kp[l], 0.f);
   for (int o = 0; o < 512; ++o) for (int k = 0; k < 3; ++k) Wp[0][(size_t)o * 8 + k] = W[0][(size_t)o * in0 + nlat + k];
   for (int l : {1, 2, 5, 6, 7}) memcpy(Wp[l].data(), W[l], sizeof(float) * 512 * 512);
-  for (int o = 0; o < 253; ++o) memcpy(&Wp[3][(size_t)o * 512], &W[3][(size_t)o * 512], sizeof(float) * 512);
+  for (int o = 0; o < rows3; ++o) memcpy(&Wp[3][(size_t)o * 512], &W[3][(size_t)o * 512], sizeof(float) * 512);
   for (int o = 0; o < 512; ++o) {
-    for (int k = 0; k < 253; ++k) Wp[4][(size_t)o * 256 + k] = W[4][(size_t)o * in4 + k];
-    for (int k = 0; k < 3; ++k) Wp[4][(size_t)o * 256 + 253 + k] = W[4][(size_t)o * in4 + 253 + nlat + k];
+    for (int k = 0; k < rows3; ++k) Wp[4][(size_t)o * Kp[4] + k] = W[4][(size_t)o * in4 + k];
+    for (int k = 0; k < 3; ++k) Wp[4][(size_t)o * Kp[4] + R3 + k] = W[4][(size_t)o * in4 + rows3 + nlat + k];
   }
 
   std::vector<float> host;
@@ -619,7 +629,7 @@ static int build_decoder(distr_ctx* ctx, int nlat, int nout, const float* w, siz
   const size_t o_W0lat_t = reserve((size_t)nlat * HID), o_W4lat_t = reserve((size_t)nlat * HID);
   const size_t o_W0lat = reserve((size_t)HID * nlat), o_W4lat = reserve((size_t)HID * nlat);
   for (int o = 0; o < HID; ++o) for (int k = 0; k < nlat; ++k) {
-    const float v0 = W[0][(size_t)o * in0 + k], v4 = W[4][(size_t)o * in4 + 253 + k];
+    const float v0 = W[0][(size_t)o * in0 + k], v4 = W[4][(size_t)o * in4 + rows3 + k];
     host[o_W0lat_t + (size_t)k * HID + o] = v0; host[o_W0lat + (size_t)o * nlat + k] = v0;
     host[o_W4lat_t + (size_t)k * HID + o] = v4; host[o_W4lat + (size_t)o * nlat + k] = v4;
   }
@@ -699,14 +709,25 @@ static int build_decoder(distr_ctx* ctx, int nlat, int nout, const float* w, siz
   return DISTR_OK;
 }
 
+// the shape decoder runs the wide tile layout (code length < 256: k_march / k_bwd<..., WIDE>)
+static inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
+
 int distr_set_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, const float* w, size_t n_floats) {
   if (!ctx || !desc || !w) return fail(ctx, DISTR_ERR_INVALID_ARG, "null argument");
   EntryGuard guard_(ctx);
   if (desc->struct_size != sizeof(distr_decoder_desc)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_decoder_desc.struct_size is %u, expected %zu", desc->struct_size, sizeof(distr_decoder_desc));
-  if (desc->latent_size != LAT || desc->hidden != HID || desc->num_linear != 9 || desc->latent_in != 4)
+  if (desc->latent_size < 1 || desc->latent_size > MAX_LAT || desc->hidden != HID || desc->num_linear != 9 || desc->latent_in != 4)
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "decoder (latent %d, hidden %d, %d linears, latent_in %d) unsupported: kernels are "
-                "specialised for DeepSDF 8x512 (latent 256, latent_in=[4])", desc->latent_size, desc->hidden, desc->num_linear, desc->latent_in);
-  int rc = build_decoder(ctx, LAT, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok);
+                "specialised for DeepSDF 8x512 with latent_in=[4] and a code length of 1..%d", desc->latent_size, desc->hidden,
+                desc->num_linear, desc->latent_in, MAX_LAT);
+  const int nlat = desc->latent_size;
+  int rc;
+  if (nlat == LAT) {
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok);
+  } else {   // no split-arithmetic planes: bf16x6 / f16x3 refuse other code lengths (check_cfg, distr_mlp_eval_*)
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16);
+    if (!rc && ctx->dec_buf_b6) { HIP_TRY(hipFree(ctx->dec_buf_b6)); ctx->dec_buf_b6 = nullptr; ctx->B6 = DecoderB6{}; ctx->H3 = DecoderH3{}; ctx->h3_ok = false; }
+  }
   if (rc) return rc;
   ctx->has_decoder = true;
   return DISTR_OK;
@@ -719,7 +740,7 @@ int distr_set_color_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, cons
   if (desc->latent_size <= LAT || desc->latent_size > 4096 || desc->hidden != HID || desc->num_linear != 9 || desc->latent_in != 4)
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "colour decoder (latent %d, hidden %d, %d linears, latent_in %d) unsupported: expected the "
                 "DeepSDF 8x512 shape with latent = 256 + color_size and last_dim = 3", desc->latent_size, desc->hidden, desc->num_linear, desc->latent_in);
-  int rc = build_decoder(ctx, desc->latent_size, 3, w, n_floats, &ctx->dec_buf_color, ctx->DC, nullptr);
+  int rc = build_decoder(ctx, desc->latent_size, 253, 3, w, n_floats, &ctx->dec_buf_color, ctx->DC, nullptr);
   if (rc) return rc;
   ctx->has_color = true;
   return DISTR_OK;
@@ -807,7 +828,7 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   int rc = check_cfg(ctx, cfg);
   if (rc) return rc;
   if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
-  if (lat_stride != 0 && lat_stride < LAT) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride must be 0 (shared shape code) or >= %d", LAT);
+  if (lat_stride != 0 && lat_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride must be 0 (shared shape code) or >= %d", ctx->D.nlat);
   if (!latent || !R || !T || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
   View V;
   const size_t single = make_view(*cfg, ws, V, ctx->save_masks, nviews);
@@ -823,7 +844,10 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
 
   // persistent tail launch: from which full-resolution step on (see distr_ctx::tail)
   int32_t* hint_dev = nullptr;
-  if (cfg->marcher != DISTR_MARCH_TRIVIAL && cfg->arith == DISTR_ARITH_F32 && ctx->tail && !cfg->concurrent && ctx->tail16_threshold > 0) {
+  // wide decoders (code length < 256) render launch-per-step on 64-ray tiles: no tail launch, no cluster / sticky / 16- / 32-ray tiles
+  // (their generated loops are laid out for the narrow lin3); values are the same, only the schedule differs
+  const bool wide = wide_decoder(ctx);
+  if (cfg->marcher != DISTR_MARCH_TRIVIAL && cfg->arith == DISTR_ARITH_F32 && ctx->tail && !cfg->concurrent && ctx->tail16_threshold > 0 && !wide) {
     bool capturing = false;
     {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -859,10 +883,10 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   const bool h3 = cfg->arith == DISTR_ARITH_F16X3;
   const bool recursive = cfg->marcher != DISTR_MARCH_TRIVIAL;     // live-ray lists + tile-size split (fine_split)
   const int t32 = ctx->hybrid_threshold, t16 = b6 ? 0 : std::min(ctx->tail16_threshold, ctx->hybrid_threshold);
-  A.t16 = recursive ? t16 : 0; A.t32 = recursive ? t32 : 0; A.which = 64;
+  A.t16 = (recursive && !wide) ? t16 : 0; A.t32 = (recursive && !wide) ? t32 : 0; A.which = 64;
   // f(origin) of every view (sample point of padded rows) is evaluated by nviews extra workgroups of ONE march launch: for the
   // recursive marchers they ride on the 16-ray role of the last step (free: a tail step); 'trivial' puts them on its first launch
-  distr_ctx::XRegion* xr = (recursive && !b6) ? xchg_region(ctx, s) : nullptr;
+  distr_ctx::XRegion* xr = (recursive && !b6 && !wide) ? xchg_region(ctx, s) : nullptr;
   auto up8 = [](int64_t v) { return (int32_t)((v + 7) / 8 * 8); };
   for (int l = V.nlev - 1; l >= 1; --l) {
     hipLaunchKernelGGL(k_coarse_init, gridv(V.lv[l].n), dim3(256), 0, s, V, l);
@@ -872,15 +896,18 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
       // tile size of a coarse level from the (host-known) pixel count of all views: a level that fits one round of 16- / 32-ray
       // tiles runs on those (small images: 111 / 212 us per step instead of 380 us)
       const int64_t ln = V.lv[l].n;
-      const bool c16 = !b6 && nviews * pad_to(ln, 16) <= t16;
-      const int crb = (nviews * pad_to(ln, 32) <= t32) ? 1 : 2;
+      const bool c16 = !b6 && !wide && nviews * pad_to(ln, 16) <= t16;
+      const int crb = (!wide && nviews * pad_to(ln, 32) <= t32) ? 1 : 2;
       const int ctile = c16 ? 16 : 32 * crb;
       unsigned tiles = NV * (unsigned)((ln + ctile - 1) / ctile);
       A.xc = next_xchg(c16 ? xr : nullptr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, 1, false, ctx->xchg_sc1);
       A.xc.spread = ctx->cluster_spread;
       if (c16 && xr) tiles = std::max(tiles, 256u);      // cluster tiles: up to 8 workgroups per 16 rays
       timer.begin();
-      if (c16) {
+      if (wide) {
+        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_COARSE, 2, true, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
+        else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, false, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
+      } else if (c16) {
         if (V.save_masks) hipLaunchKernelGGL((k_march16<MODE_COARSE, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D, ctx->D16);
         else hipLaunchKernelGGL((k_march16<MODE_COARSE, false>), dim3(tiles), dim3(NTHREADS), 0, s, A, D, ctx->D16);
       } else if (h3) {
@@ -930,11 +957,15 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
       LAUNCH_CHECK("k_tail");
       break;
     }
-    if (!recursive) {
-      // 'trivial': every in-sphere ray, every step, on 64-ray tiles
-      A.origin_tile = (st == 0) ? 1 : 0;
+    if (!recursive || wide) {
+      // 'trivial': every in-sphere ray, every step, on 64-ray tiles. Wide decoders: also the recursive marchers' live-ray lists (t16 =
+      // t32 = 0: fine_split hands every ray to the 64-ray role), f(origin) on the last step like k_step
+      A.origin_tile = (recursive ? st == V.fine_steps - 1 : st == 0) ? 1 : 0;
       const unsigned tiles = NV * (unsigned)((P + 63) / 64) + (A.origin_tile ? NV : 0u);
-      if (h3) {
+      if (wide) {
+        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
+        else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
+      } else if (h3) {
         if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
         else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
       } else if (b6) {
@@ -991,7 +1022,8 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
       BwdArgs B;
       memset(&B, 0, sizeof(B));
       B.V = V; B.zdepth = V.zdepth_s; B.zstride = V.vstride;
-      hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
+      if (wide) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
+      else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
       LAUNCH_CHECK("k_bwd<pointgrad>");
       hipLaunchKernelGGL(k_normal_finish, gridv(P), dim3(256), 0, s, V, normal, (float*)nullptr, 1);
       LAUNCH_CHECK("k_normal_finish");
@@ -1041,10 +1073,14 @@ int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews
   memset(&B, 0, sizeof(B));
   B.V = V; B.samples = W.samples; B.partial = W.partial; B.bstride = W.bstride; B.B6 = ctx->B6; B.H3 = ctx->H3;
   // tile-size split of every view's sample list (bwd_range): full rounds on 64-sample tiles, a small remainder on 32-sample tiles
+  const bool wide = wide_decoder(ctx);       // (wide decoders: the same tile split, so the same partial rows and reduction order)
   const bool bsplit = V.save_masks != 0;
   if (bsplit) {
     B.split = 1;
-    if (cfg->arith == DISTR_ARITH_F16X3) {      // the dX chain in the arithmetic of the forward it differentiates
+    if (wide) {
+      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2, 0, true>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
+      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1, 0, true>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
+    } else if (cfg->arith == DISTR_ARITH_F16X3) {      // the dX chain in the arithmetic of the forward it differentiates
       hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2, 2>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
       hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1, 2>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
     } else if (cfg->arith == DISTR_ARITH_BF16X6) {
@@ -1054,6 +1090,8 @@ int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews
       hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
       hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
     }
+  } else if (wide) {
+    hipLaunchKernelGGL((k_bwd<BWD_FULL, 2, 0, true>), dim3(NV * tiles), dim3(NTHREADS), 0, s, B, D);
   } else {
     hipLaunchKernelGGL((k_bwd<BWD_FULL, 2>), dim3(NV * tiles), dim3(NTHREADS), 0, s, B, D);     // DISTR_SAVE_MASKS=0: recompute the forward
   }
@@ -1072,7 +1110,7 @@ int render_normal_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, 
   int rc = check_cfg(ctx, cfg);
   if (rc) return rc;
   if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
-  if (lat_stride != 0 && lat_stride < LAT) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride must be 0 (shared shape code) or >= %d", LAT);
+  if (lat_stride != 0 && lat_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride must be 0 (shared shape code) or >= %d", ctx->D.nlat);
   if (!latent || !R || !T || !zdepth || !mask || !normal3xP || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
   View V;
   const size_t single = make_view(*cfg, ws, V, ctx->save_masks, nviews);
@@ -1092,7 +1130,8 @@ int render_normal_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, 
   BwdArgs B;
   memset(&B, 0, sizeof(B));
   B.V = V; B.zdepth = zdepth; B.zstride = (int64_t)P * sizeof(float);
-  hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
+  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
+  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
   LAUNCH_CHECK("k_bwd<pointgrad>");
   hipLaunchKernelGGL(k_normal_finish, dim3((unsigned)((P + 255) / 256), NV), dim3(256), 0, s, V, (float*)nullptr, normal3xP, 0);
   LAUNCH_CHECK("k_normal_finish");
@@ -1172,7 +1211,9 @@ int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   timer.begin();
   // a point list that fits one wave of 16-ray tiles runs on those (107 us instead of a 380 us 64-ray tile: decode_sdf on a few
   // thousand points is latency-bound); same values bit for bit
-  if (n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold))
+  if (wide_decoder(ctx))
+    hipLaunchKernelGGL((k_march<MODE_EVAL, 2, false, 0, true>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, A, ctx->D);
+  else if (n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold))
     hipLaunchKernelGGL((k_march16<MODE_EVAL, false>), dim3((unsigned)((n + 15) / 16)), dim3(NTHREADS), 0, s, A, ctx->D, ctx->D16);
   else hipLaunchKernelGGL((k_march<MODE_EVAL, 2, false>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, A, ctx->D);
   timer.end();
@@ -1185,6 +1226,7 @@ int distr_mlp_eval_bf16x6(distr_ctx* ctx, const float* latent, const float* xyz,
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "bf16x6: built for code length %d only (this decoder: %d); use f32", LAT, ctx->D.nlat);
   if (n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
   if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   if (n == 0) return DISTR_OK;
@@ -1205,6 +1247,7 @@ int distr_mlp_eval_f16x3(distr_ctx* ctx, const float* latent, const float* xyz, 
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: built for code length %d only (this decoder: %d); use f32", LAT, ctx->D.nlat);
   if (!ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
   if (n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
   if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
@@ -1236,7 +1279,8 @@ int distr_mlp_grad(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   BwdArgs B;
   memset(&B, 0, sizeof(B));
   B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.out_sdf = sdf; B.out_g = grad;
-  hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, B, ctx->D);
+  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, B, ctx->D);
+  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, B, ctx->D);
   LAUNCH_CHECK("k_bwd<pointgrad>");
   return DISTR_OK;
 }
@@ -1255,7 +1299,7 @@ int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, in
   if (ws_bytes < distr_mlp_backward_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
-    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, LAT * sizeof(float), s));
+    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)ctx->D.nlat * sizeof(float), s));
     return DISTR_OK;
   }
   float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
@@ -1266,7 +1310,8 @@ int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, in
   memset(&B, 0, sizeof(B));
   B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.coef = g_sdf; B.clamp = clamp; B.partial = partial; B.out_g = g_xyz;
   const unsigned tiles = (unsigned)((n + 63) / 64);
-  hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(tiles), dim3(NTHREADS), 0, s, B, ctx->D);
+  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, B, ctx->D);
+  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(tiles), dim3(NTHREADS), 0, s, B, ctx->D);
   LAUNCH_CHECK("k_bwd<pointgrad+latent>");
   if (g_latent) {
     hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->D, g_latent);
@@ -1280,6 +1325,7 @@ int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz,
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
   if (n <= 0 || !xyz || !out || !latent || !ws || layer < 0 || layer > 7) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
   if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -1296,6 +1342,7 @@ int distr_debug_tile_timing(distr_ctx* ctx, const float* latent, const float* xy
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
   if (n <= 0 || !xyz || !sdf_out || !ts_out || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
   if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;

@@ -26,6 +26,8 @@ namespace distr {
 #define DISTR_K_MARCH(M, RB, K, AR) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR>(MarchArgs, DecoderDev);
 #define DISTR_K_MARCH16(M, K) DISTR_INST_DEF __global__ void k_march16<M, K>(MarchArgs, DecoderDev, DecoderDev16);
 #define DISTR_K_BWD(M, RB, AR) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR>(BwdArgs, DecoderDev);
+#define DISTR_K_MARCH_W(M, K) DISTR_INST_DEF __global__ void k_march<M, 2, K, 0, true>(MarchArgs, DecoderDev);
+#define DISTR_K_BWD_W(M, RB) DISTR_INST_DEF __global__ void k_bwd<M, RB, 0, true>(BwdArgs, DecoderDev);
 
 #if DISTR_GROUP_ON(1)      // the full-resolution step of the exact-f32 march (the headline kernel)
 DISTR_K_STEP(true, 0) DISTR_K_STEP(false, 0)
@@ -53,7 +55,12 @@ DISTR_K_BWD(BWD_FULL, 2, 0) DISTR_K_BWD(BWD_POINTGRAD, 2, 0)
 DISTR_K_BWD(BWD_SAVED, 1, 0) DISTR_K_BWD(BWD_SAVED, 1, 1) DISTR_K_BWD(BWD_SAVED, 1, 2)
 DISTR_K_BWD(BWD_SAVED, 2, 0) DISTR_K_BWD(BWD_SAVED, 2, 1) DISTR_K_BWD(BWD_SAVED, 2, 2)
 #endif
+#if DISTR_GROUP_ON(7)      // the wide layout (code length < 256): 64-ray march tiles; 64- and 32-sample backward tiles
+DISTR_K_MARCH_W(MODE_EVAL, false) DISTR_K_MARCH_W(MODE_COARSE, true) DISTR_K_MARCH_W(MODE_COARSE, false)
+DISTR_K_MARCH_W(MODE_FINE, true) DISTR_K_MARCH_W(MODE_FINE, false)
+DISTR_K_BWD_W(BWD_FULL, 2) DISTR_K_BWD_W(BWD_POINTGRAD, 2) DISTR_K_BWD_W(BWD_SAVED, 2) DISTR_K_BWD_W(BWD_SAVED, 1)
+#endif
 
-constexpr int DISTR_NUM_INST_GROUPS = 6;
+constexpr int DISTR_NUM_INST_GROUPS = 7;
 
 }  // namespace distr

@@ -24,9 +24,9 @@ constexpr int MAX_STEPS = 2048;
 constexpr int PSTRIDE = 1040;  // floats per backward tile partial: sd0[512] sd4[512] gR[9] gc[3] pad[4]
 
 struct Consts {
-  float c0[HID];          // b0 + W0[:, :256] * latent
-  float c4[HID];          // b4 + W4[:, 253:509] * latent
-  float latent[LAT];
+  float c0[HID];          // b0 + W0[:, :C] * latent
+  float c4[HID];          // b4 + W4[:, 509-C:509] * latent
+  float latent[MAX_LAT];  // the first C entries hold this view's code
   float R[9], T[3], c[3];
   float cdist;
   int32_t vflags;         // per-view gradient switches (VF_*): a batch renders views with different no_grad_* options in one launch
@@ -326,12 +326,12 @@ DISTR_GLOBAL void __launch_bounds__(256) k_prep(View V0, DecoderDev D, const flo
     const float* Wt = (gid < 512) ? D.W0lat_t : D.W4lat_t;
     float acc = (gid < 512) ? D.b0[o] : D.b4[o];
 #pragma unroll 8
-    for (int k = 0; k < LAT; ++k) acc = __builtin_fmaf(Wt[k * HID + o], latent[k], acc);
+    for (int k = 0; k < D.nlat; ++k) acc = __builtin_fmaf(Wt[k * HID + o], latent[k], acc);   // k order: one chain per output
     if (gid < 512) C->c0[o] = acc; else C->c4[o] = acc;
   }
   if (blockIdx.x == 0) {
     const int t = threadIdx.x;
-    C->latent[t] = latent[t];
+    for (int k = t; k < D.nlat; k += 256) C->latent[k] = latent[k];
     for (int i = t; i < MAX_STEPS + 2; i += 256) { C->cnt_live[i] = 0; C->cnt_sticky[i] = 0; C->tail_sync[2 * i] = 0; C->tail_sync[2 * i + 1] = 0; }
     for (int i = t; i < PSTRIDE; i += 256) C->red[i] = 0.f;
     if (t < 12) C->cam_acc[t] = 0.f;
@@ -728,7 +728,7 @@ template <int RB, int ARITH> struct TileSmem { using type = Smem<RB>; };
 template <int RB> struct TileSmem<RB, 1> { using type = SmemB6<RB>; };
 template <int RB> struct TileSmem<RB, 2> { using type = SmemH3<RB>; };
 
-template <int MODE, int RB, bool KEEP, int ARITH = 0>
+template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false>
 __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev& D, typename TileSmem<RB, ARITH>::type& S, int tile, int ntile_grid,
                                            int which, int origin_tile) {
   constexpr int TILE = 32 * RB;
@@ -775,7 +775,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   else if (MODE == MODE_FINE) list = split ? live_sel(V, A.step) : V.lv[0].list;
   const float* c0 = (MODE == MODE_EVAL) ? A.c0c4 : V.C->c0;
   const float* c4 = (MODE == MODE_EVAL) ? A.c0c4 + HID : V.C->c4;
-  if constexpr (ARITH == 0) stage_bias<RB>(D, c0, c4, S);      // first thing: these loads travel under the prologue's dependent state loads
+  if constexpr (ARITH == 0) stage_bias<RB, WIDE>(D, c0, c4, S);      // first thing: these loads travel under the prologue's dependent state loads
 
   int32_t id = -1;
   float zd = 0.f;
@@ -809,7 +809,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
 
   uint32_t masks[8][4];
   float pre;
-  if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true>(D, c0, c4, S, masks);
+  if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true, WIDE>(D, c0, c4, S, masks);
   else if constexpr (ARITH == 1) pre = mlp_forward_b6<RB, KEEP>(D, A.B6, c0, c4, S, masks);
   else pre = mlp_forward_h3<RB, KEEP>(D, A.H3, c0, c4, S, masks);
 
@@ -875,10 +875,12 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   return true;
 }
 
-template <int MODE, int RB, bool KEEP, int ARITH = 0>
+// WIDE: decoders with a code length below 256 (distr_mlp.hpp, stage_bias); 64-ray tiles, exact f32 only
+template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false>
 __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_march(MarchArgs A, DecoderDev D) {
+  static_assert(!WIDE || (RB == 2 && ARITH == 0), "the wide layout: 64-ray tiles, exact f32");
   __shared__ typename TileSmem<RB, ARITH>::type S;
-  (void)march_tile<MODE, RB, KEEP, ARITH>(A, D, S, (int)blockIdx.x, (int)gridDim.x, A.which, A.origin_tile);
+  (void)march_tile<MODE, RB, KEEP, ARITH, WIDE>(A, D, S, (int)blockIdx.x, (int)gridDim.x, A.which, A.origin_tile);
 }
 
 // KEEP, cluster tile of CL members: this member's share of the rays' mask blocks. Every member recorded the ReLU bits of the rows IT
@@ -1949,9 +1951,10 @@ __device__ __forceinline__ void bwd_range(int64_t count, int split, int tile_siz
   else { lo = full; hi = count; first_tile = t64; }
 }
 
-template <int MODE, int RB, int ARITH = 0>
+template <int MODE, int RB, int ARITH = 0, bool WIDE = false>
 __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(BwdArgs A, DecoderDev D) {
   static_assert(ARITH == 0 || MODE == BWD_SAVED, "the split-bf16 backward exists for saved masks only");
+  static_assert(!WIDE || ARITH == 0, "the wide layout: exact f32");
   constexpr int TILE = 32 * RB;
   __shared__ typename TileSmem<RB, ARITH>::type S;
   const View& V0 = A.V;
@@ -2060,7 +2063,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
     const float* c0 = A.c0c4 ? A.c0c4 : V.C->c0;
     const float* c4 = A.c0c4 ? A.c0c4 + HID : V.C->c4;
     float pre = 0.f;
-    if constexpr (ARITH == 0) pre = mlp_forward<RB, true>(D, c0, c4, S, masks);
+    if constexpr (ARITH == 0) pre = mlp_forward<RB, true, false, false, WIDE>(D, c0, c4, S, masks);
     if (tid < TILE) {
       y = tanh_spec(pre);
       if (MODE == BWD_POINTGRAD && A.coef && A.clamp >= 0.f && !(fabsf(y) <= A.clamp)) sm.coef = 0.f;
@@ -2069,7 +2072,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
     __syncthreads();
   }
   float* part = (MODE != BWD_POINTGRAD || partial) ? partial + (size_t)tile * PSTRIDE : nullptr;
-  if constexpr (ARITH == 0) mlp_backward<RB>(D, S, masks, part, part ? part + HID : nullptr);
+  if constexpr (ARITH == 0) mlp_backward<RB, 1, WIDE>(D, S, masks, part, part ? part + HID : nullptr);
   else if constexpr (ARITH == 1) mlp_backward_b6<RB>(D, A.B6, S, masks, part, part ? part + HID : nullptr);
   else mlp_backward_h3<RB>(D, A.H3, S, masks, part, part ? part + HID : nullptr);
 
@@ -2426,7 +2429,7 @@ DISTR_GLOBAL void __launch_bounds__(256) k_points_latent_grad(const float* parti
     red[col] = s;
   }
   __syncthreads();
-  const int nlat = D.nlat;                           // 256 (SDF decoder) or 256 + color_size (colour decoder)
+  const int nlat = D.nlat;                           // C (SDF decoder) or 256 + color_size (colour decoder)
   for (int k = threadIdx.x; k < nlat; k += 256) {
     float a = 0.f;
 #pragma unroll 16
@@ -2437,10 +2440,11 @@ DISTR_GLOBAL void __launch_bounds__(256) k_points_latent_grad(const float* parti
 
 // g_latent = W0lat^T sum(delta0) + W4lat^T sum(delta4); camera chain cam_pos = -R^T T (renderer.py:180-188)
 DISTR_GLOBAL void __launch_bounds__(256) k_bwd_final(View V0, DecoderDev D, BwdWs W0, int nchunks_max, int chunk, int tile,
-                                                   float* g_latent, float* g_R, float* g_T) {   // one block per view; outputs [nviews][256 | 9 | 3]
+                                                   float* g_latent, float* g_R, float* g_T) {   // one block per view; outputs [nviews][C | 9 | 3]
   const View V = view_at(V0, blockIdx.x);
   const float* chunk_part = bws_at(W0, blockIdx.x).chunk_part;
-  if (g_latent) g_latent += (size_t)blockIdx.x * LAT;
+  const int nlat = D.nlat;
+  if (g_latent) g_latent += (size_t)blockIdx.x * nlat;
   if (g_R) g_R += (size_t)blockIdx.x * 9;
   if (g_T) g_T += (size_t)blockIdx.x * 3;
   const int k = threadIdx.x;
@@ -2459,10 +2463,12 @@ DISTR_GLOBAL void __launch_bounds__(256) k_bwd_final(View V0, DecoderDev D, BwdW
   __syncthreads();
   const float* sd0 = C->red;
   const float* sd4 = C->red + HID;
-  float a = 0.f;
+  for (int kl = k; kl < nlat; kl += 256) {
+    float a = 0.f;
 #pragma unroll 16
-  for (int o = 0; o < HID; ++o) a += D.W0lat[o * LAT + k] * sd0[o] + D.W4lat[o * LAT + k] * sd4[o];   // loads batch 16 deep
-  if (g_latent) g_latent[k] = a;
+    for (int o = 0; o < HID; ++o) a += D.W0lat[o * nlat + kl] * sd0[o] + D.W4lat[o * nlat + kl] * sd4[o];   // loads batch 16 deep
+    if (g_latent) g_latent[kl] = a;
+  }
   if (k < 12) {
     float gc[3];
 #pragma unroll

@@ -53,7 +53,8 @@ __device__ __forceinline__ const T& kernarg_ref(size_t offset) {     // the kern
 }
 
 constexpr int HID = 512;
-constexpr int LAT = 256;
+constexpr int LAT = 256;       // the code length the tile shapes are laid out for: lin3 = 253 rows + 3 xyz rows, lin4 K = 256
+constexpr int MAX_LAT = 508;   // longest code length an SDF decoder may have: lin3 keeps 509 - C >= 1 rows
 constexpr int NTHREADS = 256;
 
 // (f32x16 / f32x4 / rsrc_t: distr_dense_asm.hpp)
@@ -80,7 +81,7 @@ struct DecoderDev {
   const float* W0x;     // [3][512]   lin0 xyz columns
   float b8;             // lin8 bias of row 0
   float b8x[2];         // lin8 biases of rows 1, 2 (colour decoder)
-  int32_t nlat;         // latent length folded into c0 / c4 (256; 256 + color_size for the colour decoder)
+  int32_t nlat;         // latent length folded into c0 / c4 (the code length C of the SDF decoder; 256 + color_size for the colour decoder)
 };
 
 // A tile = RB blocks of 32 rays. RB=2: 64 rays, 133 KiB LDS, one workgroup per CU. RB=1: 32 rays, 67 KiB LDS, two
@@ -100,14 +101,16 @@ struct alignas(16) Smem : SmemBias<RB> {
   float aux[4 * TILE];   // backward: row 0 = d8, rows 1..3 = d/dxyz through lin4's xyz columns
 };
 
-template <int RB>
+// WIDE: the tile layout of decoders with a code length C < 256 -- lin3 has 509 - C > 253 rows, so lin3 (padded to 509 rows, xyz carried
+// in rows 509..511) and lin4 (K = 512) are full 512 x 512 layers like lin1 / lin2. Narrow (the default): lin3 256 rows, lin4 K = 256.
+template <int RB, bool WIDE = false>
 __device__ __forceinline__ void stage_bias(const DecoderDev& D, const float* __restrict__ c0, const float* __restrict__ c4, Smem<RB>& S) {
   if constexpr (RB == 2) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int l = 0; l < 8; ++l) {
       const float* src = (l == 0) ? c0 : (l == 4) ? c4 : D.bias[l];
-      const int n = (l == 3) ? 256 : HID;
+      const int n = (l == 3 && !WIDE) ? 256 : HID;
 #pragma unroll
       for (int i = tid; i < HID; i += NTHREADS) S.bias[l * HID + i] = (i < n) ? src[i] : 0.f;
     }
@@ -412,7 +415,7 @@ __device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float
 // Returns (every thread, for ray = tid & (TILE-1)) the pre-tanh output. masks[l] = ReLU bitmasks of layer l
 // (bit rb*16+r of masks[l][ob]). DEBUG_STOP: (test builds only) return right after layer `stop` is in X.
 // STAGED: the caller already ran stage_bias (early, so that its loads overlap the tile's prologue).
-template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false>
+template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false>
 __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* __restrict__ c0,
                                              const float* __restrict__ c4, Smem<RB>& S, uint32_t (&masks)[8][4],
                                              int stop = 8, long long* ts = nullptr) {
@@ -433,7 +436,7 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
 #pragma unroll
     for (int ob = 0; ob < 4; ++ob) wpre[ob] = w0[ob * 64];
   }
-  if (!STAGED) stage_bias<RB>(D, c0, c4, S);
+  if (!STAGED) stage_bias<RB, WIDE>(D, c0, c4, S);
   // layer-0 input rows: xyz + zero padding to K=8
 #pragma unroll
   for (int i = tid; i < 8 * TILE; i += NTHREADS) X[i] = (i < 3 * TILE) ? S.xyz[i] : 0.f;
@@ -474,7 +477,8 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     }
     {
       f32x16 acc[4][2];
-      dense_asm_k512_n4_o2_bias(acc, wpre, xaddr, voff, rs[2], rs[3], soff4, soff2, bias4 + 2 * 2048, scratch);
+      if constexpr (WIDE) dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[2], rs[3], soff4, soff4, bias4 + 2 * 2048, scratch);
+      else dense_asm_k512_n4_o2_bias(acc, wpre, xaddr, voff, rs[2], rs[3], soff4, soff2, bias4 + 2 * 2048, scratch);
       DISTR_TS(5);
       __syncthreads();
       writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[2]);
@@ -482,6 +486,30 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
       DISTR_TS(6);
       if (DEBUG_STOP && stop == 2) return 0.f;
     }
+    if constexpr (WIDE) {  // lin3: 512 -> 509 (+3 rows that carry xyz into lin4); lin4: [x3 (509) | xyz (3)] -> 512
+      {
+        f32x16 acc[4][2];
+        dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[3], rs[4], soff4, soff4, bias4 + 3 * 2048, scratch);
+        DISTR_TS(7);
+        __syncthreads();
+        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[3]);   // rows 509..511: zero weights and bias, mask 0
+        __syncthreads();
+        if (tid < 3 * TILE) X[509 * TILE + tid] = S.xyz[tid];
+        __syncthreads();
+        DISTR_TS(8);
+        if (DEBUG_STOP && stop == 3) return 0.f;
+      }
+      {
+        f32x16 acc[4][2];
+        dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[4], rs[5], soff4, soff4, bias4 + 4 * 2048, scratch);
+        DISTR_TS(9);
+        __syncthreads();
+        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[4]);
+        __syncthreads();
+        DISTR_TS(10);
+        if (DEBUG_STOP && stop == 4) return 0.f;
+      }
+    } else {
     {  // lin3: 512 -> 253 (+3 rows that carry xyz into lin4)
       f32x16 acc[2][2];
       dense_asm_k512_n2_o4_bias(acc, wpre, xaddr, voff, rs[3], rs[4], soff2, soff4, bias2, scratch);
@@ -504,6 +532,7 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
       __syncthreads();
       DISTR_TS(10);
       if (DEBUG_STOP && stop == 4) return 0.f;
+    }
     }
 #pragma unroll
     for (int l = 5; l <= 7; ++l) {
@@ -532,6 +561,24 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     DISTR_TS(4);
     if (DEBUG_STOP && stop == 1) return 0.f;
   }
+  if constexpr (WIDE) {   // lin2, lin3 (512 -> 509 + 3 xyz rows), lin4 ([x3 (509) | xyz (3)] -> 512): the shape of lin1
+#pragma unroll
+    for (int l = 2; l <= 4; ++l) {
+      f32x16 acc[4][RB];
+      acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, l), wave * 128, h);
+      dense_pf<512, 4, RB, 4, 4, 4>(D.Wf[l], X, acc, wave, lane, wpre, D.Wf[l + 1]);
+      DISTR_TS(2 * l + 1);
+      __syncthreads();
+      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
+      __syncthreads();
+      if (l == 3) {
+        if (tid < 3 * TILE) X[509 * TILE + tid] = S.xyz[tid];
+        __syncthreads();
+      }
+      DISTR_TS(2 * l + 2);
+      if (DEBUG_STOP && stop == l) return 0.f;
+    }
+  } else {
   {
     f32x16 acc[4][RB];
     acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 2), wave * 128, h);
@@ -568,6 +615,7 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     DISTR_TS(10);
   }
   if (DEBUG_STOP && stop == 4) return 0.f;
+  }
 #pragma unroll
   for (int l = 5; l <= 7; ++l) {
     f32x16 acc[4][RB];
@@ -606,7 +654,7 @@ __device__ __forceinline__ void row_sums(const float* X, float* __restrict__ dst
 
 // NOUT: rows of lin8 (1: SDF decoder; 3: colour decoder -- then S.aux rows 0..2 hold the three d8 rows and
 // delta7 = relu'(h7) * sum_c w8[c][k] * d8_c, accumulated in channel order)
-template <int RB, int NOUT = 1>
+template <int RB, int NOUT = 1, bool WIDE = false>
 __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, uint32_t (&masks)[8][4],
                                              float* __restrict__ sd0, float* __restrict__ sd4) {
   constexpr int TILE = 32 * RB;
@@ -659,13 +707,35 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
 #pragma unroll
     for (int l = 7; l >= 5; --l) {  // delta_l (512) -> delta_{l-1} (512)
       f32x16 acc[4][2];
-      if (l > 5) dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[l], rs[l > 5 ? l - 1 : l], soff4, soff4, 0u, scratch);
+      if (l > 5 || WIDE) dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[l], rs[l - 1], soff4, soff4, 0u, scratch);
       else dense_asm_k512_n4_o2_zero(acc, t, xaddr, voff, rs[5], rs[4], soff4, soff2, 0u, scratch);
       __syncthreads();
       writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[l - 1]);
       __syncthreads();
     }
     if (sd4) row_sums<RB>(X, sd4, tid);  // X = delta4
+    if constexpr (WIDE) {
+      {  // lin4^T: delta4 (512) -> [delta3 (509) | d xyz (3)]
+        f32x16 acc[4][2];
+        dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[4], rs[3], soff4, soff4, 0u, scratch);
+        __syncthreads();
+        writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[3]);  // rows 509..511 have mask 0 -> written as 0
+        if (wave == 3 && h == 1) {
+#pragma unroll
+          for (int r = 13; r < 16; ++r)
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[3][rb][r];
+        }
+        __syncthreads();
+      }
+      {  // lin3^T: delta3 (512 rows, 509 real) -> delta2 (512)
+        f32x16 acc[4][2];
+        dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[3], rs[2], soff4, soff4, 0u, scratch);
+        __syncthreads();
+        writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
+        __syncthreads();
+      }
+    } else {
     {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
       f32x16 acc[2][2];
       dense_asm_k512_n2_o4_zero(acc, t, xaddr, voff, rs[4], rs[3], soff2, soff4, 0u, scratch);
@@ -685,6 +755,7 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
       __syncthreads();
       writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
       __syncthreads();
+    }
     }
 #pragma unroll
     for (int l = 2; l >= 1; --l) {
@@ -706,6 +777,30 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
     __syncthreads();
   }
   if (sd4) row_sums<RB>(X, sd4, tid);  // X = delta4
+  if constexpr (WIDE) {
+    {  // lin4^T: delta4 (512) -> [delta3 (509) | d xyz (3)]
+      f32x16 acc[4][RB];
+      acc_zero<4, RB>(acc);
+      dense<512, 4, RB>(D.Wb[4], X, acc, wave, lane);
+      __syncthreads();
+      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[3]);  // rows 509..511 have mask 0 -> written as 0
+      if (wave == 3 && h == 1) {
+#pragma unroll
+        for (int r = 13; r < 16; ++r)
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[3][rb][r];
+      }
+      __syncthreads();
+    }
+    {  // lin3^T: delta3 (512 rows, 509 real) -> delta2 (512)
+      f32x16 acc[4][RB];
+      acc_zero<4, RB>(acc);
+      dense<512, 4, RB>(D.Wb[3], X, acc, wave, lane);
+      __syncthreads();
+      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
+      __syncthreads();
+    }
+  } else {
   {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
     f32x16 acc[2][RB];
     acc_zero<2, RB>(acc);
@@ -727,6 +822,7 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
     __syncthreads();
     writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
     __syncthreads();
+  }
   }
 #pragma unroll
   for (int l = 2; l >= 1; --l) {

@@ -107,7 +107,7 @@ class RenderStats(_Sized):
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
            'distr_dense_asm.hpp', 'distr_mesh.hpp')
 HEADERS = ('distr.h', 'distr_mesh.h')                    # include/: the C ABI
-INST_GROUPS = 6            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
+INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
 
@@ -423,9 +423,9 @@ class Context(object):
         if rc != 0:
             raise DistrError('libdistr error %d: %s' % (rc, self.L.distr_last_error(self.h).decode()))
 
-    def set_decoder(self, flat_weights):
+    def set_decoder(self, flat_weights, latent_size=256):
         w = np.ascontiguousarray(flat_weights, dtype=np.float32)
-        desc = DecoderDesc(latent_size=256, hidden=512, num_linear=9, latent_in=4)
+        desc = DecoderDesc(latent_size=int(latent_size), hidden=512, num_linear=9, latent_in=4)
         self.check(self.L.distr_set_decoder(self.h, C.byref(desc), w.ctypes.data_as(C.POINTER(C.c_float)), w.size))
 
     def set_color_decoder(self, flat_weights, latent_size):

@@ -3,8 +3,8 @@
 Host-side counterpart of `load_decoder` (core/utils/decoder_utils.py:7-51) + the layer
 construction of `Decoder.__init__` (core/graph/deep_sdf_decoder.py:19-73): takes a module or a
 state_dict, folds weight-norm (`lin{l}.weight_g/.weight_v` -> W = g * v / ||v||_row), validates that
-the architecture is the one the HIP kernels are specialised for (DeepSDF '8x512', latent 256,
-latent_in=[4], ReLU, final tanh, no LayerNorm / xyz_in_all / use_tanh; latent_dropout only in eval mode, where it is the identity), and
+the architecture is the one the HIP kernels are specialised for (DeepSDF '8x512', code length C in
+1..508, latent_in=[4], ReLU, final tanh, no LayerNorm / xyz_in_all / use_tanh; latent_dropout only in eval mode, where it is the identity), and
 returns one contiguous float32 array: for l in 0..8: W_l row-major (out,in) followed by b_l.
 The LDS/MFMA-fragment packing itself is done natively inside the library.
 """
@@ -12,7 +12,9 @@ import numpy as np
 
 from . import fixture
 
-_SHAPES = fixture.layer_shapes()
+# Code lengths the tile kernels take: 256 <= C <= 508 packs lin3's 509 - C rows zero-padded to 253 (the narrow
+# layout, the C = 256 kernels); C < 256 packs them zero-padded to 509, lin3 / lin4 then run as full 512 x 512 layers (the wide layout).
+MAX_LATENT = 508
 
 
 class UnsupportedDecoder(NotImplementedError):
@@ -54,13 +56,25 @@ def effective_weights(state_dict):
     return Ws, bs
 
 
+def latent_size_of(Ws):
+    """Code length C of a decoder: lin0 takes [latent (C) | xyz (3)]."""
+    return int(np.shape(Ws[0])[1]) - 3 if len(Ws) and np.ndim(Ws[0]) == 2 else -1
+
+
 def validate(Ws, bs):
-    if len(Ws) != len(_SHAPES):
-        raise UnsupportedDecoder('expected %d linear layers, got %d' % (len(_SHAPES), len(Ws)))
+    """Checks all nine shapes against the DeepSDF 8x512 decoder of code length C = lin0's input width - 3; returns C."""
+    if len(Ws) != fixture.NUM_LINEAR or len(bs) != fixture.NUM_LINEAR:
+        raise UnsupportedDecoder('expected %d linear layers, got %d' % (fixture.NUM_LINEAR, len(Ws)))
+    C = latent_size_of(Ws)
+    if C < 1 or C > MAX_LATENT:
+        raise UnsupportedDecoder('lin0 has shape %s: code length %d is outside 1..%d (lin3 of a latent_in=[4] decoder has 509 - C rows)'
+                                 % (np.shape(Ws[0]), C, MAX_LATENT))
+    shapes = fixture.layer_shapes(C)
     for l, (W, b) in enumerate(zip(Ws, bs)):
-        if tuple(W.shape) != _SHAPES[l] or b.shape != (_SHAPES[l][0],):
+        if tuple(np.shape(W)) != shapes[l] or tuple(np.shape(b)) != (shapes[l][0],):
             raise UnsupportedDecoder('lin%d has shape %s, kernels are specialised for %s (DeepSDF 8x512, '
-                                     'latent 256, latent_in=[4], last_dim=1)' % (l, W.shape, _SHAPES[l]))
+                                     'latent %d, latent_in=[4], last_dim=1)' % (l, np.shape(W), shapes[l], C))
+    return C
 
 
 def validate_color(Ws, bs):
@@ -114,6 +128,7 @@ def check_module_flags(decoder):
 
 
 def flatten(Ws, bs):
+    """-> flat f32 array for distr_set_decoder (its code length: latent_size_of(Ws))."""
     validate(Ws, bs)
     parts = []
     for W, b in zip(Ws, bs):
@@ -124,9 +139,14 @@ def flatten(Ws, bs):
 
 def pack_module(decoder):
     """nn.Module (optionally DataParallel-wrapped) -> flat f32 array."""
+    return pack_module_sized(decoder)[0]
+
+
+def pack_module_sized(decoder):
+    """nn.Module (optionally DataParallel-wrapped) -> (flat f32 array, code length C)."""
     check_module_flags(decoder)
     Ws, bs = effective_weights(decoder.state_dict())
-    return flatten(Ws, bs)
+    return flatten(Ws, bs), latent_size_of(Ws)
 
 
 def fixture_state_dict(Ws, bs, weight_norm=False):

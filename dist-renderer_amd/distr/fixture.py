@@ -38,32 +38,38 @@ def layer_shapes(latent_size=LATENT_SIZE, hidden=HIDDEN):
     return shapes
 
 
-def make_decoder_weights(seed=1234, latent_scale=0.003):
-    """Returns (weights, biases, latent): lists of f32 arrays W_l (out,in), b_l (out,), latent (1,256).
+def make_decoder_weights(seed=1234, latent_scale=0.003, latent_size=LATENT_SIZE):
+    """Returns (weights, biases, latent): lists of f32 arrays W_l (out,in), b_l (out,), latent (1,C), C = latent_size.
 
     Draw order is fixed (one RandomState stream) so the arrays are reproducible
     bit-for-bit on any machine: for l in 0..8 the (out,in) matrix, then for l==0 and
-    l==4 an extra (512,256) draw for the latent columns; finally the latent code.
+    l==4 an extra (512,C) draw for the latent columns; finally the latent code.
+    lin3 has 509 - C rows. For C != 256 lin4's xyz columns keep their draw (at C = 256
+    they are zero), so that the field stays a closed blob around the origin even when
+    lin3 has only a few rows (C near 508); the default decoder is unchanged, byte for byte.
     """
+    C = int(latent_size)
     rs = np.random.RandomState(seed)
-    shapes = layer_shapes()
+    shapes = layer_shapes(C)
+    r3 = shapes[3][0]
     Ws, bs = [], []
     for l, (o, i) in enumerate(shapes):
         W = rs.standard_normal((o, i)) * (math.sqrt(2.0) / math.sqrt(o))
         b = np.zeros((o,))
         if l == 0:
-            # input = [latent(256) | xyz(3)]
-            W[:, :LATENT_SIZE] = latent_scale * rs.standard_normal((o, LATENT_SIZE))
+            # input = [latent(C) | xyz(3)]
+            W[:, :C] = latent_scale * rs.standard_normal((o, C))
         if l == 4:
-            # input = [x3(253) | latent(256) | xyz(3)]
-            W[:, 253:253 + LATENT_SIZE] = latent_scale * rs.standard_normal((o, LATENT_SIZE))
-            W[:, 253 + LATENT_SIZE:] = 0.0
+            # input = [x3(509 - C) | latent(C) | xyz(3)]
+            W[:, r3:r3 + C] = latent_scale * rs.standard_normal((o, C))
+            if C == LATENT_SIZE:
+                W[:, r3 + C:] = 0.0
         if l == 8:
             W = math.sqrt(math.pi) / math.sqrt(i) + 1e-5 * rs.standard_normal((o, i))
             b = np.full((o,), -0.5)
         Ws.append(np.ascontiguousarray(W, dtype=np.float32))
         bs.append(np.ascontiguousarray(b, dtype=np.float32))
-    latent = (0.1 * rs.standard_normal((1, LATENT_SIZE))).astype(np.float32)
+    latent = (0.1 * rs.standard_normal((1, C))).astype(np.float32)
     return Ws, bs, latent
 
 
@@ -104,10 +110,10 @@ def weights_sha256(Ws, bs):
     return h.hexdigest()
 
 
-def make_latent(seed):
-    """Extra latent codes (C5 'batch of shapes'): seed -> (1,256) f32."""
+def make_latent(seed, latent_size=LATENT_SIZE):
+    """Extra latent codes (C5 'batch of shapes'): seed -> (1,C) f32."""
     rs = np.random.RandomState(seed)
-    return (0.1 * rs.standard_normal((1, LATENT_SIZE))).astype(np.float32)
+    return (0.1 * rs.standard_normal((1, int(latent_size)))).astype(np.float32)
 
 
 def load_fixture_f2(path=None):

@@ -38,9 +38,13 @@ class DecoderEngine(object):
 
     generation = 0     # number of weight uploads so far: a forward remembers it, its backward refuses to run on newer weights
 
+    latent_size = 256  # code length C of the uploaded decoder: every latent buffer of this engine has C entries per view
+
     def refresh(self, decoder):
         """(Re)uploads the weights."""
-        self.ctx.set_decoder(decoder_pack.pack_module(decoder))
+        flat, nlat = decoder_pack.pack_module_sized(decoder)
+        self.ctx.set_decoder(flat, nlat)
+        self.latent_size = nlat
         self._key = _param_key(decoder)
         self.generation += 1
 
@@ -69,8 +73,25 @@ def engine_from_weights(Ws, bs, device_index=0):
     eng = DecoderEngine.__new__(DecoderEngine)
     eng.ctx = binding.Context(device_index)
     eng.device = torch.device('cuda', device_index)
-    eng.ctx.set_decoder(decoder_pack.flatten(Ws, bs))
+    eng.ctx.set_decoder(decoder_pack.flatten(Ws, bs), decoder_pack.latent_size_of(Ws))
+    eng.latent_size = decoder_pack.latent_size_of(Ws)
     return eng
+
+
+def check_split_arith(engine, arith):
+    """The split arithmetics (bf16x6 / f16x3) are built for the code length 256 only."""
+    if arith != 'f32' and engine.latent_size != 256:
+        raise decoder_pack.UnsupportedDecoder("arith=%r is built for code length 256 only; this decoder's code length is %d: use arith='f32'"
+                                              % (arith, engine.latent_size))
+
+
+def _code(engine, latent, dev, views=False):
+    """latent -> flat f32 device buffer of C (views=True: (1, C) shared or (B, C)) entries; ValueError naming (1, C) otherwise."""
+    C = engine.latent_size
+    lat = _f32c(latent, dev)
+    if lat.numel() == 0 or lat.numel() % C or (not views and lat.numel() != C):
+        raise ValueError('latent has shape %s; this decoder takes (1, %d)%s' % (tuple(latent.shape), C, ' or (B, %d)' % C if views else ''))
+    return lat.reshape(-1, C) if views else lat.reshape(-1)
 
 
 class ColorEngine(object):
@@ -216,9 +237,9 @@ class RenderFunction(torch.autograd.Function):
         dev = engine.device
         H, W = cfg.band_rows, cfg.W
         P = H * W
-        lat, Rc, Tc = _f32c(latent, dev).reshape(-1), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
-        if lat.numel() != 256 or Rc.numel() != 9 or Tc.numel() != 3:
-            raise ValueError('expected latent (1,256), R (3,3), T (3)')
+        lat, Rc, Tc = _code(engine, latent, dev), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
+        if Rc.numel() != 9 or Tc.numel() != 3:
+            raise ValueError('expected latent (1,%d), R (3,3), T (3)' % engine.latent_size)
         fwd_bytes, bwd_bytes = engine.ctx.workspace_bytes(cfg)
         ws = torch.empty(fwd_bytes, dtype=torch.uint8, device=dev)
         zdepth = torch.empty(P, dtype=torch.float32, device=dev)
@@ -256,7 +277,7 @@ class RenderFunction(torch.autograd.Function):
         P = cfg.band_rows * cfg.W
         gz, gq = prep(g_zdepth, P), prep(g_min_sdf, P)
         gd, gn = (prep(g_depth, P), prep(g_normal, 3 * P)) if cfg.want_normal else (None, None)
-        g_lat = torch.empty(256, dtype=torch.float32, device=dev)
+        g_lat = torch.empty(engine.latent_size, dtype=torch.float32, device=dev)
         g_R = torch.empty(9, dtype=torch.float32, device=dev)
         g_T = torch.empty(3, dtype=torch.float32, device=dev)
         ws_b = torch.empty(ctx.bwd_bytes, dtype=torch.uint8, device=dev)
@@ -279,7 +300,7 @@ def render_call(engine, cfg, latent, R, T):
 
 
 class RenderBatchFunction(torch.autograd.Function):
-    """Several views in one launch sequence (distr_render_forward_batch): (latent (1,256) shared by all views or (B,256), R (B,3,3),
+    """Several views in one launch sequence (distr_render_forward_batch): (latent (1,C) shared by all views or (B,C), R (B,3,3),
     T (B,3)) -> (zdepth (B,P), mask (B,P) uint8, min_sdf (B,P), depth (B,H,W), normal (B,H,W,3)). Every view's values and
     gradients are bit-identical to its own RenderFunction call; what changes is the schedule (one march launch per step for all
     views: the views' latency-bound tails overlap). `view_flags`: per-view DISTR_VIEW_GRAD_* (the no_grad_* options of each view)."""
@@ -291,9 +312,10 @@ class RenderBatchFunction(torch.autograd.Function):
         P = H * W
         Rc, Tc = _f32c(R, dev).reshape(-1, 9), _f32c(T, dev).reshape(-1, 3)
         B = Rc.shape[0]
-        lat = _f32c(latent, dev).reshape(-1, 256)
+        lat = _code(engine, latent, dev, views=True)
         if Tc.shape[0] != B or lat.shape[0] not in (1, B) or not (1 <= B <= binding.MAX_VIEWS):
-            raise ValueError('expected latent (1,256) or (B,256), R (B,3,3), T (B,3) with 1 <= B <= %d' % binding.MAX_VIEWS)
+            raise ValueError('expected latent (1,%d) or (B,%d), R (B,3,3), T (B,3) with 1 <= B <= %d'
+                             % (engine.latent_size, engine.latent_size, binding.MAX_VIEWS))
         shared = lat.shape[0] == 1
         fwd_bytes, bwd_bytes = engine.ctx.workspace_bytes(cfg)
         ws = torch.empty(B * fwd_bytes, dtype=torch.uint8, device=dev)
@@ -309,7 +331,7 @@ class RenderBatchFunction(torch.autograd.Function):
         flags = None if view_flags is None else (C.c_int32 * B)(*[int(f) for f in view_flags])
         p = binding.ptr
         engine.ctx.check(engine.ctx.L.distr_render_forward_batch(
-            engine.ctx.h, C.byref(cfg), B, flags, p(lat), 0 if shared else 256, p(Rc), p(Tc), p(zdepth), p(mask), p(min_sdf),
+            engine.ctx.h, C.byref(cfg), B, flags, p(lat), 0 if shared else engine.latent_size, p(Rc), p(Tc), p(zdepth), p(mask), p(min_sdf),
             p(depth) if cfg.want_normal else None, p(normal) if cfg.want_normal else None, p(ws), ws.numel(), engine.ctx.stream()))
         _check_f16_range(engine, cfg, ws, B, fwd_bytes, needs_grad=any(ctx.needs_input_grad[:3]))
         ctx.engine, ctx.cfg, ctx.ws, ctx.bwd_bytes, ctx.B, ctx.shared = engine, cfg, ws, bwd_bytes, B, shared
@@ -333,7 +355,7 @@ class RenderBatchFunction(torch.autograd.Function):
         P = cfg.band_rows * cfg.W
         gz, gq = prep(g_zdepth, B * P), prep(g_min_sdf, B * P)
         gd, gn = (prep(g_depth, B * P), prep(g_normal, 3 * B * P)) if cfg.want_normal else (None, None)
-        g_lat = torch.empty(B, 256, dtype=torch.float32, device=dev)
+        g_lat = torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev)
         g_R = torch.empty(B, 9, dtype=torch.float32, device=dev)
         g_T = torch.empty(B, 3, dtype=torch.float32, device=dev)
         ws_b = torch.empty(B * ctx.bwd_bytes, dtype=torch.uint8, device=dev)
@@ -348,7 +370,7 @@ class RenderBatchFunction(torch.autograd.Function):
 
 
 def render_batch_call(engine, cfg, latent, R, T, view_flags=None):
-    """Batched render_call: R (B,3,3), T (B,3), latent (1,256) (shared) or (B,256)."""
+    """Batched render_call: R (B,3,3), T (B,3), latent (1,C) (shared) or (B,C)."""
     need_bwd = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in (latent, R, T))
     cfg = cfg.clone()
     cfg.save_for_backward = 1 if need_bwd else 0
@@ -361,16 +383,17 @@ def render_normal_batch_call(engine, cfg, latent, R, T, zdepth, mask):
     P = cfg.band_rows * cfg.W
     Rc, Tc = _f32c(R, dev).reshape(-1, 9), _f32c(T, dev).reshape(-1, 3)
     B = Rc.shape[0]
-    lat = _f32c(latent, dev).reshape(-1, 256)
+    lat = _code(engine, latent, dev, views=True)
     if lat.shape[0] not in (1, B) or not (1 <= B <= binding.MAX_VIEWS):
-        raise ValueError('expected latent (1,256) or (B,256), R (B,3,3), T (B,3) with 1 <= B <= %d' % binding.MAX_VIEWS)
+        raise ValueError('expected latent (1,%d) or (B,%d), R (B,3,3), T (B,3) with 1 <= B <= %d'
+                         % (engine.latent_size, engine.latent_size, binding.MAX_VIEWS))
     z = _f32c(zdepth, dev).reshape(B, P)
     m = mask.detach().to(device=dev).reshape(B, P).to(torch.uint8).contiguous()
     fwd_bytes, _ = engine.ctx.workspace_bytes(cfg)
     ws = torch.empty(B * fwd_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(B, 3, P, dtype=torch.float32, device=dev)
     p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_render_normal_batch(engine.ctx.h, C.byref(cfg), B, p(lat), 0 if lat.shape[0] == 1 else 256, p(Rc), p(Tc),
+    engine.ctx.check(engine.ctx.L.distr_render_normal_batch(engine.ctx.h, C.byref(cfg), B, p(lat), 0 if lat.shape[0] == 1 else engine.latent_size, p(Rc), p(Tc),
                                                             p(z), p(m), p(out), p(ws), ws.numel(), engine.ctx.stream()))
     return out
 
@@ -413,7 +436,7 @@ def render_normal_call(engine, cfg, latent, R, T, zdepth, mask):
     (SURVEY.md A.6-1)."""
     dev = engine.device
     P = cfg.band_rows * cfg.W
-    lat, Rc, Tc = _f32c(latent, dev).reshape(-1), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
+    lat, Rc, Tc = _code(engine, latent, dev), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
     z = _f32c(zdepth, dev).reshape(-1)
     m = mask.detach().to(device=dev).reshape(-1).to(torch.uint8).contiguous()
     fwd_bytes, _ = engine.ctx.workspace_bytes(cfg)
@@ -432,8 +455,9 @@ def mlp_eval(engine, latent, points, clamp_dist=None, arith='f32'):
     for a point whose activations leave that range)."""
     if arith not in binding.ARITH:
         raise ValueError("arith must be one of %s" % sorted(binding.ARITH))
+    check_split_arith(engine, arith)
     dev = engine.device
-    lat = _f32c(latent, dev).reshape(-1)
+    lat = _code(engine, latent, dev)
     x = _f32c(points, dev).reshape(-1, 3)
     n = x.shape[0]
     out = torch.empty(n, 1, dtype=torch.float32, device=dev)
@@ -446,7 +470,7 @@ def mlp_eval(engine, latent, points, clamp_dist=None, arith='f32'):
 
 
 class DecodeSdfFunction(torch.autograd.Function):
-    """decode_sdf with autograd (decoder_utils.py:53-74 called without no_grad): (latent (1,256), points (n,3)) -> (n,1);
+    """decode_sdf with autograd (decoder_utils.py:53-74 called without no_grad): (latent (1,C), points (n,3)) -> (n,1);
     backward = distr_mlp_backward (one fused forward-recompute + dX chain per point, latent gradient from the delta sums)."""
 
     @staticmethod
@@ -462,12 +486,12 @@ class DecodeSdfFunction(torch.autograd.Function):
         engine = ctx.engine
         dev = engine.device
         latent, points = ctx.saved_tensors
-        lat = _f32c(latent, dev).reshape(-1)
+        lat = _code(engine, latent, dev)
         x = _f32c(points, dev).reshape(-1, 3)
         n = x.shape[0]
         gs = _f32c(g, dev).reshape(-1)
         g_x = torch.empty(n, 3, dtype=torch.float32, device=dev) if ctx.need[1] else None
-        g_l = torch.empty(256, dtype=torch.float32, device=dev) if ctx.need[0] else None
+        g_l = torch.empty(engine.latent_size, dtype=torch.float32, device=dev) if ctx.need[0] else None
         ws = torch.empty(engine.ctx.L.distr_mlp_backward_workspace_bytes(n), dtype=torch.uint8, device=dev)
         p = binding.ptr
         engine.ctx.check(engine.ctx.L.distr_mlp_backward(engine.ctx.h, p(lat), p(x), n, p(gs), -1.0 if ctx.clamp is None else float(ctx.clamp),
@@ -482,7 +506,7 @@ def mlp_eval_autograd(engine, latent, points, clamp_dist=None):
 def mlp_grad(engine, latent, points):
     """(sdf (n,), d sdf/d xyz (n,3)) of the unclamped decoder."""
     dev = engine.device
-    lat = _f32c(latent, dev).reshape(-1)
+    lat = _code(engine, latent, dev)
     x = _f32c(points, dev).reshape(-1, 3)
     n = x.shape[0]
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
@@ -496,7 +520,7 @@ def mlp_grad(engine, latent, points):
 def debug_mlp_layer(engine, latent, points, layer):
     """Test aid: post-activation of hidden layer `layer` -> (n,512)."""
     dev = engine.device
-    lat = _f32c(latent, dev).reshape(-1)
+    lat = _code(engine, latent, dev)
     x = _f32c(points, dev).reshape(-1, 3)
     n = x.shape[0]
     out = torch.empty(n, 512, dtype=torch.float32, device=dev)
@@ -510,7 +534,7 @@ def debug_mlp_layer(engine, latent, points, layer):
 def debug_tile_timing(engine, latent, points, tile):
     """Test aid: (sdf (n,), stamps (tiles, 20, 2) int64 [shader clock, 100 MHz wall clock]) of the decoder tile phases."""
     dev = engine.device
-    lat = _f32c(latent, dev).reshape(-1)
+    lat = _code(engine, latent, dev)
     x = _f32c(points, dev).reshape(-1, 3)
     n = x.shape[0]
     tiles = (n + tile - 1) // tile
