@@ -284,16 +284,19 @@ int check_cfg(distr_ctx* ctx, const distr_render_cfg* c) {
   return DISTR_OK;
 }
 
+inline bool is_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return cs != hipStreamCaptureStatusNone;
+}
+
 // Exchange region of `stream` (allocated on the stream's first render: 32 MiB of granule slots + 128 KiB of uncached assembly
 // words; steady state never allocates). Null (-> single-workgroup tiles) when disabled, out of regions, or the allocation fails.
 distr_ctx::XRegion* xchg_region(distr_ctx* ctx, hipStream_t stream) {
   if (!ctx->cluster) return nullptr;
-  {  // a launch sequence that is being captured into a graph would replay with the epochs of the capture (the barrier words
-     // would already match) and must not allocate or query streams: single-workgroup tiles for captured renders
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();
-    else if (cs != hipStreamCaptureStatusNone) return nullptr;
-  }
+  // a launch sequence that is being captured into a graph would replay with the epochs of the capture (the barrier words
+  // would already match) and must not allocate or query streams: single-workgroup tiles for captured renders
+  if (is_capturing(stream)) return nullptr;
   distr_ctx::XRegion* free_slot = nullptr;
   for (auto& r : ctx->xr) {
     if (r.used && r.stream == stream) { r.last_use = ++ctx->xr_clock; return &r; }
@@ -475,6 +478,7 @@ size_t bwd_bytes(const distr_render_cfg& c) {
 }
 
 inline dim3 grid1(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+inline dim3 gridv(const View& V, int64_t n) { return dim3((unsigned)((n + 255) / 256), (unsigned)V.nviews); }   // (blocks of 256, view)
 
 struct MarchTimer {  // optional hipEvent bracket around the march kernel launches
   distr_ctx* ctx; hipStream_t s; bool on;
@@ -494,6 +498,20 @@ struct MarchTimer {  // optional hipEvent bracket around the march kernel launch
     ctx->ev_used++;
   }
 };
+
+// Prologue of the entry points that run a decoder on a point list: the caller's own argument check (args_ok, with its text), the
+// workspace size, then the constants the tiles read instead of the latent columns of lin0 / lin4 (k_latent_consts), at the 256-byte
+// aligned start of the workspace. An empty list (n == 0) gets the checks only.
+int point_list_prologue(distr_ctx* ctx, const DecoderDev& D, const float* latent, int64_t n, bool args_ok, void* ws, size_t ws_bytes, size_t ws_need,
+                        hipStream_t s, float** c0c4, const char* bad_args = "bad argument", const char* small_ws = "workspace too small") {
+  if (!args_ok) return fail(ctx, DISTR_ERR_INVALID_ARG, "%s", bad_args);
+  if (ws_bytes < ws_need) return fail(ctx, DISTR_ERR_WORKSPACE, "%s", small_ws);
+  *c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  if (n == 0) return DISTR_OK;
+  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, *c0c4, D, latent);
+  LAUNCH_CHECK("k_latent_consts");
+  return DISTR_OK;
+}
 
 }  // namespace
 
@@ -608,9 +626,13 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
     offWf[l] = reserve(Wp[l].size());
     pack_fragments(Wp[l].data(), Kp[l], Op[l], host.data() + offWf[l]);
   }
-  for (int l = 1; l < 8; ++l) {
+  auto transposed = [&](int l) {   // Wp[l] as [K][O]: the backward dX chain multiplies by it (K' = Op[l], O' = Kp[l])
     std::vector<float> Wt((size_t)Kp[l] * Op[l]);
     for (int o = 0; o < Op[l]; ++o) for (int k = 0; k < Kp[l]; ++k) Wt[(size_t)k * Op[l] + o] = Wp[l][(size_t)o * Kp[l] + k];
+    return Wt;
+  };
+  for (int l = 1; l < 8; ++l) {
+    const std::vector<float> Wt = transposed(l);
     offWb[l] = reserve(Wt.size());
     pack_fragments(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], host.data() + offWb[l]);
   }
@@ -668,8 +690,7 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
       pack_fragments_b6(Wp[l].data(), Kp[l], Op[l], hb.data() + offb[l]);
     }
     for (int l = 1; l < 8; ++l) {   // transposed matrices (backward dX chain): K' = Op[l], O' = Kp[l]
-      std::vector<float> Wt((size_t)Kp[l] * Op[l]);
-      for (int o = 0; o < Op[l]; ++o) for (int k = 0; k < Kp[l]; ++k) Wt[(size_t)k * Op[l] + o] = Wp[l][(size_t)o * Kp[l] + k];
+      const std::vector<float> Wt = transposed(l);
       offbt[l] = (hb.size() + 127) & ~(size_t)127;
       hb.resize(offbt[l] + Wt.size() * 3, 0);
       pack_fragments_b6(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], hb.data() + offbt[l]);
@@ -683,8 +704,7 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
         if (!pack_fragments_h3(Wp[l].data(), Kp[l], Op[l], hb.data() + offh[l])) *h3_ok = false;
       }
       for (int l = 1; l < 8; ++l) {
-        std::vector<float> Wt((size_t)Kp[l] * Op[l]);
-        for (int o = 0; o < Op[l]; ++o) for (int k = 0; k < Kp[l]; ++k) Wt[(size_t)k * Op[l] + o] = Wp[l][(size_t)o * Kp[l] + k];
+        const std::vector<float> Wt = transposed(l);
         offht[l] = (hb.size() + 127) & ~(size_t)127;
         hb.resize(offht[l] + Wt.size() * 2, 0);
         (void)pack_fragments_h3(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], hb.data() + offht[l]);
@@ -708,9 +728,6 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
   }
   return DISTR_OK;
 }
-
-// the shape decoder runs the wide tile layout (code length < 256: k_march / k_bwd<..., WIDE>)
-static inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
 
 int distr_set_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, const float* w, size_t n_floats) {
   if (!ctx || !desc || !w) return fail(ctx, DISTR_ERR_INVALID_ARG, "null argument");
@@ -751,16 +768,13 @@ int distr_color_eval(distr_ctx* ctx, const float* latent_cat, const float* xyz, 
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
-  if (n < 0 || !latent_cat || (n > 0 && (!xyz || !rgb)) || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "colour workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)ws;
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->DC, latent_cat);
-  LAUNCH_CHECK("k_latent_consts");
-  if (n > 0) {
-    hipLaunchKernelGGL(k_color, dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, rgb, ctx->DC);
-    LAUNCH_CHECK("k_color");
-  }
+  float* c0c4;
+  const int rc = point_list_prologue(ctx, ctx->DC, latent_cat, n, !(n < 0 || !latent_cat || (n > 0 && (!xyz || !rgb)) || !ws), ws, ws_bytes,
+                                     distr_mlp_workspace_bytes(n), s, &c0c4, "null device pointer", "colour workspace too small");
+  if (rc || n == 0) return rc;
+  hipLaunchKernelGGL(k_color, dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, rgb, ctx->DC);
+  LAUNCH_CHECK("k_color");
   return DISTR_OK;
 }
 
@@ -770,17 +784,16 @@ int distr_color_backward(distr_ctx* ctx, const float* latent_cat, const float* x
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
-  if (n < 0 || !latent_cat || (n > 0 && (!xyz || !g_rgb)) || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  if (ws_bytes < distr_mlp_backward_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "colour backward workspace too small");
   hipStream_t s = (hipStream_t)stream;
+  float* c0c4;
+  const int rc = point_list_prologue(ctx, ctx->DC, latent_cat, n, !(n < 0 || !latent_cat || (n > 0 && (!xyz || !g_rgb)) || !ws), ws, ws_bytes,
+                                     distr_mlp_backward_workspace_bytes(n), s, &c0c4, "null device pointer", "colour backward workspace too small");
+  if (rc) return rc;
   if (n == 0) {
     if (g_latent_cat) HIP_TRY(hipMemsetAsync(g_latent_cat, 0, (size_t)ctx->DC.nlat * sizeof(float), s));
     return DISTR_OK;
   }
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   float* partial = (float*)(((uintptr_t)(c0c4 + 2 * HID) + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->DC, latent_cat);
-  LAUNCH_CHECK("k_latent_consts");
   const unsigned tiles = (unsigned)((n + 63) / 64);
   hipLaunchKernelGGL(k_color_bwd, dim3(tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, g_rgb, g_xyz, partial, ctx->DC);
   LAUNCH_CHECK("k_color_bwd");
@@ -820,6 +833,205 @@ int make_view_flags(distr_ctx* ctx, const distr_render_cfg& c, int nviews, const
 }
 
 inline int64_t pad_to(int64_t v, int64_t g) { return (v + g - 1) / g * g; }
+inline int32_t up8(int64_t v) { return (int32_t)((v + 7) / 8 * 8); }
+
+// ---- The variants of k_step, k_tail, k_march, k_march16 and k_bwd: distr_inst.hpp lists them. What the list holds, and what the callers
+// below therefore settle before they ask for one:
+//   * the wide layout (code length < 256) exists in f32 on 64-ray / 64- and 32-sample tiles only: no k_step, k_tail or k_march16, so wide
+//     decoders render launch-per-step without tail launch, cluster, sticky, 16- or 32-ray tiles (those generated loops are laid out for
+//     the narrow lin3); values are the same, only the schedule differs;
+//   * the split arithmetics (1 bf16x6, 2 f16x3) have no 16-ray role (k_march16 and k_tail are f32 only), no MODE_EVAL tiles, and their
+//     backward is the one over saved masks; check_cfg admits them for code length 256 only, so never together with wide.
+// A launcher looks the requested variant up in the list, launches it and checks the launch (`what` names it in the error text). A
+// combination without a line in the list is refused: no other instantiation is ever named, so this unit holds none of their code.
+inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
+
+#define DISTR_LAUNCH_IF(cond, kernel, ...) \
+  if (cond) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTHREADS), 0, s, __VA_ARGS__); LAUNCH_CHECK(what); return DISTR_OK; }
+// per family: which run-time values select a line of the list, and the kernel's arguments
+#define DISTR_TRY_STEP(K, AR) DISTR_LAUNCH_IF(keep == K && arith == AR, (k_step<K, AR>), A, ctx->D, ctx->D16, G)
+#define DISTR_TRY_TAIL(K) DISTR_LAUNCH_IF(keep == K, (k_tail<K>), A, ctx->D, ctx->D16)
+#define DISTR_TRY_MARCH(M, RB, K, AR, W) \
+  DISTR_LAUNCH_IF(mode == M && rb == RB && keep == K && arith == AR && wide == W, (k_march<M, RB, K, AR, W>), A, ctx->D)
+#define DISTR_TRY_MARCH16(M, K) DISTR_LAUNCH_IF(mode == M && keep == K, (k_march16<M, K>), A, ctx->D, ctx->D16)
+#define DISTR_TRY_BWD(M, RB, AR, W) DISTR_LAUNCH_IF(mode == M && rb == RB && arith == AR && wide == W, (k_bwd<M, RB, AR, W>), B, ctx->D)
+
+int launch_step(distr_ctx* ctx, const char* what, bool keep, int arith, unsigned grid, hipStream_t s, const MarchArgs& A, const StepGrid& G) {
+  DISTR_ALL_GROUPS(DISTR_TRY_STEP, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_step<%d, %d> (distr_inst.hpp)", (int)keep, arith);
+}
+
+int launch_tail(distr_ctx* ctx, const char* what, bool keep, unsigned grid, hipStream_t s, const MarchArgs& A) {
+  DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_TRY_TAIL, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_tail<%d> (distr_inst.hpp)", (int)keep);
+}
+
+int launch_march(distr_ctx* ctx, const char* what, int mode, int rb, bool keep, int arith, bool wide, unsigned grid, hipStream_t s, const MarchArgs& A) {
+  DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_TRY_MARCH, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_march<%d, %d, %d, %d, %d> (distr_inst.hpp)", mode, rb, (int)keep, arith, (int)wide);
+}
+
+int launch_march16(distr_ctx* ctx, const char* what, int mode, bool keep, unsigned grid, hipStream_t s, const MarchArgs& A) {
+  DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_TRY_MARCH16, DISTR_NO_VARIANT)
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_march16<%d, %d> (distr_inst.hpp)", mode, (int)keep);
+}
+
+int launch_bwd(distr_ctx* ctx, const char* what, int mode, int rb, int arith, bool wide, unsigned grid, hipStream_t s, const BwdArgs& B) {
+  DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_TRY_BWD)
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_bwd<%d, %d, %d, %d> (distr_inst.hpp)", mode, rb, arith, (int)wide);
+}
+
+// What a forward render has decided before its first march launch.
+struct RenderPlan {
+  int t16, t32;                 // largest remainders (rays) that run on 16- / 32-ray tiles (t16 = 0: no 16-ray role)
+  bool wide;                    // wide_decoder(): 64-ray tiles, one launch per step
+  bool b6, h3;                  // split-bf16 / split-f16 tiles (h3 implies b6): 64- and 32-ray roles only, no cluster tiles
+  bool recursive;               // live-ray lists + tile-size split (fine_split)
+  distr_ctx::XRegion* xr;       // exchange region of the cluster tiles, or null
+  int arith() const { return h3 ? DISTR_ARITH_F16X3 : b6 ? DISTR_ARITH_BF16X6 : DISTR_ARITH_F32; }
+};
+
+// persistent tail launch: from which full-resolution step on (see distr_ctx::tail); sets V.tail_from, returns the device word k_finalize
+// writes the next render's hint to (or null)
+int32_t* choose_tail_from(distr_ctx* ctx, View& V, hipStream_t s) {
+  int32_t* hint_dev = nullptr;
+  if (V.cfg.marcher == DISTR_MARCH_TRIVIAL || V.cfg.arith != DISTR_ARITH_F32 || !ctx->tail || V.cfg.concurrent || ctx->tail16_threshold <= 0 ||
+      wide_decoder(ctx))
+    return hint_dev;
+  int32_t* hint = tail_hint_slot(ctx, V.cfg, V.nviews, is_capturing(s), &hint_dev);
+  if (ctx->tail_force >= 0) V.tail_from = std::min(ctx->tail_force, V.fine_steps);
+  else if ((int64_t)V.nviews * V.P <= ctx->tail_px) V.tail_from = 0;
+  else if (hint) {
+    const int32_t h = __atomic_load_n(hint, __ATOMIC_RELAXED);
+    if (h >= 0 && h + 2 <= V.fine_steps) V.tail_from = h;      // (nothing to gain from a tail of one step)
+  }
+  return hint_dev;
+}
+
+int setup_levels(distr_ctx* ctx, const View& V, const float* latent, int64_t lat_stride, const float* R, const float* T, const ViewFlags& vf,
+                 hipStream_t s) {
+  hipLaunchKernelGGL(k_prep, dim3(4, (unsigned)V.nviews), dim3(256), 0, s, V, ctx->D, latent, lat_stride, R, T, vf);
+  LAUNCH_CHECK("k_prep");
+  for (int l = 0; l < V.nlev; ++l) {
+    hipLaunchKernelGGL(k_setup_level, gridv(V, V.lv[l].n), dim3(256), 0, s, V, l);
+    LAUNCH_CHECK("k_setup_level");
+    if (V.band) {
+      hipLaunchKernelGGL(k_maxinit_full, gridv(V, (int64_t)V.lv[l].full_h * V.lv[l].w), dim3(256), 0, s, V, l);
+      LAUNCH_CHECK("k_maxinit_full");
+    }
+  }
+  return DISTR_OK;
+}
+
+// the coarse levels of the pyramid, coarsest first: one march launch per step
+int march_coarse(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p, MarchTimer& timer, hipStream_t s) {
+  const int nviews = V.nviews;
+  const bool keep = V.save_masks != 0;
+  for (int l = V.nlev - 1; l >= 1; --l) {
+    hipLaunchKernelGGL(k_coarse_init, gridv(V, V.lv[l].n), dim3(256), 0, s, V, l);
+    LAUNCH_CHECK("k_coarse_init");
+    for (int st = 0; st < V.lv[l].steps; ++st) {
+      A.lvl = l; A.step = st; A.origin_tile = 0;
+      // tile size of a coarse level from the (host-known) pixel count of all views: a level that fits one round of 16- / 32-ray
+      // tiles runs on those (small images: 111 / 212 us per step instead of 380 us)
+      const int64_t ln = V.lv[l].n;
+      const bool c16 = !p.b6 && !p.wide && nviews * pad_to(ln, 16) <= p.t16;
+      const int crb = (!p.wide && nviews * pad_to(ln, 32) <= p.t32) ? 1 : 2;
+      const int ctile = c16 ? 16 : 32 * crb;
+      unsigned tiles = (unsigned)nviews * (unsigned)((ln + ctile - 1) / ctile);
+      A.xc = next_xchg(c16 ? p.xr : nullptr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, 1, false, ctx->xchg_sc1);
+      A.xc.spread = ctx->cluster_spread;
+      if (c16 && p.xr) tiles = std::max(tiles, 256u);      // cluster tiles: up to 8 workgroups per 16 rays
+      timer.begin();
+      const int rc = c16 ? launch_march16(ctx, "k_march<coarse>", MODE_COARSE, keep, tiles, s, A)
+                         : launch_march(ctx, "k_march<coarse>", MODE_COARSE, crb, keep, p.arith(), p.wide, tiles, s, A);
+      if (rc) return rc;
+      timer.end();
+    }
+  }
+  return DISTR_OK;
+}
+
+// the full-resolution steps: a march launch per step ('trivial', wide decoders), or k_step per step up to tail_from and k_tail from there
+int march_fine(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p, MarchTimer& timer, hipStream_t s) {
+  const int nviews = V.nviews, P = V.P, t16 = p.t16, t32 = p.t32;
+  const unsigned NV = (unsigned)nviews;
+  const bool keep = V.save_masks != 0;
+  hipLaunchKernelGGL(k_fine_init, gridv(V, P), dim3(256), 0, s, V);
+  LAUNCH_CHECK("k_fine_init");
+  // upper bounds of a step's live rays in the virtual concatenation of the views (every view padded to 16 / 64 rays)
+  const int64_t N64 = (int64_t)nviews * pad_to(P, 64);
+  for (int st = 0; st < V.fine_steps; ++st) {
+    A.lvl = 0; A.step = st;
+    timer.begin();
+    if (st == V.tail_from) {
+      // every remaining step inside this launch (k_tail): 256 workgroups, one per compute unit
+      A.origin_tile = 1;
+      A.xc = next_xchg(p.xr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, (uint32_t)(V.fine_steps - st), ctx->sticky, ctx->xchg_sc1);
+      A.xc.spread = ctx->cluster_spread;
+      A.xc.t_go = TAIL_T_GO;
+      A.tail_absent = ctx->tail_absent;
+      if (int rc = launch_tail(ctx, "k_tail", keep, 256, s, A)) return rc;
+      timer.end();
+      break;
+    }
+    if (!p.recursive || p.wide) {
+      // 'trivial': every in-sphere ray, every step, on 64-ray tiles. Wide decoders: also the recursive marchers' live-ray lists (t16 =
+      // t32 = 0: fine_split hands every ray to the 64-ray role), f(origin) on the last step like k_step
+      A.origin_tile = (p.recursive ? st == V.fine_steps - 1 : st == 0) ? 1 : 0;
+      const unsigned tiles = NV * (unsigned)((P + 63) / 64) + (A.origin_tile ? NV : 0u);
+      if (int rc = launch_march(ctx, "k_march<fine>", MODE_FINE, 2, keep, p.arith(), p.wide, tiles, s, A)) return rc;
+      timer.end();
+      continue;
+    }
+    // one launch per step: the three tile sizes are roles of the same grid (k_step, fine_split). Roles that are provably empty
+    // from the pixel count alone get no workgroups: with N64 <= bound the remainder rules never reach the 64-ray role (bound <
+    // one round, distr_create), with N64 <= t16 the 32-ray role stays empty too.
+    const int64_t bound = (t16 < t32) ? (int64_t)t32 + t16 : t32;
+    const bool skip64 = N64 <= bound;
+    const bool skip32 = t32 <= t16 || N64 <= t16;
+    StepGrid G;
+    G.n64 = skip64 ? 0 : std::min(up8(N64 / 64), 256);            // persistent: at most one 64-ray workgroup per CU
+    A.origin_tile = (st == V.fine_steps - 1) ? 1 : 0;
+    if (p.b6) {
+      // split-bf16: no 16-ray role; the views' origin tiles (last step) close the 32-ray role's grid
+      G.n32 = up8(std::min<int64_t>(N64, t32) / 32 + (A.origin_tile ? nviews : 0));
+      G.n16 = 0;
+      A.xc = next_xchg(nullptr, s, false, ctx->max_cl, 0, ctx->min_cl);
+    } else {
+      G.n32 = skip32 ? 0 : up8(std::min<int64_t>(N64, t32) / 32);
+      A.xc = next_xchg(p.xr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, (uint32_t)(V.fine_steps - st), ctx->sticky && !V.cfg.concurrent, ctx->xchg_sc1);
+      A.xc.spread = ctx->cluster_spread;
+      unsigned n16 = (unsigned)(std::min<int64_t>(N64, t16) / 16) + (A.origin_tile ? NV : 0u);
+      if (p.xr) n16 = std::max(n16, 256u);                           // cluster tiles: 8 / 4 / 2 workgroups per tile of at most 32 / 64 / 128
+      G.n16 = up8(n16);
+    }
+    if (int rc = launch_step(ctx, "k_step", keep, p.arith(), (unsigned)(G.n64 + G.n32 + G.n16), s, A, G)) return rc;
+    timer.end();
+  }
+  return DISTR_OK;
+}
+
+int finalize_and_normals(distr_ctx* ctx, const View& V, bool wide, int32_t* hint_dev, float* zdepth, uint8_t* mask,
+                         float* min_sdf, float* depth, float* normal, hipStream_t s) {
+  const int P = V.P;
+  hipLaunchKernelGGL(k_finalize, gridv(V, P), dim3(256), 0, s, V, zdepth, mask, min_sdf, depth, hint_dev, (int32_t)ctx->tail_rays);
+  LAUNCH_CHECK("k_finalize");
+  if (!V.cfg.want_normal) return DISTR_OK;
+  if (V.cfg.use_depth2normal) {
+    hipLaunchKernelGGL(k_depth2normal, gridv(V, P), dim3(256), 0, s, V, depth, normal);
+    LAUNCH_CHECK("k_depth2normal");
+    return DISTR_OK;
+  }
+  if (normal) HIP_TRY(hipMemsetAsync(normal, 0, (size_t)V.nviews * P * 3 * sizeof(float), s));
+  BwdArgs B;
+  memset(&B, 0, sizeof(B));
+  B.V = V; B.zdepth = V.zdepth_s; B.zstride = V.vstride;
+  if (int rc = launch_bwd(ctx, "k_bwd<pointgrad>", BWD_POINTGRAD, 2, 0, wide, (unsigned)V.nviews * (unsigned)((P + 63) / 64), s, B)) return rc;
+  hipLaunchKernelGGL(k_normal_finish, gridv(V, P), dim3(256), 0, s, V, normal, (float*)nullptr, 1);
+  LAUNCH_CHECK("k_normal_finish");
+  return DISTR_OK;
+}
 
 int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, const int32_t* view_flags, const float* latent,
                         int64_t lat_stride, const float* R, const float* T, float* zdepth, uint8_t* mask, float* min_sdf,
@@ -837,199 +1049,28 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   rc = make_view_flags(ctx, *cfg, nviews, view_flags, vf);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const DecoderDev& D = ctx->D;
-  const int P = V.P;
-  const unsigned NV = (unsigned)nviews;
-  auto gridv = [&](int64_t n) { return dim3((unsigned)((n + 255) / 256), NV); };   // (blocks of 256, view)
-
-  // persistent tail launch: from which full-resolution step on (see distr_ctx::tail)
-  int32_t* hint_dev = nullptr;
-  // wide decoders (code length < 256) render launch-per-step on 64-ray tiles: no tail launch, no cluster / sticky / 16- / 32-ray tiles
-  // (their generated loops are laid out for the narrow lin3); values are the same, only the schedule differs
-  const bool wide = wide_decoder(ctx);
-  if (cfg->marcher != DISTR_MARCH_TRIVIAL && cfg->arith == DISTR_ARITH_F32 && ctx->tail && !cfg->concurrent && ctx->tail16_threshold > 0 && !wide) {
-    bool capturing = false;
-    {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-      else capturing = cs != hipStreamCaptureStatusNone;
-    }
-    int32_t* hint = tail_hint_slot(ctx, *cfg, nviews, capturing, &hint_dev);
-    if (ctx->tail_force >= 0) V.tail_from = std::min(ctx->tail_force, V.fine_steps);
-    else if ((int64_t)nviews * P <= ctx->tail_px) V.tail_from = 0;
-    else if (hint) {
-      const int32_t h = __atomic_load_n(hint, __ATOMIC_RELAXED);
-      if (h >= 0 && h + 2 <= V.fine_steps) V.tail_from = h;      // (nothing to gain from a tail of one step)
-    }
-  }
-
-  hipLaunchKernelGGL(k_prep, dim3(4, NV), dim3(256), 0, s, V, D, latent, lat_stride, R, T, vf);
-  LAUNCH_CHECK("k_prep");
-  for (int l = 0; l < V.nlev; ++l) {
-    hipLaunchKernelGGL(k_setup_level, gridv(V.lv[l].n), dim3(256), 0, s, V, l);
-    LAUNCH_CHECK("k_setup_level");
-    if (V.band) {
-      hipLaunchKernelGGL(k_maxinit_full, gridv((int64_t)V.lv[l].full_h * V.lv[l].w), dim3(256), 0, s, V, l);
-      LAUNCH_CHECK("k_maxinit_full");
-    }
-  }
+  int32_t* hint_dev = choose_tail_from(ctx, V, s);
+  if ((rc = setup_levels(ctx, V, latent, lat_stride, R, T, vf, s))) return rc;
+  RenderPlan p;
+  p.wide = wide_decoder(ctx);
+  p.b6 = cfg->arith != DISTR_ARITH_F32;
+  p.h3 = cfg->arith == DISTR_ARITH_F16X3;
+  p.recursive = cfg->marcher != DISTR_MARCH_TRIVIAL;
+  p.t32 = ctx->hybrid_threshold; p.t16 = p.b6 ? 0 : std::min(ctx->tail16_threshold, ctx->hybrid_threshold);
   MarchTimer timer(ctx, s);
   MarchArgs A;
   memset(&A, 0, sizeof(A));
   A.V = V;
   A.B6 = ctx->B6;
   A.H3 = ctx->H3;
-  const bool b6 = cfg->arith != DISTR_ARITH_F32;                   // split-bf16 / split-f16 tiles: 64- and 32-ray roles only, no cluster tiles
-  const bool h3 = cfg->arith == DISTR_ARITH_F16X3;
-  const bool recursive = cfg->marcher != DISTR_MARCH_TRIVIAL;     // live-ray lists + tile-size split (fine_split)
-  const int t32 = ctx->hybrid_threshold, t16 = b6 ? 0 : std::min(ctx->tail16_threshold, ctx->hybrid_threshold);
-  A.t16 = (recursive && !wide) ? t16 : 0; A.t32 = (recursive && !wide) ? t32 : 0; A.which = 64;
+  const bool split = p.recursive && !p.wide;         // else every ray on 64-ray tiles
+  A.t16 = split ? p.t16 : 0; A.t32 = split ? p.t32 : 0; A.which = 64;
   // f(origin) of every view (sample point of padded rows) is evaluated by nviews extra workgroups of ONE march launch: for the
   // recursive marchers they ride on the 16-ray role of the last step (free: a tail step); 'trivial' puts them on its first launch
-  distr_ctx::XRegion* xr = (recursive && !b6 && !wide) ? xchg_region(ctx, s) : nullptr;
-  auto up8 = [](int64_t v) { return (int32_t)((v + 7) / 8 * 8); };
-  for (int l = V.nlev - 1; l >= 1; --l) {
-    hipLaunchKernelGGL(k_coarse_init, gridv(V.lv[l].n), dim3(256), 0, s, V, l);
-    LAUNCH_CHECK("k_coarse_init");
-    for (int st = 0; st < V.lv[l].steps; ++st) {
-      A.lvl = l; A.step = st; A.origin_tile = 0;
-      // tile size of a coarse level from the (host-known) pixel count of all views: a level that fits one round of 16- / 32-ray
-      // tiles runs on those (small images: 111 / 212 us per step instead of 380 us)
-      const int64_t ln = V.lv[l].n;
-      const bool c16 = !b6 && !wide && nviews * pad_to(ln, 16) <= t16;
-      const int crb = (!wide && nviews * pad_to(ln, 32) <= t32) ? 1 : 2;
-      const int ctile = c16 ? 16 : 32 * crb;
-      unsigned tiles = NV * (unsigned)((ln + ctile - 1) / ctile);
-      A.xc = next_xchg(c16 ? xr : nullptr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, 1, false, ctx->xchg_sc1);
-      A.xc.spread = ctx->cluster_spread;
-      if (c16 && xr) tiles = std::max(tiles, 256u);      // cluster tiles: up to 8 workgroups per 16 rays
-      timer.begin();
-      if (wide) {
-        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_COARSE, 2, true, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, false, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      } else if (c16) {
-        if (V.save_masks) hipLaunchKernelGGL((k_march16<MODE_COARSE, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D, ctx->D16);
-        else hipLaunchKernelGGL((k_march16<MODE_COARSE, false>), dim3(tiles), dim3(NTHREADS), 0, s, A, D, ctx->D16);
-      } else if (h3) {
-        if (V.save_masks) {
-          if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, true, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-          else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, true, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        } else {
-          if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, false, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-          else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, false, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        }
-      } else if (b6) {
-        if (V.save_masks) {
-          if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, true, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-          else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, true, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        } else {
-          if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, false, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-          else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, false, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        }
-      } else if (V.save_masks) {
-        if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      } else {
-        if (crb == 1) hipLaunchKernelGGL((k_march<MODE_COARSE, 1, false>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_COARSE, 2, false>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      }
-      timer.end();
-      LAUNCH_CHECK("k_march<coarse>");
-    }
-  }
-  hipLaunchKernelGGL(k_fine_init, gridv(P), dim3(256), 0, s, V);
-  LAUNCH_CHECK("k_fine_init");
-  // upper bounds of a step's live rays in the virtual concatenation of the views (every view padded to 16 / 64 rays)
-  const int64_t N64 = (int64_t)nviews * pad_to(P, 64);
-  for (int st = 0; st < V.fine_steps; ++st) {
-    A.lvl = 0; A.step = st;
-    timer.begin();
-    if (st == V.tail_from) {
-      // every remaining step inside this launch (k_tail): 256 workgroups, one per compute unit
-      A.origin_tile = 1;
-      A.xc = next_xchg(xr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, (uint32_t)(V.fine_steps - st), ctx->sticky, ctx->xchg_sc1);
-      A.xc.spread = ctx->cluster_spread;
-      A.xc.t_go = TAIL_T_GO;
-      A.tail_absent = ctx->tail_absent;
-      if (V.save_masks) hipLaunchKernelGGL((k_tail<true>), dim3(256), dim3(NTHREADS), 0, s, A, D, ctx->D16);
-      else hipLaunchKernelGGL((k_tail<false>), dim3(256), dim3(NTHREADS), 0, s, A, D, ctx->D16);
-      timer.end();
-      LAUNCH_CHECK("k_tail");
-      break;
-    }
-    if (!recursive || wide) {
-      // 'trivial': every in-sphere ray, every step, on 64-ray tiles. Wide decoders: also the recursive marchers' live-ray lists (t16 =
-      // t32 = 0: fine_split hands every ray to the 64-ray role), f(origin) on the last step like k_step
-      A.origin_tile = (recursive ? st == V.fine_steps - 1 : st == 0) ? 1 : 0;
-      const unsigned tiles = NV * (unsigned)((P + 63) / 64) + (A.origin_tile ? NV : 0u);
-      if (wide) {
-        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      } else if (h3) {
-        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false, 2>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      } else if (b6) {
-        if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-        else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false, 1>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      } else if (V.save_masks) hipLaunchKernelGGL((k_march<MODE_FINE, 2, true>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      else hipLaunchKernelGGL((k_march<MODE_FINE, 2, false>), dim3(tiles), dim3(NTHREADS), 0, s, A, D);
-      timer.end();
-      LAUNCH_CHECK("k_march<fine>");
-      continue;
-    }
-    // one launch per step: the three tile sizes are roles of the same grid (k_step, fine_split). Roles that are provably empty
-    // from the pixel count alone get no workgroups: with N64 <= bound the remainder rules never reach the 64-ray role (bound <
-    // one round, distr_create), with N64 <= t16 the 32-ray role stays empty too.
-    const int64_t bound = (t16 < t32) ? (int64_t)t32 + t16 : t32;
-    const bool skip64 = N64 <= bound;
-    const bool skip32 = t32 <= t16 || N64 <= t16;
-    StepGrid G;
-    G.n64 = skip64 ? 0 : std::min(up8(N64 / 64), 256);            // persistent: at most one 64-ray workgroup per CU
-    A.origin_tile = (st == V.fine_steps - 1) ? 1 : 0;
-    if (b6) {
-      // split-bf16: no 16-ray role; the views' origin tiles (last step) close the 32-ray role's grid
-      G.n32 = up8(std::min<int64_t>(N64, t32) / 32 + (A.origin_tile ? nviews : 0));
-      G.n16 = 0;
-      A.xc = next_xchg(nullptr, s, false, ctx->max_cl, 0, ctx->min_cl);
-      const unsigned grid = (unsigned)(G.n64 + G.n32);
-      if (h3) {
-        if (V.save_masks) hipLaunchKernelGGL((k_step<true, 2>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-        else hipLaunchKernelGGL((k_step<false, 2>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-      } else if (V.save_masks) hipLaunchKernelGGL((k_step<true, 1>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-      else hipLaunchKernelGGL((k_step<false, 1>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-    } else {
-      G.n32 = skip32 ? 0 : up8(std::min<int64_t>(N64, t32) / 32);
-      A.xc = next_xchg(xr, s, ctx->xchg_ts, ctx->max_cl, ctx->cluster_test_abort, ctx->min_cl, (uint32_t)(V.fine_steps - st), ctx->sticky && !cfg->concurrent, ctx->xchg_sc1);
-      A.xc.spread = ctx->cluster_spread;
-      unsigned n16 = (unsigned)(std::min<int64_t>(N64, t16) / 16) + (A.origin_tile ? NV : 0u);
-      if (xr) n16 = std::max(n16, 256u);                             // cluster tiles: 8 / 4 / 2 workgroups per tile of at most 32 / 64 / 128
-      G.n16 = up8(n16);
-      const unsigned grid = (unsigned)(G.n64 + G.n32 + G.n16);
-      if (V.save_masks) hipLaunchKernelGGL((k_step<true>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-      else hipLaunchKernelGGL((k_step<false>), dim3(grid), dim3(NTHREADS), 0, s, A, D, ctx->D16, G);
-    }
-    timer.end();
-    LAUNCH_CHECK("k_step");
-  }
-  hipLaunchKernelGGL(k_finalize, gridv(P), dim3(256), 0, s, V, zdepth, mask, min_sdf, depth, hint_dev, (int32_t)ctx->tail_rays);
-  LAUNCH_CHECK("k_finalize");
-  if (cfg->want_normal) {
-    if (cfg->use_depth2normal) {
-      hipLaunchKernelGGL(k_depth2normal, gridv(P), dim3(256), 0, s, V, depth, normal);
-      LAUNCH_CHECK("k_depth2normal");
-    } else {
-      if (normal) HIP_TRY(hipMemsetAsync(normal, 0, (size_t)nviews * P * 3 * sizeof(float), s));
-      BwdArgs B;
-      memset(&B, 0, sizeof(B));
-      B.V = V; B.zdepth = V.zdepth_s; B.zstride = V.vstride;
-      if (wide) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      LAUNCH_CHECK("k_bwd<pointgrad>");
-      hipLaunchKernelGGL(k_normal_finish, gridv(P), dim3(256), 0, s, V, normal, (float*)nullptr, 1);
-      LAUNCH_CHECK("k_normal_finish");
-    }
-  }
-  return DISTR_OK;
+  p.xr = (split && !p.b6) ? xchg_region(ctx, s) : nullptr;
+  if ((rc = march_coarse(ctx, V, A, p, timer, s))) return rc;
+  if ((rc = march_fine(ctx, V, A, p, timer, s))) return rc;
+  return finalize_and_normals(ctx, V, p.wide, hint_dev, zdepth, mask, min_sdf, depth, normal, s);
 }
 
 int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, const void* ws, size_t ws_bytes, const float* g_zdepth,
@@ -1075,27 +1116,12 @@ int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews
   // tile-size split of every view's sample list (bwd_range): full rounds on 64-sample tiles, a small remainder on 32-sample tiles
   const bool wide = wide_decoder(ctx);       // (wide decoders: the same tile split, so the same partial rows and reduction order)
   const bool bsplit = V.save_masks != 0;
-  if (bsplit) {
-    B.split = 1;
-    if (wide) {
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2, 0, true>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1, 0, true>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
-    } else if (cfg->arith == DISTR_ARITH_F16X3) {      // the dX chain in the arithmetic of the forward it differentiates
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2, 2>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1, 2>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
-    } else if (cfg->arith == DISTR_ARITH_BF16X6) {
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2, 1>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1, 1>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
-    } else {
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 2>), dim3(NV * (unsigned)((smax + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-      hipLaunchKernelGGL((k_bwd<BWD_SAVED, 1>), dim3(NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32)), dim3(NTHREADS), 0, s, B, D);
-    }
-  } else if (wide) {
-    hipLaunchKernelGGL((k_bwd<BWD_FULL, 2, 0, true>), dim3(NV * tiles), dim3(NTHREADS), 0, s, B, D);
-  } else {
-    hipLaunchKernelGGL((k_bwd<BWD_FULL, 2>), dim3(NV * tiles), dim3(NTHREADS), 0, s, B, D);     // DISTR_SAVE_MASKS=0: recompute the forward
-  }
-  LAUNCH_CHECK("k_bwd");
+  B.split = bsplit ? 1 : 0;
+  if (bsplit) {     // the dX chain in the arithmetic of the forward it differentiates
+    rc = launch_bwd(ctx, "k_bwd", BWD_SAVED, 2, cfg->arith, wide, NV * (unsigned)((smax + 63) / 64), s, B);
+    if (!rc) rc = launch_bwd(ctx, "k_bwd", BWD_SAVED, 1, cfg->arith, wide, NV * (unsigned)((std::min<size_t>(smax, 8192) + 31) / 32), s, B);
+  } else rc = launch_bwd(ctx, "k_bwd", BWD_FULL, 2, 0, wide, NV * tiles, s, B);     // DISTR_SAVE_MASKS=0: recompute the forward
+  if (rc) return rc;
   hipLaunchKernelGGL(k_bwd_reduce, dim3((2 * HID + 12 + 255) / 256, nchunks, NV), dim3(256), 0, s, V, W, BWD_CHUNK, bsplit ? -1 : TILE);
   LAUNCH_CHECK("k_bwd_reduce");
   hipLaunchKernelGGL(k_bwd_final, dim3(NV), dim3(256), 0, s, V, D, W, (int)nchunks, BWD_CHUNK, bsplit ? -1 : TILE, g_latent, g_R, g_T);
@@ -1130,9 +1156,7 @@ int render_normal_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, 
   BwdArgs B;
   memset(&B, 0, sizeof(B));
   B.V = V; B.zdepth = zdepth; B.zstride = (int64_t)P * sizeof(float);
-  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(NV * (unsigned)((P + 63) / 64)), dim3(NTHREADS), 0, s, B, D);
-  LAUNCH_CHECK("k_bwd<pointgrad>");
+  if ((rc = launch_bwd(ctx, "k_bwd<pointgrad>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), NV * (unsigned)((P + 63) / 64), s, B))) return rc;
   hipLaunchKernelGGL(k_normal_finish, dim3((unsigned)((P + 255) / 256), NV), dim3(256), 0, s, V, (float*)nullptr, normal3xP, 0);
   LAUNCH_CHECK("k_normal_finish");
   return DISTR_OK;
@@ -1143,9 +1167,7 @@ int render_normal_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews, 
 int distr_render_forward(distr_ctx* ctx, const distr_render_cfg* cfg, const float* latent, const float* R, const float* T,
                          float* zdepth, uint8_t* mask, float* min_sdf, float* depth, float* normal, void* ws, size_t ws_bytes,
                          void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  return render_forward_impl(ctx, cfg, 1, nullptr, latent, 0, R, T, zdepth, mask, min_sdf, depth, normal, ws, ws_bytes, stream);
+  return distr_render_forward_batch(ctx, cfg, 1, nullptr, latent, 0, R, T, zdepth, mask, min_sdf, depth, normal, ws, ws_bytes, stream);
 }
 
 int distr_render_forward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const int32_t* view_flags,
@@ -1160,10 +1182,7 @@ int distr_render_forward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int3
 int distr_render_backward(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws, size_t ws_bytes, const float* g_zdepth,
                           const float* g_min_sdf, const float* g_depth, const float* g_normal, float* g_latent, float* g_R,
                           float* g_T, void* ws_bwd, size_t ws_bwd_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  return render_backward_impl(ctx, cfg, 1, ws, ws_bytes, g_zdepth, g_min_sdf, g_depth, g_normal, g_latent, g_R, g_T, ws_bwd,
-                              ws_bwd_bytes, stream);
+  return distr_render_backward_batch(ctx, cfg, 1, ws, ws_bytes, g_zdepth, g_min_sdf, g_depth, g_normal, g_latent, g_R, g_T, ws_bwd, ws_bwd_bytes, stream);
 }
 
 int distr_render_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const void* ws, size_t ws_bytes,
@@ -1177,9 +1196,7 @@ int distr_render_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int
 
 int distr_render_normal(distr_ctx* ctx, const distr_render_cfg* cfg, const float* latent, const float* R, const float* T,
                         const float* zdepth, const uint8_t* mask, float* normal3xP, void* ws, size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  return render_normal_impl(ctx, cfg, 1, latent, 0, R, T, zdepth, mask, normal3xP, ws, ws_bytes, stream);
+  return distr_render_normal_batch(ctx, cfg, 1, latent, 0, R, T, zdepth, mask, normal3xP, ws, ws_bytes, stream);
 }
 
 int distr_render_normal_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const float* latent, int64_t latent_stride,
@@ -1197,13 +1214,10 @@ int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
-  if (n == 0) return DISTR_OK;
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);
-  LAUNCH_CHECK("k_latent_consts");
+  float* c0c4;
+  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  if (rc || n == 0) return rc;
   MarchArgs A;
   memset(&A, 0, sizeof(A));
   A.xyz = xyz; A.sdf_out = sdf; A.c0c4 = c0c4; A.n = n; A.clamp = clamp;
@@ -1211,57 +1225,43 @@ int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   timer.begin();
   // a point list that fits one wave of 16-ray tiles runs on those (107 us instead of a 380 us 64-ray tile: decode_sdf on a few
   // thousand points is latency-bound); same values bit for bit
-  if (wide_decoder(ctx))
-    hipLaunchKernelGGL((k_march<MODE_EVAL, 2, false, 0, true>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, A, ctx->D);
-  else if (n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold))
-    hipLaunchKernelGGL((k_march16<MODE_EVAL, false>), dim3((unsigned)((n + 15) / 16)), dim3(NTHREADS), 0, s, A, ctx->D, ctx->D16);
-  else hipLaunchKernelGGL((k_march<MODE_EVAL, 2, false>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, A, ctx->D);
+  const bool wide = wide_decoder(ctx);
+  if (!wide && n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold)) rc = launch_march16(ctx, "k_march<eval>", MODE_EVAL, false, (unsigned)((n + 15) / 16), s, A);
+  else rc = launch_march(ctx, "k_march<eval>", MODE_EVAL, 2, false, 0, wide, (unsigned)((n + 63) / 64), s, A);
   timer.end();
-  LAUNCH_CHECK("k_march<eval>");
+  return rc;
+}
+
+// decode_sdf in one of the split arithmetics (h3: f16x3, else bf16x6)
+static int mlp_eval_split(distr_ctx* ctx, bool h3, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
+                          size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "%s: built for code length %d only (this decoder: %d); use f32", h3 ? "f16x3" : "bf16x6", LAT, ctx->D.nlat);
+  if (h3 && !ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
+  hipStream_t s = (hipStream_t)stream;
+  float* c0c4;      // (exact f32: the latent columns stay a per-call constant)
+  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  if (rc || n == 0) return rc;
+  const dim3 grid((unsigned)((n + 63) / 64));
+  MarchTimer timer(ctx, s);
+  timer.begin();
+  if (h3) hipLaunchKernelGGL(k_eval_h3, grid, dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->H3);
+  else hipLaunchKernelGGL(k_eval_b6, grid, dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->B6);
+  timer.end();
+  LAUNCH_CHECK(h3 ? "k_eval_h3" : "k_eval_b6");
   return DISTR_OK;
 }
 
 int distr_mlp_eval_bf16x6(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
                           size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "bf16x6: built for code length %d only (this decoder: %d); use f32", LAT, ctx->D.nlat);
-  if (n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
-  if (n == 0) return DISTR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);      // (exact f32: the latent columns stay a per-call constant)
-  LAUNCH_CHECK("k_latent_consts");
-  MarchTimer timer(ctx, s);
-  timer.begin();
-  hipLaunchKernelGGL(k_eval_b6, dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->B6);
-  timer.end();
-  LAUNCH_CHECK("k_eval_b6");
-  return DISTR_OK;
+  return mlp_eval_split(ctx, false, latent, xyz, n, clamp, sdf, ws, ws_bytes, stream);
 }
 
 int distr_mlp_eval_f16x3(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
                          size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: built for code length %d only (this decoder: %d); use f32", LAT, ctx->D.nlat);
-  if (!ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
-  if (n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
-  if (n == 0) return DISTR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);      // (exact f32: the latent columns stay a per-call constant)
-  LAUNCH_CHECK("k_latent_consts");
-  MarchTimer timer(ctx, s);
-  timer.begin();
-  hipLaunchKernelGGL(k_eval_h3, dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->H3);
-  timer.end();
-  LAUNCH_CHECK("k_eval_h3");
-  return DISTR_OK;
+  return mlp_eval_split(ctx, true, latent, xyz, n, clamp, sdf, ws, ws_bytes, stream);
 }
 
 int distr_mlp_grad(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float* sdf, float* grad, void* ws,
@@ -1269,20 +1269,14 @@ int distr_mlp_grad(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (n < 0 || (n > 0 && (!xyz || !sdf || !grad)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
-  if (n == 0) return DISTR_OK;
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);
-  LAUNCH_CHECK("k_latent_consts");
+  float* c0c4;
+  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf || !grad)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  if (rc || n == 0) return rc;
   BwdArgs B;
   memset(&B, 0, sizeof(B));
   B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.out_sdf = sdf; B.out_g = grad;
-  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, B, ctx->D);
-  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, B, ctx->D);
-  LAUNCH_CHECK("k_bwd<pointgrad>");
-  return DISTR_OK;
+  return launch_bwd(ctx, "k_bwd<pointgrad>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), (unsigned)((n + 63) / 64), s, B);
 }
 
 size_t distr_mlp_backward_workspace_bytes(int64_t n) {
@@ -1295,24 +1289,20 @@ int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, in
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (n < 0 || (n > 0 && (!xyz || !g_sdf)) || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_backward_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
+  float* c0c4;
+  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !g_sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_backward_workspace_bytes(n), s, &c0c4);
+  if (rc) return rc;
   if (n == 0) {
     if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)ctx->D.nlat * sizeof(float), s));
     return DISTR_OK;
   }
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   float* partial = (float*)(((uintptr_t)(c0c4 + 2 * HID) + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);
-  LAUNCH_CHECK("k_latent_consts");
   BwdArgs B;
   memset(&B, 0, sizeof(B));
   B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.coef = g_sdf; B.clamp = clamp; B.partial = partial; B.out_g = g_xyz;
   const unsigned tiles = (unsigned)((n + 63) / 64);
-  if (wide_decoder(ctx)) hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2, 0, true>), dim3(tiles), dim3(NTHREADS), 0, s, B, ctx->D);
-  else hipLaunchKernelGGL((k_bwd<BWD_POINTGRAD, 2>), dim3(tiles), dim3(NTHREADS), 0, s, B, ctx->D);
-  LAUNCH_CHECK("k_bwd<pointgrad+latent>");
+  if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), tiles, s, B))) return rc;
   if (g_latent) {
     hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->D, g_latent);
     LAUNCH_CHECK("k_points_latent_grad");
@@ -1326,12 +1316,10 @@ int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz,
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
   if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
-  if (n <= 0 || !xyz || !out || !latent || !ws || layer < 0 || layer > 7) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);
-  LAUNCH_CHECK("k_latent_consts");
+  float* c0c4;
+  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n <= 0 || !xyz || !out || !latent || !ws || layer < 0 || layer > 7), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  if (rc) return rc;
   hipLaunchKernelGGL((k_debug_layer<2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, layer, out, ctx->D, (long long*)nullptr);
   LAUNCH_CHECK("k_debug_layer");
   return DISTR_OK;
@@ -1343,14 +1331,23 @@ int distr_debug_tile_timing(distr_ctx* ctx, const float* latent, const float* xy
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
   if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
-  if (n <= 0 || !xyz || !sdf_out || !ts_out || !latent || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");
-  if (ws_bytes < distr_mlp_workspace_bytes(n)) return fail(ctx, DISTR_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, c0c4, ctx->D, latent);
-  LAUNCH_CHECK("k_latent_consts");
+  float* c0c4;
+  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n <= 0 || !xyz || !sdf_out || !ts_out || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  if (rc) return rc;
   hipLaunchKernelGGL((k_debug_layer<2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, 8, sdf_out, ctx->D, ts_out);
   LAUNCH_CHECK("k_debug_layer<timing>");
+  return DISTR_OK;
+}
+
+// the counters a finished render left in its workspace (Consts), read back once the stream has drained; V = the render's layout
+static int read_consts(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws, hipStream_t s, View& V, const Consts** C) {
+  make_view(*cfg, const_cast<void*>(ws), V, ctx->save_masks);
+  static thread_local std::vector<char> hostbuf;
+  hostbuf.resize(sizeof(Consts));
+  HIP_TRY(hipMemcpyAsync(hostbuf.data(), V.C, sizeof(Consts), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *C = (const Consts*)hostbuf.data();
   return DISTR_OK;
 }
 
@@ -1362,13 +1359,8 @@ int distr_get_render_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const vo
   if (out->struct_size != sizeof(distr_render_stats))   // never write past what the caller allocated
     return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_render_stats.struct_size is %u, expected %zu (set it before the call)", out->struct_size, sizeof(distr_render_stats));
   View V;
-  make_view(*cfg, const_cast<void*>(ws), V, ctx->save_masks);
-  hipStream_t s = (hipStream_t)stream;
-  static thread_local std::vector<char> hostbuf;
-  hostbuf.resize(sizeof(Consts));
-  HIP_TRY(hipMemcpyAsync(hostbuf.data(), V.C, sizeof(Consts), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const Consts* C = (const Consts*)hostbuf.data();
+  const Consts* C;
+  if ((rc = read_consts(ctx, cfg, ws, (hipStream_t)stream, V, &C))) return rc;
   memset(out, 0, sizeof(*out));
   out->struct_size = (uint32_t)sizeof(*out);
   out->num_in_sphere = C->cnt_level[0];
@@ -1429,13 +1421,8 @@ int distr_get_live_counts(distr_ctx* ctx, const distr_render_cfg* cfg, const voi
   int rc = check_cfg(ctx, cfg);
   if (rc) return rc;
   View V;
-  make_view(*cfg, const_cast<void*>(ws), V, ctx->save_masks);
-  hipStream_t s = (hipStream_t)stream;
-  static thread_local std::vector<char> hostbuf;
-  hostbuf.resize(sizeof(Consts));
-  HIP_TRY(hipMemcpyAsync(hostbuf.data(), V.C, sizeof(Consts), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const Consts* C = (const Consts*)hostbuf.data();
+  const Consts* C;
+  if ((rc = read_consts(ctx, cfg, ws, (hipStream_t)stream, V, &C))) return rc;
   int k = 0;
   for (int l = V.nlev - 1; l >= 1; --l)
     for (int st = 0; st < V.lv[l].steps; ++st) { if (k < cap) out[k] = C->cnt_level[l]; ++k; }

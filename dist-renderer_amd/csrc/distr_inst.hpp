@@ -1,66 +1,78 @@
-// distr_inst.hpp -- the big template kernels as explicit instantiations, one GROUP per translation unit, so that libdistr.so builds in
-// parallel (distr.binding.build_library compiles distr_api.hip and the distr_inst_<group>.hip files side by side and links them: ~1.5 min
-// instead of ~4.5 on 8 cores). distr_api.hip (DISTR_INST_GROUP undefined) sees every instantiation as `extern template`: it launches the
-// kernels, the group's translation unit holds their code. A kernel missing from the lists below still works -- distr_api.hip then
-// instantiates it itself, only slower to build.
+// distr_inst.hpp -- THE list of variants of the big template kernels (k_step, k_tail, k_march, k_march16, k_bwd): one line per
+// instantiation, with its template arguments, in the DISTR_GROUP_<n> list of the translation unit that holds its code (libdistr.so builds
+// those units in parallel: distr.binding.build_library compiles distr_api.hip and distr_inst.hip once per group side by side and links
+// them, ~1.5 min instead of ~4.5 on 8 cores). Two things are generated from the lists, and nothing else names a variant:
+//   * the declarations at the end: `template` for the group a unit builds (DISTR_INST_GROUP), `extern template` for all of them in
+//     distr_api.hip, which launches the kernels and holds none of their code;
+//   * the launchers of distr_api.hip (launch_step ... launch_bwd): run-time values to a listed instantiation, anything else refused.
+// So a variant exists exactly when it has a line here; tests/test_host_logic.py checks on a built tree that distr_api.hip's device code
+// defines none of these kernels.
 #pragma once
 #include "distr_kernels.hpp"
 
 namespace distr {
 
-#ifdef DISTR_INST_GROUP
-#define DISTR_INST_DEF template
-#else
-#define DISTR_INST_DEF extern template
-#endif
+// Every list takes one macro per kernel family and calls it once per variant, in the order the unit emits them:
+//   STEP(KEEP, ARITH)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE)
+// KEEP = save the ReLU masks, RB = 32-ray blocks of a tile, ARITH = DISTR_ARITH_* (0 f32, 1 bf16x6, 2 f16x3), WIDE = the layout for
+// code lengths below 256.
+
+// the full-resolution step of the exact-f32 march (the headline kernel)
+#define DISTR_GROUP_1(STEP, TAIL, MARCH, MARCH16, BWD) \
+  STEP(true, 0) STEP(false, 0)
+// the persistent tail launch
+#define DISTR_GROUP_2(STEP, TAIL, MARCH, MARCH16, BWD) \
+  TAIL(true) TAIL(false)
+// exact-f32 march tiles: coarse levels, 'trivial', point lists; 16-ray / cluster tiles
+#define DISTR_GROUP_3(STEP, TAIL, MARCH, MARCH16, BWD) \
+  MARCH(MODE_EVAL, 2, false, 0, false) \
+  MARCH(MODE_COARSE, 1, true, 0, false) MARCH(MODE_COARSE, 1, false, 0, false) MARCH(MODE_COARSE, 2, true, 0, false) MARCH(MODE_COARSE, 2, false, 0, false) \
+  MARCH(MODE_FINE, 2, true, 0, false) MARCH(MODE_FINE, 2, false, 0, false) \
+  MARCH16(MODE_EVAL, false) MARCH16(MODE_COARSE, true) MARCH16(MODE_COARSE, false)
+// the step kernel in the two opt-in arithmetics
+#define DISTR_GROUP_4(STEP, TAIL, MARCH, MARCH16, BWD) \
+  STEP(true, 1) STEP(false, 1) STEP(true, 2) STEP(false, 2)
+// march tiles in the two opt-in arithmetics
+#define DISTR_GROUP_5(STEP, TAIL, MARCH, MARCH16, BWD) \
+  MARCH(MODE_COARSE, 1, true, 1, false) MARCH(MODE_COARSE, 1, false, 1, false) MARCH(MODE_COARSE, 2, true, 1, false) MARCH(MODE_COARSE, 2, false, 1, false) \
+  MARCH(MODE_FINE, 2, true, 1, false) MARCH(MODE_FINE, 2, false, 1, false) \
+  MARCH(MODE_COARSE, 1, true, 2, false) MARCH(MODE_COARSE, 1, false, 2, false) MARCH(MODE_COARSE, 2, true, 2, false) MARCH(MODE_COARSE, 2, false, 2, false) \
+  MARCH(MODE_FINE, 2, true, 2, false) MARCH(MODE_FINE, 2, false, 2, false)
+// backward kernels
+#define DISTR_GROUP_6(STEP, TAIL, MARCH, MARCH16, BWD) \
+  BWD(BWD_FULL, 2, 0, false) BWD(BWD_POINTGRAD, 2, 0, false) \
+  BWD(BWD_SAVED, 1, 0, false) BWD(BWD_SAVED, 1, 1, false) BWD(BWD_SAVED, 1, 2, false) \
+  BWD(BWD_SAVED, 2, 0, false) BWD(BWD_SAVED, 2, 1, false) BWD(BWD_SAVED, 2, 2, false)
+// the wide layout (code length < 256): 64-ray march tiles; 64- and 32-sample backward tiles
+#define DISTR_GROUP_7(STEP, TAIL, MARCH, MARCH16, BWD) \
+  MARCH(MODE_EVAL, 2, false, 0, true) MARCH(MODE_COARSE, 2, true, 0, true) MARCH(MODE_COARSE, 2, false, 0, true) \
+  MARCH(MODE_FINE, 2, true, 0, true) MARCH(MODE_FINE, 2, false, 0, true) \
+  BWD(BWD_FULL, 2, 0, true) BWD(BWD_POINTGRAD, 2, 0, true) BWD(BWD_SAVED, 2, 0, true) BWD(BWD_SAVED, 1, 0, true)
+
+constexpr int DISTR_NUM_INST_GROUPS = 7;
+
+#define DISTR_ALL_GROUPS(...) \
+  DISTR_GROUP_1(__VA_ARGS__) DISTR_GROUP_2(__VA_ARGS__) DISTR_GROUP_3(__VA_ARGS__) DISTR_GROUP_4(__VA_ARGS__) DISTR_GROUP_5(__VA_ARGS__) \
+  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__)
+#define DISTR_NO_VARIANT(...)      // for the families a use of the lists does not ask for
 
 // in a group's translation unit only that group is instantiated; the launching unit declares all of them extern
-#if defined(DISTR_INST_GROUP)
-#define DISTR_GROUP_ON(g) (DISTR_INST_GROUP == (g))
+#ifdef DISTR_INST_GROUP
+#define DISTR_INST_DEF template
+#define DISTR_INST_CAT_(a, b) a##b
+#define DISTR_INST_CAT(a, b) DISTR_INST_CAT_(a, b)
+#define DISTR_INST_LIST DISTR_INST_CAT(DISTR_GROUP_, DISTR_INST_GROUP)
 #else
-#define DISTR_GROUP_ON(g) 1
+#define DISTR_INST_DEF extern template
+#define DISTR_INST_LIST DISTR_ALL_GROUPS
 #endif
 
 #define DISTR_K_STEP(K, AR) DISTR_INST_DEF __global__ void k_step<K, AR>(MarchArgs, DecoderDev, DecoderDev16, StepGrid);
 #define DISTR_K_TAIL(K) DISTR_INST_DEF __global__ void k_tail<K>(MarchArgs, DecoderDev, DecoderDev16);
-#define DISTR_K_MARCH(M, RB, K, AR) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR>(MarchArgs, DecoderDev);
+#define DISTR_K_MARCH(M, RB, K, AR, W) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR, W>(MarchArgs, DecoderDev);
 #define DISTR_K_MARCH16(M, K) DISTR_INST_DEF __global__ void k_march16<M, K>(MarchArgs, DecoderDev, DecoderDev16);
-#define DISTR_K_BWD(M, RB, AR) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR>(BwdArgs, DecoderDev);
-#define DISTR_K_MARCH_W(M, K) DISTR_INST_DEF __global__ void k_march<M, 2, K, 0, true>(MarchArgs, DecoderDev);
-#define DISTR_K_BWD_W(M, RB) DISTR_INST_DEF __global__ void k_bwd<M, RB, 0, true>(BwdArgs, DecoderDev);
+#define DISTR_K_BWD(M, RB, AR, W) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR, W>(BwdArgs, DecoderDev);
 
-#if DISTR_GROUP_ON(1)      // the full-resolution step of the exact-f32 march (the headline kernel)
-DISTR_K_STEP(true, 0) DISTR_K_STEP(false, 0)
-#endif
-#if DISTR_GROUP_ON(2)      // the persistent tail launch
-DISTR_K_TAIL(true) DISTR_K_TAIL(false)
-#endif
-#if DISTR_GROUP_ON(3)      // exact-f32 march tiles: coarse levels, 'trivial', point lists; 16-ray / cluster tiles
-DISTR_K_MARCH(MODE_EVAL, 2, false, 0)
-DISTR_K_MARCH(MODE_COARSE, 1, true, 0) DISTR_K_MARCH(MODE_COARSE, 1, false, 0) DISTR_K_MARCH(MODE_COARSE, 2, true, 0) DISTR_K_MARCH(MODE_COARSE, 2, false, 0)
-DISTR_K_MARCH(MODE_FINE, 2, true, 0) DISTR_K_MARCH(MODE_FINE, 2, false, 0)
-DISTR_K_MARCH16(MODE_EVAL, false) DISTR_K_MARCH16(MODE_COARSE, true) DISTR_K_MARCH16(MODE_COARSE, false)
-#endif
-#if DISTR_GROUP_ON(4)      // the step kernel in the two opt-in arithmetics
-DISTR_K_STEP(true, 1) DISTR_K_STEP(false, 1) DISTR_K_STEP(true, 2) DISTR_K_STEP(false, 2)
-#endif
-#if DISTR_GROUP_ON(5)      // march tiles in the two opt-in arithmetics
-DISTR_K_MARCH(MODE_COARSE, 1, true, 1) DISTR_K_MARCH(MODE_COARSE, 1, false, 1) DISTR_K_MARCH(MODE_COARSE, 2, true, 1) DISTR_K_MARCH(MODE_COARSE, 2, false, 1)
-DISTR_K_MARCH(MODE_FINE, 2, true, 1) DISTR_K_MARCH(MODE_FINE, 2, false, 1)
-DISTR_K_MARCH(MODE_COARSE, 1, true, 2) DISTR_K_MARCH(MODE_COARSE, 1, false, 2) DISTR_K_MARCH(MODE_COARSE, 2, true, 2) DISTR_K_MARCH(MODE_COARSE, 2, false, 2)
-DISTR_K_MARCH(MODE_FINE, 2, true, 2) DISTR_K_MARCH(MODE_FINE, 2, false, 2)
-#endif
-#if DISTR_GROUP_ON(6)      // backward kernels
-DISTR_K_BWD(BWD_FULL, 2, 0) DISTR_K_BWD(BWD_POINTGRAD, 2, 0)
-DISTR_K_BWD(BWD_SAVED, 1, 0) DISTR_K_BWD(BWD_SAVED, 1, 1) DISTR_K_BWD(BWD_SAVED, 1, 2)
-DISTR_K_BWD(BWD_SAVED, 2, 0) DISTR_K_BWD(BWD_SAVED, 2, 1) DISTR_K_BWD(BWD_SAVED, 2, 2)
-#endif
-#if DISTR_GROUP_ON(7)      // the wide layout (code length < 256): 64-ray march tiles; 64- and 32-sample backward tiles
-DISTR_K_MARCH_W(MODE_EVAL, false) DISTR_K_MARCH_W(MODE_COARSE, true) DISTR_K_MARCH_W(MODE_COARSE, false)
-DISTR_K_MARCH_W(MODE_FINE, true) DISTR_K_MARCH_W(MODE_FINE, false)
-DISTR_K_BWD_W(BWD_FULL, 2) DISTR_K_BWD_W(BWD_POINTGRAD, 2) DISTR_K_BWD_W(BWD_SAVED, 2) DISTR_K_BWD_W(BWD_SAVED, 1)
-#endif
-
-constexpr int DISTR_NUM_INST_GROUPS = 7;
+DISTR_INST_LIST(DISTR_K_STEP, DISTR_K_TAIL, DISTR_K_MARCH, DISTR_K_MARCH16, DISTR_K_BWD)
 
 }  // namespace distr

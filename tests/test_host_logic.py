@@ -821,7 +821,8 @@ def test_build_is_split_into_parallel_units_and_checked():
     assert labels == ['api'] + ['inst%d' % g for g in range(1, binding.INST_GROUPS + 1)]
     hdr = open(os.path.join(binding.CSRC, 'distr_inst.hpp')).read()
     assert int(re.search(r'DISTR_NUM_INST_GROUPS = (\d+)', hdr).group(1)) == binding.INST_GROUPS
-    assert sorted(set(int(g) for g in re.findall(r'DISTR_GROUP_ON\((\d+)\)', hdr))) == list(range(1, binding.INST_GROUPS + 1))
+    assert sorted(set(int(g) for g in re.findall(r'#define DISTR_GROUP_(\d+)\(', hdr))) == list(range(1, binding.INST_GROUPS + 1))
+    assert all('DISTR_GROUP_%d(__VA_ARGS__)' % g in hdr for g in range(1, binding.INST_GROUPS + 1))      # ... and every group is used
     for label, cmd, out in steps:
         assert '--offload-arch=gfx950' in cmd and '-save-temps=obj' in cmd and '-ffp-contract=off' in cmd
         assert ('-DDISTR_INST_GROUP=%s' % label[4:] in cmd) == label.startswith('inst')
@@ -834,6 +835,17 @@ def test_build_is_split_into_parallel_units_and_checked():
     if os.path.exists(asm) and os.path.exists(binding.LIB_PATH) and os.path.getmtime(binding.LIB_PATH) >= os.path.getmtime(asm):
         res = binding.check_generated_code()          # (the build of this checkout, if it is there: raises on a finding)
         assert any('k_step' in n for n in res)
+        # every variant distr_api.hip can launch is a line of distr_inst.hpp's lists, built by a group unit: the launching unit's device
+        # code (the one check_generated_code() does not scan) defines none of the big template kernels ...
+
+        def kernels(unit, src):
+            with open(os.path.join(binding.CSRC, '_obj', unit, src + '-hip-amdgcn-amd-amdhsa-gfx950.s')) as f:
+                return set(re.findall(r'^(_ZN5distr\d+k_\w+):', f.read(), re.M))
+        api = kernels('api', 'distr_api')
+        assert api and not [k for k in api if re.match(r'_ZN5distr\d+k_(march16|march|step|tail|bwd)I', k)]
+        # ... and every cluster kernel is defined in the unit CLUSTER_KERNELS sends the scanners to
+        for unit, sym in binding.CLUSTER_KERNELS:
+            assert [k for k in kernels(unit, 'distr_inst') if re.match(r'_ZN5distr\d+' + sym, k)], (unit, sym)
 
 
 def test_bench_live_traffic_failure_paths(monkeypatch, tmp_path):
