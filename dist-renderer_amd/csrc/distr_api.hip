@@ -17,6 +17,7 @@
 #include "distr_losses.hpp"
 #include "distr_mesh.hpp"
 #include "distr_mlp_b6.hpp"
+#include "distr_samples.hpp"
 
 using namespace distr;
 
@@ -1209,12 +1210,10 @@ int distr_render_normal_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32
 
 size_t distr_mlp_workspace_bytes(int64_t n) { (void)n; return 2 * HID * sizeof(float) + 256; }
 
-int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
-                   size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
+// decode_sdf on a point list (distr_mlp_eval, and the list of distr_depth_samples_forward); the caller holds the EntryGuard
+static int mlp_eval_impl(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
+                         size_t ws_bytes, hipStream_t s) {
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  hipStream_t s = (hipStream_t)stream;
   float* c0c4;
   int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
   if (rc || n == 0) return rc;
@@ -1230,6 +1229,13 @@ int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_
   else rc = launch_march(ctx, "k_march<eval>", MODE_EVAL, 2, false, 0, wide, (unsigned)((n + 63) / 64), s, A);
   timer.end();
   return rc;
+}
+
+int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
+                   size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  return mlp_eval_impl(ctx, latent, xyz, n, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // decode_sdf in one of the split arithmetics (h3: f16x3, else bf16x6)
@@ -1284,12 +1290,10 @@ size_t distr_mlp_backward_workspace_bytes(int64_t n) {
   return distr_mlp_workspace_bytes(n) + tiles * PSTRIDE * sizeof(float) + 256;
 }
 
-int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
-                       float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
+// backward of decode_sdf on a point list (distr_mlp_backward, distr_depth_samples_backward); the caller holds the EntryGuard
+static int mlp_backward_impl(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
+                             float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  hipStream_t s = (hipStream_t)stream;
   float* c0c4;
   int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !g_sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_backward_workspace_bytes(n), s, &c0c4);
   if (rc) return rc;
@@ -1308,6 +1312,13 @@ int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, in
     LAUNCH_CHECK("k_points_latent_grad");
   }
   return DISTR_OK;
+}
+
+int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
+                       float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  return mlp_backward_impl(ctx, latent, xyz, n, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, int layer, float* out, void* ws,
@@ -1730,6 +1741,188 @@ int distr_nearest_sqdist(distr_ctx* ctx, const float* a, int64_t na, const float
     LAUNCH_CHECK("k_dist_sums");
     hipLaunchKernelGGL(mesh::k_mesh_top_scan<mesh::D2>, dim3(1), dim3(mesh::MB), 0, s, (const mesh::D2*)btot, nblk, boff, (mesh::D2*)sums);
     LAUNCH_CHECK("k_mesh_top_scan");
+  }
+  return DISTR_OK;
+}
+
+}  // extern "C"
+
+// ---- depth maps back-projected into SDF samples (include/distr_samples.h, kernels: distr_samples.hpp)
+namespace {
+
+struct SampPlan {
+  samples::Geo G;
+  samples::Views VW;
+  int nviews;
+  int64_t ntot, nmax;        // valid pixels of all views, of the largest view
+  int nblk_px;               // blocks of MTILE pixels per view (count / compact)
+  int nblk_cam;              // blocks of MTILE valid pixels of the largest view (camera gradient)
+};
+
+int samp_cfg(distr_ctx* ctx, const distr_samples_cfg* c, int32_t nviews, SampPlan& p) {
+  if (!c) return fail(ctx, DISTR_ERR_INVALID_ARG, "null samples cfg");
+  if (c->struct_size != sizeof(distr_samples_cfg))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_samples_cfg.struct_size %u: this library expects %zu (set it with DISTR_INIT)", c->struct_size, sizeof(distr_samples_cfg));
+  if (c->H < 1 || c->W < 1 || (int64_t)c->H * c->W > ((int64_t)1 << 26)) return fail(ctx, DISTR_ERR_INVALID_ARG, "image size %d x %d", c->H, c->W);
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d: 1..%d", nviews, DISTR_MAX_VIEWS);
+  if (c->mode != DISTR_SAMPLES_SURFACE && c->mode != DISTR_SAMPLES_FREESPACE) return fail(ctx, DISTR_ERR_INVALID_ARG, "samples mode %d", c->mode);
+  if (c->mode == DISTR_SAMPLES_FREESPACE && (c->number < 1 || c->number > DISTR_SAMPLES_MAX_NUMBER))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "free-space samples: number %d (1..%d)", c->number, DISTR_SAMPLES_MAX_NUMBER);
+  memset(&p, 0, sizeof(p));
+  p.G.H = c->H; p.G.W = c->W; p.G.P = c->H * c->W;
+  memcpy(p.G.Ki, c->K_inv, sizeof(p.G.Ki));
+  memcpy(p.G.M, c->M, sizeof(p.G.M));
+  p.G.mode = c->mode;
+  p.G.m = c->mode == DISTR_SAMPLES_SURFACE ? 2 : c->number;
+  p.nviews = nviews;
+  p.nblk_px = (p.G.P + samples::MTILE - 1) / samples::MTILE;
+  return DISTR_OK;
+}
+
+int samp_counts(distr_ctx* ctx, const int64_t* counts, SampPlan& p) {
+  if (!counts) return fail(ctx, DISTR_ERR_INVALID_ARG, "null counts (host array of nviews, from distr_depth_samples_count)");
+  for (int v = 0; v < p.nviews; ++v) {
+    if (counts[v] < 0 || counts[v] > p.G.P) return fail(ctx, DISTR_ERR_INVALID_ARG, "counts[%d] = %lld: outside 0..H*W", v, (long long)counts[v]);
+    p.VW.n[v] = (int32_t)counts[v];
+    p.VW.off[v] = (int32_t)p.ntot;
+    p.ntot += counts[v];
+    p.nmax = std::max(p.nmax, (int64_t)counts[v]);
+  }
+  if (p.ntot * p.G.m > ((int64_t)1 << 29)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "point list of %lld entries: too long", (long long)(p.ntot * p.G.m));
+  p.nblk_cam = (int)std::max<int64_t>(1, (p.nmax + samples::MTILE - 1) / samples::MTILE);
+  return DISTR_OK;
+}
+
+struct SampCountWs { int *btot, *boff, *totals; size_t bytes; };
+SampCountWs samp_count_ws(void* base, const SampPlan& p) {
+  WsCarve c(base);
+  SampCountWs w;
+  w.btot = c.take<int>((size_t)p.nviews * p.nblk_px);
+  w.boff = c.take<int>((size_t)p.nviews * p.nblk_px);
+  w.totals = c.take<int>(DISTR_MAX_VIEWS);
+  w.bytes = c.bytes();
+  return w;
+}
+
+struct SampBwdWs { float *g_xyz, *part; void* mlp; size_t mlp_bytes, bytes; };
+SampBwdWs samp_bwd_ws(void* base, const SampPlan& p) {
+  WsCarve c(base);
+  SampBwdWs w;
+  w.g_xyz = c.take<float>((size_t)(3 * p.ntot * p.G.m));
+  w.part = c.take<float>((size_t)p.nviews * p.nblk_cam * 12);
+  w.mlp_bytes = distr_mlp_backward_workspace_bytes(p.nmax * p.G.m);
+  w.mlp = c.take<char>(w.mlp_bytes);
+  w.bytes = c.bytes();
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int distr_depth_samples_workspace_bytes(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const int64_t* counts,
+                                        size_t* count_bytes, size_t* forward_bytes, size_t* backward_bytes) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  SampPlan p;
+  if (int rc = samp_cfg(ctx, cfg, nviews, p)) return rc;
+  if (count_bytes) *count_bytes = samp_count_ws(nullptr, p).bytes;
+  if (!counts) {
+    if (forward_bytes || backward_bytes) return fail(ctx, DISTR_ERR_INVALID_ARG, "forward / backward workspace sizes need the counts");
+    return DISTR_OK;
+  }
+  if (int rc = samp_counts(ctx, counts, p)) return rc;
+  if (forward_bytes) *forward_bytes = distr_mlp_workspace_bytes(p.ntot * p.G.m);
+  if (backward_bytes) *backward_bytes = samp_bwd_ws(nullptr, p).bytes;
+  return DISTR_OK;
+}
+
+int distr_depth_samples_count(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const float* depth, int32_t* index,
+                              int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  SampPlan p;
+  if (int rc = samp_cfg(ctx, cfg, nviews, p)) return rc;
+  if (!depth || !index || !counts || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null pointer");
+  if (ws_bytes < samp_count_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples count workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const SampCountWs w = samp_count_ws(ws, p);
+  const dim3 grid((unsigned)p.nblk_px, (unsigned)nviews);
+  hipLaunchKernelGGL(samples::k_samp_count, grid, dim3(samples::MB), 0, s, depth, p.G.P, p.nblk_px, w.btot);
+  LAUNCH_CHECK("k_samp_count");
+  hipLaunchKernelGGL(samples::k_samp_top_scan, dim3((unsigned)nviews), dim3(samples::MB), 0, s, (const int*)w.btot, p.nblk_px, w.boff, w.totals);
+  LAUNCH_CHECK("k_samp_top_scan");
+  hipLaunchKernelGGL(samples::k_samp_compact, grid, dim3(samples::MB), 0, s, depth, p.G.P, p.nblk_px, (const int*)w.boff, index);
+  LAUNCH_CHECK("k_samp_compact");
+  int tot[DISTR_MAX_VIEWS];
+  HIP_TRY(hipMemcpyAsync(tot, w.totals, sizeof(int) * nviews, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int v = 0; v < nviews; ++v) counts[v] = tot[v];
+  return DISTR_OK;
+}
+
+int distr_depth_samples_forward(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const int64_t* counts, const int32_t* index,
+                                const float* latent, int64_t latent_stride, const float* RT, const float* depth, const float* normal,
+                                const float* draws, float* xyz, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  SampPlan p;
+  if (int rc = samp_cfg(ctx, cfg, nviews, p)) return rc;
+  if (int rc = samp_counts(ctx, counts, p)) return rc;
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->D.nlat);
+  if (!index || !latent || !RT || !depth || !draws || !ws || (p.G.mode == DISTR_SAMPLES_SURFACE && !normal) || (p.ntot > 0 && (!xyz || !out)))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  const int64_t L = p.ntot * p.G.m;
+  if (ws_bytes < distr_mlp_workspace_bytes(L)) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples forward workspace too small");
+  if (L == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((p.nmax + samples::MB - 1) / samples::MB), (unsigned)nviews);
+  hipLaunchKernelGGL(samples::k_samp_points, grid, dim3(samples::MB), 0, s, p.G, p.VW, index, RT, depth, normal, draws, xyz);
+  LAUNCH_CHECK("k_samp_points");
+  if (latent_stride == 0 || nviews == 1) {
+    if (int rc = mlp_eval_impl(ctx, latent, xyz, L, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
+  } else {           // a code per view: the evaluator takes one code per launch sequence (stream order keeps the shared workspace safe)
+    for (int v = 0; v < nviews; ++v) {
+      const int64_t o = (int64_t)p.G.m * p.VW.off[v], n = (int64_t)p.G.m * p.VW.n[v];
+      if (int rc = mlp_eval_impl(ctx, latent + v * latent_stride, xyz + 3 * o, n, cfg->clamp_dist, out + o, ws, ws_bytes, s)) return rc;
+    }
+  }
+  if (p.G.mode == DISTR_SAMPLES_SURFACE) {
+    hipLaunchKernelGGL(samples::k_samp_epilogue, grid, dim3(samples::MB), 0, s, p.VW, draws, out);
+    LAUNCH_CHECK("k_samp_epilogue");
+  }
+  return DISTR_OK;
+}
+
+int distr_depth_samples_backward(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const int64_t* counts, const int32_t* index,
+                                 const float* latent, int64_t latent_stride, const float* RT, const float* depth, const float* draws,
+                                 const float* xyz, const float* g_out, float* g_latent, float* g_RT, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  SampPlan p;
+  if (int rc = samp_cfg(ctx, cfg, nviews, p)) return rc;
+  if (int rc = samp_counts(ctx, counts, p)) return rc;
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->D.nlat);
+  if (!index || !latent || !RT || !depth || !draws || !ws || (p.ntot > 0 && (!xyz || !g_out))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < samp_bwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples backward workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const SampBwdWs w = samp_bwd_ws(ws, p);
+  // the point-list backward view by view: every view keeps the tiles and the reduction order of its stand-alone call
+  for (int v = 0; v < nviews; ++v) {
+    const int64_t o = (int64_t)p.G.m * p.VW.off[v], n = (int64_t)p.G.m * p.VW.n[v];
+    if (int rc = mlp_backward_impl(ctx, latent + v * latent_stride, xyz + 3 * o, n, g_out + o, cfg->clamp_dist, g_RT ? w.g_xyz + 3 * o : nullptr,
+                                   g_latent ? g_latent + (int64_t)v * ctx->D.nlat : nullptr, w.mlp, w.mlp_bytes, s))
+      return rc;
+  }
+  if (g_RT) {
+    hipLaunchKernelGGL(samples::k_samp_cam_bwd, dim3((unsigned)p.nblk_cam, (unsigned)nviews), dim3(samples::MB), 0, s, p.G, p.VW, index, RT, depth,
+                       draws, (const float*)w.g_xyz, p.nblk_cam, w.part);
+    LAUNCH_CHECK("k_samp_cam_bwd");
+    hipLaunchKernelGGL(samples::k_samp_cam_fin, dim3((unsigned)nviews), dim3(samples::MB), 0, s, p.VW, RT, (const float*)w.part, p.nblk_cam, g_RT);
+    LAUNCH_CHECK("k_samp_cam_fin");
   }
   return DISTR_OK;
 }

@@ -28,6 +28,11 @@ EXPORTS = ['distr_version', 'distr_abi_version', 'distr_create_abi', 'distr_dest
 # shape evaluation (include/distr_mesh.h, included by distr.h): marching cubes, surface sampling, nearest-point distances
 MESH_EXPORTS = ['distr_mc_workspace_bytes', 'distr_mc_count', 'distr_mc_emit', 'distr_sample_workspace_bytes', 'distr_sample_surface',
                 'distr_nearest_workspace_bytes', 'distr_nearest_sqdist']
+# depth maps back-projected into SDF samples (include/distr_samples.h, included by distr.h): SDFRenderer_deepsdf
+SAMPLES_EXPORTS = ['distr_depth_samples_workspace_bytes', 'distr_depth_samples_count', 'distr_depth_samples_forward',
+                   'distr_depth_samples_backward']
+SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
+SAMPLES_MAX_NUMBER = 64                             # DISTR_SAMPLES_MAX_NUMBER
 
 ABI_VERSION = 6                                   # DISTR_ABI_VERSION of include/distr.h this mirror was written against
 MAX_VIEWS = 64                                    # DISTR_MAX_VIEWS
@@ -88,6 +93,22 @@ class WarpCfg(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K', C.c_float * 9), ('K_inv', C.c_float * 9), ('thres_depth', C.c_float)]
 
 
+class SamplesCfg(_Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K_inv', C.c_float * 9), ('M', C.c_float * 9),
+                ('clamp_dist', C.c_float), ('mode', C.c_int32), ('number', C.c_int32)]
+
+
+def make_samples_cfg(img_hw, intrinsic, transform_matrix, clamp_dist, mode, number=1):
+    """distr_samples_cfg of one get_samples / get_freespace_samples call (include/distr_samples.h); clamp_dist None = no clamp."""
+    cfg = SamplesCfg()
+    cfg.H, cfg.W = int(img_hw[0]), int(img_hw[1])
+    cfg.K_inv = (C.c_float * 9)(*np.linalg.inv(np.asarray(intrinsic, dtype=np.float64)).astype(np.float32).reshape(-1))
+    cfg.M = (C.c_float * 9)(*np.asarray(transform_matrix, dtype=np.float32).reshape(-1))
+    cfg.clamp_dist = -1.0 if clamp_dist is None else float(clamp_dist)
+    cfg.mode, cfg.number = SAMPLES_MODES[mode], int(number)
+    return cfg
+
+
 def make_warp_cfg(img_hw, intrinsic, thres_depth):
     cfg = WarpCfg()
     cfg.H, cfg.W = int(img_hw[0]), int(img_hw[1])
@@ -105,8 +126,8 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h')                    # include/: the C ABI
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp')
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h')                    # include/: the C ABI
 INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -319,6 +340,11 @@ def lib():
             L.distr_nearest_workspace_bytes.argtypes = [i64]
             L.distr_nearest_workspace_bytes.restype = C.c_size_t
             L.distr_nearest_sqdist.argtypes = [vp, fp, i64, fp, i64, fp, vp, vp, C.c_size_t, vp]
+            szp, scfg = C.POINTER(C.c_size_t), C.POINTER(SamplesCfg)
+            L.distr_depth_samples_workspace_bytes.argtypes = [vp, scfg, i32, i64p, szp, szp, szp]
+            L.distr_depth_samples_count.argtypes = [vp, scfg, i32, fp, vp, i64p, vp, C.c_size_t, vp]
+            L.distr_depth_samples_forward.argtypes = [vp, scfg, i32, i64p, vp, fp, i64, fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
+            L.distr_depth_samples_backward.argtypes = [vp, scfg, i32, i64p, vp, fp, i64, fp, fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
             _lib = L
     return _lib
 

@@ -503,6 +503,104 @@ def mlp_eval_autograd(engine, latent, points, clamp_dist=None):
     return DecodeSdfFunction.apply(latent, points, engine, clamp_dist)
 
 
+def depth_samples_count(engine, cfg, depth):
+    """Valid pixels (0 < depth < 1e5) of V depth maps (V, H, W), compacted on the GPU in row-major order (distr_depth_samples_count: a
+    fixed-order scan, one host read). Returns (depth as the f32 device tensor the kernels read, index (V, H*W) int32 whose first
+    counts[v] entries of row v are the valid pixels of view v, counts: list of V ints)."""
+    dev = engine.device
+    d = _f32c(depth, dev).reshape(-1, cfg.H * cfg.W)
+    V = d.shape[0]
+    L, p = engine.ctx.L, binding.ptr
+    nb = C.c_size_t()
+    engine.ctx.check(L.distr_depth_samples_workspace_bytes(engine.ctx.h, C.byref(cfg), V, None, C.byref(nb), None, None))
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    index = torch.empty(V, cfg.H * cfg.W, dtype=torch.int32, device=dev)
+    counts = (C.c_int64 * V)()
+    engine.ctx.check(L.distr_depth_samples_count(engine.ctx.h, C.byref(cfg), V, p(d), p(index), counts, p(ws), ws.numel(), engine.ctx.stream()))
+    return d, index, [int(c) for c in counts]
+
+
+class DepthSamplesFunction(torch.autograd.Function):
+    """SDFRenderer_deepsdf.get_samples / get_freespace_samples (core/sdfrenderer/renderer_deepsdf.py:14-64) of V views as one node:
+    (latent (1,C) shared or (V,C), RT (V,3,4)) -> the list of distr_depth_samples_forward (include/distr_samples.h: per view
+    [pos | neg] or [draw][pixel]). `obs` = (depth, normal or None, draws, index, counts): observations and random draws, no gradient.
+    backward = distr_depth_samples_backward: g_latent (summed over the views of a shared code), g_RT."""
+
+    @staticmethod
+    def forward(ctx, latent, RT, engine, cfg, obs):
+        depth, normal, draws, index, counts = obs
+        dev = engine.device
+        V = len(counts)
+        lat = _code(engine, latent, dev, views=True)
+        if lat.shape[0] not in (1, V):
+            raise ValueError('latent has shape %s; %d views take (1, %d) or (%d, %d)' % (tuple(latent.shape), V, engine.latent_size, V, engine.latent_size))
+        rt = _f32c(RT, dev).reshape(V, 3, 4)
+        m = 2 if cfg.mode == binding.SAMPLES_MODES['surface'] else cfg.number
+        n = m * sum(counts)
+        L, p = engine.ctx.L, binding.ptr
+        cnt = (C.c_int64 * V)(*counts)
+        fb, bb = C.c_size_t(), C.c_size_t()
+        engine.ctx.check(L.distr_depth_samples_workspace_bytes(engine.ctx.h, C.byref(cfg), V, cnt, None, C.byref(fb), C.byref(bb)))
+        xyz = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        ws = torch.empty(fb.value, dtype=torch.uint8, device=dev)
+        stride = 0 if lat.shape[0] == 1 else engine.latent_size
+        engine.ctx.check(L.distr_depth_samples_forward(engine.ctx.h, C.byref(cfg), V, cnt, p(index), p(lat), stride, p(rt), p(depth), p(normal),
+                                                       p(draws), p(xyz), p(out), p(ws), ws.numel(), engine.ctx.stream()))
+        ctx.engine, ctx.cfg, ctx.obs, ctx.cnt, ctx.stride, ctx.bwd_bytes = engine, cfg, obs, cnt, stride, bb.value
+        ctx.shapes = (latent.shape, RT.shape)
+        ctx.need = (latent.requires_grad, RT.requires_grad)
+        ctx.save_for_backward(lat, rt, xyz)
+        ctx.mark_non_differentiable(xyz)
+        return out, xyz
+
+    @staticmethod
+    def backward(ctx, g_out, _g_xyz):
+        engine, cfg = ctx.engine, ctx.cfg
+        depth, normal, draws, index, counts = ctx.obs
+        lat, rt, xyz = ctx.saved_tensors
+        dev = engine.device
+        V = len(counts)
+        g = _f32c(g_out, dev).reshape(-1)
+        g_l = torch.empty(V, engine.latent_size, dtype=torch.float32, device=dev) if ctx.need[0] else None
+        g_rt = torch.empty(V, 3, 4, dtype=torch.float32, device=dev) if ctx.need[1] else None
+        ws = torch.empty(ctx.bwd_bytes, dtype=torch.uint8, device=dev)
+        L, p = engine.ctx.L, binding.ptr
+        engine.ctx.check(L.distr_depth_samples_backward(engine.ctx.h, C.byref(cfg), V, ctx.cnt, p(index), p(lat), ctx.stride, p(rt), p(depth), p(draws),
+                                                        p(xyz), p(g), p(g_l), p(g_rt), p(ws), ws.numel(), engine.ctx.stream()))
+        if g_l is not None:
+            g_l = (g_l.sum(0) if ctx.stride == 0 and V > 1 else g_l).reshape(ctx.shapes[0])
+        return g_l, (None if g_rt is None else g_rt.reshape(ctx.shapes[1])), None, None, None
+
+
+def _samples_list(engine, cfg, latent, RT, obs):
+    out, xyz = DepthSamplesFunction.apply(latent, RT, engine, cfg, obs)
+    counts = obs[4]
+    m = 2 if cfg.mode == binding.SAMPLES_MODES['surface'] else cfg.number
+    return list(torch.split(out, [m * c for c in counts])), xyz
+
+
+def samples_call(engine, cfg, latent, RT, depth, normal, eta_map, index, counts):
+    """get_samples of V views: eta_map = sum(counts) floats (view after view). Returns ([(samples_pos (N_v,), samples_neg (N_v,))
+    per view], the point list (2 sum N, 3) the decoder saw, without gradient)."""
+    dev = engine.device
+    obs = (depth, _f32c(normal, dev).reshape(len(counts), -1), _f32c(eta_map, dev).reshape(-1), index, counts)
+    if obs[2].numel() != sum(counts) or obs[1].shape[1] != 3 * cfg.H * cfg.W:
+        raise ValueError('eta_map needs %d entries (one per valid pixel), normal (%d, %d, %d, 3)' % (sum(counts), len(counts), cfg.H, cfg.W))
+    per_view, xyz = _samples_list(engine, cfg, latent, RT, obs)
+    return [tuple(torch.split(o, [c, c])) for o, c in zip(per_view, counts)], xyz
+
+
+def freespace_call(engine, cfg, latent, RT, depth, ratio, index, counts):
+    """get_freespace_samples of V views: ratio = number * sum(counts) floats (per view [draw][pixel]). Returns ([samples
+    (number * N_v,) per view], the point list)."""
+    dev = engine.device
+    obs = (depth, None, _f32c(ratio, dev).reshape(-1), index, counts)
+    if obs[2].numel() != cfg.number * sum(counts):
+        raise ValueError('ratio needs number * N = %d entries' % (cfg.number * sum(counts)))
+    return _samples_list(engine, cfg, latent, RT, obs)
+
+
 def mlp_grad(engine, latent, points):
     """(sdf (n,), d sdf/d xyz (n,3)) of the unclamped decoder."""
     dev = engine.device

@@ -367,5 +367,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 
 /* shape evaluation after the render path: marching cubes, surface sampling, chamfer distances */
 #include "distr_mesh.h"
+/* depth maps back-projected into SDF samples (SDFRenderer_deepsdf) */
+#include "distr_samples.h"
 
 #endif /* DISTR_H_ */
