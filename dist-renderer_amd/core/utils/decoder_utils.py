@@ -73,6 +73,59 @@ def decode_sdf_gradient(decoder, latent_vector, points, clamp_dist=0.1, MAX_POIN
     return g
 
 
+def _batch_layout(Cn, latent_vectors, points, counts):
+    """(flat points (sum N, 3), counts as a list, output shape without the last axis) of a decode_sdf_batch / decode_sdf_gradient_batch
+    call for a decoder of code length Cn; ValueError for shapes that do not fit. Pure shape logic: runs without a GPU."""
+    if latent_vectors.dim() != 2 or latent_vectors.shape[1] != Cn or latent_vectors.shape[0] < 1:
+        raise ValueError('latent_vectors has shape %s; this decoder takes (S, C) = (S, %d): one code per segment' % (tuple(latent_vectors.shape), Cn))
+    S = latent_vectors.shape[0]
+    if counts is None:
+        if points.dim() != 3 or points.shape[0] != S or points.shape[2] != 3:
+            raise ValueError('points has shape %s; without counts %d codes take (S, N, 3) = (%d, N, 3)' % (tuple(points.shape), S, S))
+        return points.reshape(-1, 3), [points.shape[1]] * S, (S, points.shape[1])
+    counts = [int(c) for c in (counts.tolist() if torch.is_tensor(counts) else counts)]
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError('points has shape %s; with counts it is the flat list (sum N, 3)' % (tuple(points.shape),))
+    if len(counts) != S or min(counts) < 0:
+        raise ValueError('counts %r: %d codes take %d segment sizes >= 0' % (counts, S, S))
+    if sum(counts) != points.shape[0]:
+        raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), points.shape[0]))
+    return points, counts, (points.shape[0],)
+
+
+def _batch_args(decoder, latent_vectors, points, counts):
+    if latent_vectors is None:
+        raise NotImplementedError('latent_vectors=None (a code in every input row, decoder_utils.py:58-59) is not supported')
+    eng = _engine(decoder, points)
+    return (eng,) + _batch_layout(eng.latent_size, latent_vectors, points, counts)
+
+
+def decode_sdf_batch(decoder, latent_vectors, points, counts=None, clamp_dist=0.1, no_grad=False):
+    """decode_sdf for S shape codes in one launch sequence (not in the reference, which loops): latent_vectors (S, C); points either
+    (S, N, 3) -> (S, N, 1), or the flat list (sum N, 3) with `counts` (a sequence or a CPU int tensor of S segment sizes >= 0, segment
+    s = the next counts[s] rows) -> (sum N, 1). Every segment's slice is byte for byte decode_sdf(decoder, latent_vectors[s:s+1], its
+    points); so are, unless `no_grad`, its gradients w.r.t. the points and row s of the gradient w.r.t. latent_vectors
+    (distr_mlp_eval_multi / distr_mlp_backward_multi; more than 64 segments run in chunks of 64). f32 arithmetic."""
+    eng, x, counts, shape = _batch_args(decoder, latent_vectors, points, counts)
+    if (not no_grad) and torch.is_grad_enabled() and (latent_vectors.requires_grad or points.requires_grad):
+        out = functions.mlp_eval_multi_autograd(eng, latent_vectors, x, counts, clamp_dist)
+    else:
+        out = functions.mlp_eval_multi(eng, latent_vectors, x, counts, clamp_dist)
+    return out.reshape(shape + (1,))
+
+
+def decode_sdf_gradient_batch(decoder, latent_vectors, points, counts=None, clamp_dist=0.1):
+    """decode_sdf_gradient for S shape codes in one launch sequence; arguments as decode_sdf_batch, returns (S, N, 3) or (sum N, 3) with
+    decode_sdf_gradient's value semantics (3 x the gradient, zero where |f| > clamp_dist), detached; byte for byte the single call per
+    segment."""
+    eng, x, counts, shape = _batch_args(decoder, latent_vectors, points, counts)
+    sdf, g = functions.mlp_grad_multi(eng, latent_vectors, x, counts)
+    g = 3.0 * g
+    if clamp_dist is not None:
+        g = g * (sdf.abs() <= clamp_dist).to(g.dtype)[:, None]
+    return g.reshape(shape + (3,))
+
+
 def decode_color(decoder, color_code, shape_code, points, MAX_POINTS=100000, no_grad=False):
     """(n,3) surface points -> (n,3) rgb of the colour decoder (decoder_utils.py:94-112); differentiable w.r.t. the colour code,
     the shape code and the points unless `no_grad` (distr_color_backward). MAX_POINTS chunking is unnecessary (accepted, ignored)."""

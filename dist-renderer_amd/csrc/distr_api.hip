@@ -500,6 +500,19 @@ struct MarchTimer {  // optional hipEvent bracket around the march kernel launch
   }
 };
 
+// workspace carving: every array on a 256-byte boundary, the base aligned up (the byte counts include that slack)
+struct WsCarve {
+  uintptr_t at;
+  size_t used = 0;
+  explicit WsCarve(void* base) : at(((uintptr_t)base + 255) & ~(uintptr_t)255) {}
+  template <typename T> T* take(size_t n) {
+    T* p = (T*)(at + used);
+    used += (n * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+  size_t bytes() const { return used + 256; }
+};
+
 // Prologue of the entry points that run a decoder on a point list: the caller's own argument check (args_ok, with its text), the
 // workspace size, then the constants the tiles read instead of the latent columns of lin0 / lin4 (k_latent_consts), at the 256-byte
 // aligned start of the workspace. An empty list (n == 0) gets the checks only.
@@ -509,7 +522,7 @@ int point_list_prologue(distr_ctx* ctx, const DecoderDev& D, const float* latent
   if (ws_bytes < ws_need) return fail(ctx, DISTR_ERR_WORKSPACE, "%s", small_ws);
   *c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   if (n == 0) return DISTR_OK;
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, *c0c4, D, latent);
+  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, *c0c4, D, latent, (int64_t)0, (SegTable*)nullptr, SegCounts{});
   LAUNCH_CHECK("k_latent_consts");
   return DISTR_OK;
 }
@@ -799,7 +812,7 @@ int distr_color_backward(distr_ctx* ctx, const float* latent_cat, const float* x
   hipLaunchKernelGGL(k_color_bwd, dim3(tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, g_rgb, g_xyz, partial, ctx->DC);
   LAUNCH_CHECK("k_color_bwd");
   if (g_latent_cat) {
-    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->DC, g_latent_cat);
+    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->DC, g_latent_cat, (const SegTable*)nullptr);
     LAUNCH_CHECK("k_points_latent_grad");
   }
   return DISTR_OK;
@@ -1308,7 +1321,7 @@ static int mlp_backward_impl(distr_ctx* ctx, const float* latent, const float* x
   const unsigned tiles = (unsigned)((n + 63) / 64);
   if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), tiles, s, B))) return rc;
   if (g_latent) {
-    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->D, g_latent);
+    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->D, g_latent, (const SegTable*)nullptr);
     LAUNCH_CHECK("k_points_latent_grad");
   }
   return DISTR_OK;
@@ -1319,6 +1332,144 @@ int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, in
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   return mlp_backward_impl(ctx, latent, xyz, n, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- segmented point lists (distr_mlp_*_multi): S segments with a code each, one launch sequence for all of them
+namespace {
+
+struct MultiPlan {
+  SegCounts cnt;
+  int64_t ntot;              // points of all segments
+  unsigned tiles;            // 64-point tiles of all segments (every segment's count rounded up on its own)
+};
+
+// the plan of a segmented list, or why the list is refused: the error code, and the text through fail() (ctx may be null: the workspace sizes)
+int multi_plan(distr_ctx* ctx, int32_t nseg, const int64_t* counts, MultiPlan& p) {
+  memset(&p, 0, sizeof(p));
+  if (nseg < 1 || nseg > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nseg %d: 1..%d", nseg, DISTR_MAX_VIEWS);
+  if (!counts) return fail(ctx, DISTR_ERR_INVALID_ARG, "null counts (host array of nseg)");
+  int64_t tiles = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (counts[s] < 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "counts[%d] = %lld: negative", s, (long long)counts[s]);
+    if (counts[s] > ((int64_t)1 << 30) || (p.ntot += counts[s]) > ((int64_t)1 << 30))
+      return fail(ctx, DISTR_ERR_UNSUPPORTED, "segmented point list: more than 2^30 points");
+    p.cnt.n[s] = counts[s];
+    tiles += (counts[s] + SEG_TILE - 1) / SEG_TILE;
+  }
+  p.tiles = (unsigned)tiles;
+  return DISTR_OK;
+}
+
+// workspace of a segmented call: [segments][1024] latent constants | tile table | (backward) [tiles][PSTRIDE] partials
+struct MultiWs { float* c0c4; SegTable* tab; float* partial; size_t bytes; };
+MultiWs multi_ws(void* base, int32_t nseg, const MultiPlan& p, bool backward) {
+  WsCarve c(base);
+  MultiWs w;
+  w.c0c4 = c.take<float>((size_t)nseg * 2 * HID);
+  w.tab = c.take<SegTable>(1);
+  w.partial = backward ? c.take<float>((size_t)p.tiles * PSTRIDE) : nullptr;
+  w.bytes = c.bytes();
+  return w;
+}
+
+// checks (ptrs_ok: the caller's per-point arrays are there; an empty list needs none) + the constants and the tile table of every segment
+int multi_prologue(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, bool ptrs_ok, void* ws,
+                   size_t ws_bytes, bool backward, hipStream_t s, MultiPlan& p, MultiWs& w) {
+  if (int rc = multi_plan(ctx, nseg, counts, p)) return rc;
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->D.nlat);
+  if (!latent || !ws || (p.ntot > 0 && !ptrs_ok)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < multi_ws(nullptr, nseg, p, backward).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "segmented point list: workspace too small");
+  w = multi_ws(ws, nseg, p, backward);
+  if (p.ntot == 0) return DISTR_OK;
+  hipLaunchKernelGGL(k_latent_consts, dim3(4, (unsigned)nseg), dim3(256), 0, s, w.c0c4, ctx->D, latent, latent_stride, w.tab, p.cnt);
+  LAUNCH_CHECK("k_latent_consts<segments>");
+  return DISTR_OK;
+}
+
+// decode_sdf of a segmented list (distr_mlp_eval_multi, distr_depth_samples_forward with a code per view); the caller holds the EntryGuard
+int mlp_eval_multi_impl(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, const float* xyz,
+                        float clamp, float* sdf, void* ws, size_t ws_bytes, hipStream_t s) {
+  MultiPlan p;
+  MultiWs w;
+  int rc = multi_prologue(ctx, nseg, counts, latent, latent_stride, xyz && sdf, ws, ws_bytes, false, s, p, w);
+  if (rc || p.ntot == 0) return rc;
+  MarchArgs A;
+  memset(&A, 0, sizeof(A));
+  A.xyz = xyz; A.sdf_out = sdf; A.c0c4 = w.c0c4; A.seg = w.tab; A.clamp = clamp;
+  MarchTimer timer(ctx, s);
+  timer.begin();
+  rc = launch_march(ctx, "k_march<eval, segments>", MODE_EVAL, 2, false, 0, wide_decoder(ctx), p.tiles, s, A);
+  timer.end();
+  return rc;
+}
+
+// its backward (distr_mlp_backward_multi, distr_depth_samples_backward): g_xyz and / or one g_latent row per segment
+int mlp_backward_multi_impl(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, const float* xyz,
+                            const float* g_sdf, float clamp, float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, hipStream_t s) {
+  MultiPlan p;
+  MultiWs w;
+  int rc = multi_prologue(ctx, nseg, counts, latent, latent_stride, xyz && g_sdf, ws, ws_bytes, true, s, p, w);
+  if (rc) return rc;
+  if (p.ntot == 0) {
+    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * ctx->D.nlat * sizeof(float), s));
+    return DISTR_OK;
+  }
+  BwdArgs B;
+  memset(&B, 0, sizeof(B));
+  B.xyz = xyz; B.c0c4 = w.c0c4; B.seg = w.tab; B.coef = g_sdf; B.clamp = clamp; B.partial = w.partial; B.out_g = g_xyz;
+  if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent, segments>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), p.tiles, s, B))) return rc;
+  if (g_latent) {
+    hipLaunchKernelGGL(k_points_latent_grad, dim3((unsigned)nseg), dim3(256), 0, s, (const float*)w.partial, 0, ctx->D, g_latent, (const SegTable*)w.tab);
+    LAUNCH_CHECK("k_points_latent_grad<segments>");
+  }
+  return DISTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t distr_mlp_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  MultiPlan p;
+  return multi_plan(nullptr, nseg, counts_host, p) == DISTR_OK ? multi_ws(nullptr, nseg, p, false).bytes : 0;
+}
+
+size_t distr_mlp_backward_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  MultiPlan p;
+  return multi_plan(nullptr, nseg, counts_host, p) == DISTR_OK ? multi_ws(nullptr, nseg, p, true).bytes : 0;
+}
+
+int distr_mlp_eval_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride, const float* xyz,
+                         float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  return mlp_eval_multi_impl(ctx, nseg, counts_host, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int distr_mlp_grad_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride, const float* xyz,
+                         float* sdf, float* grad, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  MultiPlan p;
+  MultiWs w;
+  const int rc = multi_prologue(ctx, nseg, counts_host, latent, latent_stride, xyz && sdf && grad, ws, ws_bytes, false, s, p, w);
+  if (rc || p.ntot == 0) return rc;
+  BwdArgs B;
+  memset(&B, 0, sizeof(B));
+  B.xyz = xyz; B.c0c4 = w.c0c4; B.seg = w.tab; B.out_sdf = sdf; B.out_g = grad;
+  return launch_bwd(ctx, "k_bwd<pointgrad, segments>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), p.tiles, s, B);
+}
+
+int distr_mlp_backward_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                             const float* xyz, const float* g_sdf, float clamp, float* g_xyz, float* g_latent, void* ws, size_t ws_bytes,
+                             void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  return mlp_backward_multi_impl(ctx, nseg, counts_host, latent, latent_stride, xyz, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, int layer, float* out, void* ws,
@@ -1564,19 +1715,6 @@ bool mc_grid_ok(int32_t nx, int32_t ny, int32_t nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
 }
 
-// workspace carving: every array on a 256-byte boundary, the base aligned up (the byte counts include that slack)
-struct WsCarve {
-  uintptr_t at;
-  size_t used = 0;
-  explicit WsCarve(void* base) : at(((uintptr_t)base + 255) & ~(uintptr_t)255) {}
-  template <typename T> T* take(size_t n) {
-    T* p = (T*)(at + used);
-    used += (n * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-  size_t bytes() const { return used + 256; }
-};
-
 struct McWs {
   uint16_t* info;
   int *vbase, *act, *afb;
@@ -1757,6 +1895,7 @@ struct SampPlan {
   int64_t ntot, nmax;        // valid pixels of all views, of the largest view
   int nblk_px;               // blocks of MTILE pixels per view (count / compact)
   int nblk_cam;              // blocks of MTILE valid pixels of the largest view (camera gradient)
+  int64_t seg[DISTR_MAX_VIEWS];   // entries of the point list per view (m per valid pixel): the segments of the decoder calls
 };
 
 int samp_cfg(distr_ctx* ctx, const distr_samples_cfg* c, int32_t nviews, SampPlan& p) {
@@ -1787,6 +1926,7 @@ int samp_counts(distr_ctx* ctx, const int64_t* counts, SampPlan& p) {
     p.VW.off[v] = (int32_t)p.ntot;
     p.ntot += counts[v];
     p.nmax = std::max(p.nmax, (int64_t)counts[v]);
+    p.seg[v] = counts[v] * p.G.m;
   }
   if (p.ntot * p.G.m > ((int64_t)1 << 29)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "point list of %lld entries: too long", (long long)(p.ntot * p.G.m));
   p.nblk_cam = (int)std::max<int64_t>(1, (p.nmax + samples::MTILE - 1) / samples::MTILE);
@@ -1804,13 +1944,16 @@ SampCountWs samp_count_ws(void* base, const SampPlan& p) {
   return w;
 }
 
+// forward: one plain evaluation (shared code) or one segmented one (a code per view); sized for either
+size_t samp_fwd_bytes(const SampPlan& p) { return std::max(distr_mlp_workspace_bytes(p.ntot * p.G.m), distr_mlp_multi_workspace_bytes(p.nviews, p.seg)); }
+
 struct SampBwdWs { float *g_xyz, *part; void* mlp; size_t mlp_bytes, bytes; };
 SampBwdWs samp_bwd_ws(void* base, const SampPlan& p) {
   WsCarve c(base);
   SampBwdWs w;
   w.g_xyz = c.take<float>((size_t)(3 * p.ntot * p.G.m));
   w.part = c.take<float>((size_t)p.nviews * p.nblk_cam * 12);
-  w.mlp_bytes = distr_mlp_backward_workspace_bytes(p.nmax * p.G.m);
+  w.mlp_bytes = distr_mlp_backward_multi_workspace_bytes(p.nviews, p.seg);      // one segmented backward: a segment per view
   w.mlp = c.take<char>(w.mlp_bytes);
   w.bytes = c.bytes();
   return w;
@@ -1832,7 +1975,7 @@ int distr_depth_samples_workspace_bytes(distr_ctx* ctx, const distr_samples_cfg*
     return DISTR_OK;
   }
   if (int rc = samp_counts(ctx, counts, p)) return rc;
-  if (forward_bytes) *forward_bytes = distr_mlp_workspace_bytes(p.ntot * p.G.m);
+  if (forward_bytes) *forward_bytes = samp_fwd_bytes(p);
   if (backward_bytes) *backward_bytes = samp_bwd_ws(nullptr, p).bytes;
   return DISTR_OK;
 }
@@ -1874,7 +2017,7 @@ int distr_depth_samples_forward(distr_ctx* ctx, const distr_samples_cfg* cfg, in
   if (!index || !latent || !RT || !depth || !draws || !ws || (p.G.mode == DISTR_SAMPLES_SURFACE && !normal) || (p.ntot > 0 && (!xyz || !out)))
     return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
   const int64_t L = p.ntot * p.G.m;
-  if (ws_bytes < distr_mlp_workspace_bytes(L)) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples forward workspace too small");
+  if (ws_bytes < samp_fwd_bytes(p)) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples forward workspace too small");
   if (L == 0) return DISTR_OK;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((p.nmax + samples::MB - 1) / samples::MB), (unsigned)nviews);
@@ -1882,11 +2025,8 @@ int distr_depth_samples_forward(distr_ctx* ctx, const distr_samples_cfg* cfg, in
   LAUNCH_CHECK("k_samp_points");
   if (latent_stride == 0 || nviews == 1) {
     if (int rc = mlp_eval_impl(ctx, latent, xyz, L, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
-  } else {           // a code per view: the evaluator takes one code per launch sequence (stream order keeps the shared workspace safe)
-    for (int v = 0; v < nviews; ++v) {
-      const int64_t o = (int64_t)p.G.m * p.VW.off[v], n = (int64_t)p.G.m * p.VW.n[v];
-      if (int rc = mlp_eval_impl(ctx, latent + v * latent_stride, xyz + 3 * o, n, cfg->clamp_dist, out + o, ws, ws_bytes, s)) return rc;
-    }
+  } else {           // a code per view: one segmented evaluation, a segment (with tiles of its own) per view
+    if (int rc = mlp_eval_multi_impl(ctx, nviews, p.seg, latent, latent_stride, xyz, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
   }
   if (p.G.mode == DISTR_SAMPLES_SURFACE) {
     hipLaunchKernelGGL(samples::k_samp_epilogue, grid, dim3(samples::MB), 0, s, p.VW, draws, out);
@@ -1910,11 +2050,10 @@ int distr_depth_samples_backward(distr_ctx* ctx, const distr_samples_cfg* cfg, i
   if (ws_bytes < samp_bwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "depth-samples backward workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const SampBwdWs w = samp_bwd_ws(ws, p);
-  // the point-list backward view by view: every view keeps the tiles and the reduction order of its stand-alone call
-  for (int v = 0; v < nviews; ++v) {
-    const int64_t o = (int64_t)p.G.m * p.VW.off[v], n = (int64_t)p.G.m * p.VW.n[v];
-    if (int rc = mlp_backward_impl(ctx, latent + v * latent_stride, xyz + 3 * o, n, g_out + o, cfg->clamp_dist, g_RT ? w.g_xyz + 3 * o : nullptr,
-                                   g_latent ? g_latent + (int64_t)v * ctx->D.nlat : nullptr, w.mlp, w.mlp_bytes, s))
+  // one segmented point-list backward, a segment per view: every view keeps the tiles and the reduction order of its stand-alone call
+  if (p.ntot > 0 || g_latent) {
+    if (int rc = mlp_backward_multi_impl(ctx, nviews, p.seg, latent, latent_stride, xyz, g_out, cfg->clamp_dist, g_RT ? w.g_xyz : nullptr, g_latent,
+                                         w.mlp, w.mlp_bytes, s))
       return rc;
   }
   if (g_RT) {

@@ -174,6 +174,29 @@ __device__ __forceinline__ void vfind(int32_t c, int32_t incl, int B, int g, int
   cnt = __shfl(c, b);
 }
 
+// Segmented point list (distr_mlp_*_multi): segment s = n[s] points from point off[s] on, with its own latent constants, on
+// ceil(n[s] / 64) tiles of ITS OWN (no tile straddles two segments, so a segment's tiles are those of its stand-alone call).
+// tend[s] = tiles of segments 0..s (an empty segment repeats its predecessor's value; entries behind the last segment hold the
+// total). Written by k_latent_consts from the host's counts, read by every tile: one load per lane + a ballot.
+constexpr int SEG_TILE = 64;
+struct SegCounts { int64_t n[DISTR_MAX_VIEWS]; };
+struct SegTable { int32_t tend[DISTR_MAX_VIEWS]; int32_t off[DISTR_MAX_VIEWS]; int32_t n[DISTR_MAX_VIEWS]; };
+static_assert(DISTR_MAX_VIEWS == 64, "one lane per segment");
+// segment of global tile `tile`: its index, the tile's first point inside the segment, the segment's first point and its count;
+// false: the tile lies behind the last segment. All results are wave-uniform (scalar registers).
+__device__ __forceinline__ bool seg_find(const SegTable* T, int tile, int& s, int64_t& base, int64_t& off, int64_t& count) {
+  const int lane = threadIdx.x & 63;
+  const int32_t end = T->tend[lane];
+  const unsigned long long hit = __ballot(tile < end);
+  if (hit == 0ull) return false;
+  s = __builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1);
+  const int32_t first = __builtin_amdgcn_readfirstlane(s ? T->tend[s - 1] : 0);
+  base = (int64_t)(tile - first) * SEG_TILE;
+  off = __builtin_amdgcn_readfirstlane(T->off[s]);
+  count = __builtin_amdgcn_readfirstlane(T->n[s]);
+  return true;
+}
+
 struct Sample { int32_t src; float zb; float coef; int32_t flags; float sdf; int32_t mblock; int32_t pad0, pad1; };
 
 // row source encoding: fine rows (level 0): the full-resolution march step that produced the row (the pixel is the row's own, k_bwd_prep
@@ -360,14 +383,28 @@ DISTR_GLOBAL void __launch_bounds__(256) k_prep(View V0, DecoderDev D, const flo
 }
 
 // latent constants only (decode_sdf / decode_sdf_gradient entry points)
-DISTR_GLOBAL void __launch_bounds__(256) k_latent_consts(float* c0c4 /*[1024]*/, DecoderDev D, const float* __restrict__ latent) {
+// Grid (4, segments): segment s reads the code at latent + s * lat_stride (0: one shared code) and writes c0c4[s][1024]. A segmented
+// list (tab != null) also gets its tile table here, from the host's counts (block (0, 0), one thread: at most 64 entries).
+DISTR_GLOBAL void __launch_bounds__(256) k_latent_consts(float* c0c4 /*[segments][1024]*/, DecoderDev D, const float* __restrict__ latent,
+                                                       int64_t lat_stride, SegTable* tab, SegCounts cnt) {
+  if (tab && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    int32_t tiles = 0, off = 0;
+    for (int s = 0; s < DISTR_MAX_VIEWS; ++s) {
+      const int32_t n = (s < (int)gridDim.y) ? (int32_t)cnt.n[s] : 0;
+      tab->off[s] = off; tab->n[s] = n;
+      off += n;
+      tiles += (n + SEG_TILE - 1) / SEG_TILE;
+      tab->tend[s] = tiles;
+    }
+  }
   const int gid = blockIdx.x * 256 + threadIdx.x;
   const int o = gid & 511;
   const float* Wt = (gid < 512) ? D.W0lat_t : D.W4lat_t;
   float acc = (gid < 512) ? D.b0[o] : D.b4[o];
+  latent += (int64_t)blockIdx.y * lat_stride;
 #pragma unroll 8
   for (int k = 0; k < D.nlat; ++k) acc = __builtin_fmaf(Wt[k * HID + o], latent[k], acc);
-  c0c4[gid] = acc;
+  c0c4[(size_t)blockIdx.y * (2 * HID) + gid] = acc;
 }
 
 // ------------------------------------------------------------------------------------------ ray setup
@@ -701,6 +738,7 @@ struct MarchArgs {
   DecoderB6 B6;              // split-bf16 weight planes (kernels instantiated with ARITH = 1, distr_render_cfg.arith)
   DecoderH3 H3;              // split-f16 weight planes (ARITH = 2)
   int32_t tail_absent;       // tests (DISTR_TAIL_TEST_ABSENT=n): workgroups 0 .. n-1 of k_tail leave at once, as if they never became resident
+  const SegTable* seg;       // MODE_EVAL on 64-point tiles: segmented list (c0c4 = [segments][1024], n unused); null: one code, n points
 };
 
 // One pyramid level of view b, read from the kernel-argument segment (MarchArgs is the first argument of every march kernel): a scalar
@@ -739,9 +777,15 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   bool origin = false;
   int vb = 0;
   int64_t base = (int64_t)tile * TILE, count = 0;
+  int seg = 0;               // MODE_EVAL: this tile's segment and the segment's first point (a plain list: 0, 0)
+  int64_t poff = 0;
   if (MODE == MODE_EVAL) {
-    count = A.n;
-    if (base >= count) return false;
+    if (TILE == SEG_TILE && A.seg) {
+      if (!seg_find(A.seg, tile, seg, base, poff, count)) return false;
+    } else {
+      count = A.n;
+      if (base >= count) return false;
+    }
   } else if (origin_tile && tile >= ntile_grid - B) {
     origin = true;
     vb = tile - (ntile_grid - B);
@@ -773,8 +817,8 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   const int32_t* list = nullptr;
   if (MODE == MODE_COARSE) list = level_at(A.lvl, vb).list;
   else if (MODE == MODE_FINE) list = split ? live_sel(V, A.step) : V.lv[0].list;
-  const float* c0 = (MODE == MODE_EVAL) ? A.c0c4 : V.C->c0;
-  const float* c4 = (MODE == MODE_EVAL) ? A.c0c4 + HID : V.C->c4;
+  const float* c0 = (MODE == MODE_EVAL) ? A.c0c4 + (size_t)seg * (2 * HID) : V.C->c0;
+  const float* c4 = (MODE == MODE_EVAL) ? c0 + HID : V.C->c4;
   if constexpr (ARITH == 0) stage_bias<RB, WIDE>(D, c0, c4, S);      // first thing: these loads travel under the prologue's dependent state loads
 
   int32_t id = -1;
@@ -788,8 +832,9 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
       valid = r < count;
       if (valid) {
         if (MODE == MODE_EVAL) {
-          id = (int32_t)r;
-          p[0] = A.xyz[r * 3]; p[1] = A.xyz[r * 3 + 1]; p[2] = A.xyz[r * 3 + 2];
+          const int64_t gr = poff + r;
+          id = (int32_t)gr;
+          p[0] = A.xyz[gr * 3]; p[1] = A.xyz[gr * 3 + 1]; p[2] = A.xyz[gr * 3 + 2];
         } else {
           id = list[r];
           const LevelView L = (MODE == MODE_COARSE) ? level_at(A.lvl, vb) : V.lv[0];
@@ -1924,6 +1969,7 @@ struct BwdArgs {
   float* out_g;              // POINTGRAD explicit: [n][3] (pixel lists: V.n_g)
   DecoderB6 B6;              // split-bf16 weight planes (k_bwd<BWD_SAVED, RB, 1>: distr_render_cfg.arith)
   DecoderH3 H3;              // split-f16 weight planes (k_bwd<BWD_SAVED, RB, 2>)
+  const SegTable* seg;       // POINTGRAD explicit on 64-point tiles: segmented list (c0c4 = [segments][1024], n unused); null: one code
 };
 
 __device__ __forceinline__ int32_t vget(int32_t x, int b, int B) { return (B <= 1) ? x : __shfl(x, b); }
@@ -1963,10 +2009,16 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
   const int B = explicit_points ? 1 : V0.nviews;
   int tile = blockIdx.x, vb = 0;
   int64_t count, base;
+  int seg = 0;               // explicit points: this tile's segment and the segment's first point (a plain list: 0, 0)
+  int64_t poff = 0;
   if (explicit_points) {
-    count = A.n;
-    base = (int64_t)tile * TILE;
-    if (base >= count) return;
+    if (TILE == SEG_TILE && A.seg) {
+      if (!seg_find(A.seg, tile, seg, base, poff, count)) return;      // `tile` stays the global one: the partial row
+    } else {
+      count = A.n;
+      base = (int64_t)tile * TILE;
+      if (base >= count) return;
+    }
   } else if (MODE == BWD_POINTGRAD) {
     // valid-pixel lists of all views, each padded to whole tiles
     const int32_t c = vload(&V0.C->cnt_normal, V0.vstride, B);
@@ -2040,6 +2092,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
       float p[3] = {0.f, 0.f, 0.f};
       r = base + tid;
       valid = r < count;
+      r += poff;               // explicit points: index into the whole list
       if (valid) {
         if (MODE == BWD_POINTGRAD && A.xyz) {
           p[0] = A.xyz[r * 3]; p[1] = A.xyz[r * 3 + 1]; p[2] = A.xyz[r * 3 + 2];
@@ -2060,8 +2113,8 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
       S.xyz[tid] = p[0]; S.xyz[TILE + tid] = p[1]; S.xyz[2 * TILE + tid] = p[2];
     }
     __syncthreads();
-    const float* c0 = A.c0c4 ? A.c0c4 : V.C->c0;
-    const float* c4 = A.c0c4 ? A.c0c4 + HID : V.C->c4;
+    const float* c0 = A.c0c4 ? A.c0c4 + (size_t)seg * (2 * HID) : V.C->c0;
+    const float* c4 = A.c0c4 ? c0 + HID : V.C->c4;
     float pre = 0.f;
     if constexpr (ARITH == 0) pre = mlp_forward<RB, true, false, false, WIDE>(D, c0, c4, S, masks);
     if (tid < TILE) {
@@ -2421,15 +2474,27 @@ DISTR_GLOBAL void __launch_bounds__(256) k_bwd_reduce(View V0, BwdWs W0, int chu
 }
 
 // decode_sdf backward (explicit points): ordered column sums of the tile partials, then g_latent as in k_bwd_final
-DISTR_GLOBAL void __launch_bounds__(256) k_points_latent_grad(const float* partial, int ntiles, DecoderDev D, float* g_latent) {
+// One block per segment of a segmented list (tab != null; `ntiles` unused): the segment's own tile range, in tile order -- the
+// order of its stand-alone call -- into g_latent[segment][nlat]; a segment without points writes zeros.
+DISTR_GLOBAL void __launch_bounds__(256) k_points_latent_grad(const float* partial, int ntiles, DecoderDev D, float* g_latent, const SegTable* tab) {
   __shared__ float red[2 * HID];
+  const int nlat = D.nlat;                           // C (SDF decoder) or 256 + color_size (colour decoder)
+  int t0 = 0, t1 = ntiles;
+  if (tab) {
+    t0 = blockIdx.x ? tab->tend[blockIdx.x - 1] : 0;
+    t1 = tab->tend[blockIdx.x];
+    g_latent += (size_t)blockIdx.x * nlat;
+    if (t0 == t1) {
+      for (int k = threadIdx.x; k < nlat; k += 256) g_latent[k] = 0.f;
+      return;
+    }
+  }
   for (int col = threadIdx.x; col < 2 * HID; col += 256) {
     float s = 0.f;
-    for (int t = 0; t < ntiles; ++t) s += partial[(size_t)t * PSTRIDE + col];
+    for (int t = t0; t < t1; ++t) s += partial[(size_t)t * PSTRIDE + col];
     red[col] = s;
   }
   __syncthreads();
-  const int nlat = D.nlat;                           // C (SDF decoder) or 256 + color_size (colour decoder)
   for (int k = threadIdx.x; k < nlat; k += 256) {
     float a = 0.f;
 #pragma unroll 16

@@ -31,6 +31,11 @@ MESH_EXPORTS = ['distr_mc_workspace_bytes', 'distr_mc_count', 'distr_mc_emit', '
 # depth maps back-projected into SDF samples (include/distr_samples.h, included by distr.h): SDFRenderer_deepsdf
 SAMPLES_EXPORTS = ['distr_depth_samples_workspace_bytes', 'distr_depth_samples_count', 'distr_depth_samples_forward',
                    'distr_depth_samples_backward']
+# the decoder on a segmented point list (include/distr_multi.h, included by distr.h): many shape codes in one launch sequence
+MULTI_EXPORTS = ['distr_mlp_multi_workspace_bytes', 'distr_mlp_backward_multi_workspace_bytes', 'distr_mlp_eval_multi',
+                 'distr_mlp_grad_multi', 'distr_mlp_backward_multi']
+MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
+SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
 SAMPLES_MAX_NUMBER = 64                             # DISTR_SAMPLES_MAX_NUMBER
 
@@ -127,7 +132,7 @@ class RenderStats(_Sized):
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
            'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h')                    # include/: the C ABI
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h')                    # include/: the C ABI
 INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -345,6 +350,12 @@ def lib():
             L.distr_depth_samples_count.argtypes = [vp, scfg, i32, fp, vp, i64p, vp, C.c_size_t, vp]
             L.distr_depth_samples_forward.argtypes = [vp, scfg, i32, i64p, vp, fp, i64, fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
             L.distr_depth_samples_backward.argtypes = [vp, scfg, i32, i64p, vp, fp, i64, fp, fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
+            for f in (L.distr_mlp_multi_workspace_bytes, L.distr_mlp_backward_multi_workspace_bytes):
+                f.argtypes = [i32, i64p]
+                f.restype = C.c_size_t
+            L.distr_mlp_eval_multi.argtypes = [vp, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp]
+            L.distr_mlp_grad_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, fp, vp, C.c_size_t, vp]
+            L.distr_mlp_backward_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, C.c_float, fp, fp, vp, C.c_size_t, vp]
             _lib = L
     return _lib
 

@@ -503,6 +503,130 @@ def mlp_eval_autograd(engine, latent, points, clamp_dist=None):
     return DecodeSdfFunction.apply(latent, points, engine, clamp_dist)
 
 
+def segment_plan(counts, max_segments=binding.MAX_SEGMENTS, tile=binding.SEG_TILE):
+    """Host-side plan of a segmented point list (pure Python, no GPU): counts[s] >= 0 points per segment ->
+    dict(counts: as a list of int, offsets: first point of every segment, tiles: ceil(n_s / 64) tiles each (a tile never holds two
+    segments; an empty segment gets none), total: points, chunks: [(s0, s1)] runs of at most 64 segments, one distr_mlp_*_multi call each)."""
+    counts = [int(c) for c in counts]
+    if not counts:
+        raise ValueError('a segmented point list needs at least one segment')
+    if min(counts) < 0:
+        raise ValueError('segment sizes must be >= 0, got %r' % (counts,))
+    offsets, at = [], 0
+    for c in counts:
+        offsets.append(at)
+        at += c
+    S = len(counts)
+    return dict(counts=counts, offsets=offsets, tiles=[(c + tile - 1) // tile for c in counts], total=at,
+                chunks=[(s0, min(S, s0 + max_segments)) for s0 in range(0, S, max_segments)])
+
+
+def _multi_args(engine, latents, points, counts):
+    """(codes (S, C) or (1, C) shared, flat points (N, 3), plan) of a segmented call; ValueError on a shape that does not fit."""
+    dev = engine.device
+    plan = segment_plan(counts)
+    S, Cn = len(plan['tiles']), engine.latent_size
+    lat = _f32c(latents, dev)
+    if lat.numel() not in (Cn, S * Cn):
+        raise ValueError('latents have shape %s; %d segments take (S, C) = (%d, %d) (or (1, %d): one shared code)'
+                         % (tuple(latents.shape), S, S, Cn, Cn))
+    x = _f32c(points, dev).reshape(-1, 3)
+    if x.shape[0] != plan['total']:
+        raise ValueError('counts sum to %d, but there are %d points' % (plan['total'], x.shape[0]))
+    return lat.reshape(-1, Cn), x, plan
+
+
+def _multi_chunks(lat, plan):
+    """Per chunk of at most 64 segments: (first segment, segments, first point, first code row, latent_stride); a shared code (lat (1, C))
+    is row 0 with stride 0 in every chunk. Pure Python."""
+    shared = lat.shape[0] == 1
+    for s0, s1 in plan['chunks']:
+        yield s0, s1 - s0, plan['offsets'][s0], (0 if shared else s0), (0 if shared else lat.shape[1])
+
+
+def _multi_run(engine, latents, points, counts, ws_bytes, outputs, call):
+    """The plumbing every segmented call shares. Checks the arguments, allocates `outputs(n points, S)`, then per chunk runs
+    call(head, tail, p0, s0, out) with head = the arguments every distr_mlp_*_multi begins with (handle, nseg, counts, codes,
+    latent_stride, xyz of the chunk), tail = those it ends with (workspace of ws_bytes(nseg, counts), its size, stream), p0 / s0 = the
+    chunk's first point / segment (where its slices of the per-point / per-segment arrays start). Returns the outputs."""
+    lat, x, plan = _multi_args(engine, latents, points, counts)
+    out = outputs(x.shape[0], len(plan['tiles']))
+    ctx, p = engine.ctx, binding.ptr
+    for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
+        cnt = (C.c_int64 * ns)(*plan['counts'][s0:s0 + ns])
+        ws = torch.empty(ws_bytes(ns, cnt), dtype=torch.uint8, device=engine.device)
+        ctx.check(call((ctx.h, ns, cnt, p(lat[row:]), stride, p(x[p0:])), (p(ws), ws.numel(), ctx.stream()), p0, s0, out))
+    return out
+
+
+def _clamp_arg(clamp_dist):
+    return -1.0 if clamp_dist is None else float(clamp_dist)
+
+
+def mlp_eval_multi(engine, latents, points, counts, clamp_dist=None):
+    """decode_sdf of a segmented point list: segment s = counts[s] consecutive rows of points (sum counts, 3), decoded with latents[s]
+    (latents (S, C); (1, C) = one shared code) -> (sum counts, 1). One launch sequence per 64 segments (distr_mlp_eval_multi); every
+    segment's slice is byte for byte mlp_eval of that segment alone."""
+    L, p, dev = engine.ctx.L, binding.ptr, engine.device
+    return _multi_run(engine, latents, points, counts, L.distr_mlp_multi_workspace_bytes,
+                      lambda n, S: torch.empty(n, 1, dtype=torch.float32, device=dev),
+                      lambda head, tail, p0, s0, out: L.distr_mlp_eval_multi(*head, _clamp_arg(clamp_dist), p(out[p0:]), *tail))
+
+
+def mlp_grad_multi(engine, latents, points, counts):
+    """(sdf (sum counts,), d sdf/d xyz (sum counts, 3)) of the unclamped decoder on a segmented point list (see mlp_eval_multi)."""
+    L, p, dev = engine.ctx.L, binding.ptr, engine.device
+    return _multi_run(engine, latents, points, counts, L.distr_mlp_multi_workspace_bytes,
+                      lambda n, S: (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev)),
+                      lambda head, tail, p0, s0, out: L.distr_mlp_grad_multi(*head, p(out[0][p0:]), p(out[1][p0:]), *tail))
+
+
+def mlp_backward_multi(engine, latents, points, counts, g_sdf, clamp_dist=None, need_latent=True, need_points=True):
+    """Backward of mlp_eval_multi for the upstream gradient g_sdf (sum counts,): (g_latent (S, C): one row per segment, also for a
+    shared code (the caller sums), g_points (sum counts, 3)); either is None when not needed."""
+    L, p, dev = engine.ctx.L, binding.ptr, engine.device
+    gs = _f32c(g_sdf, dev).reshape(-1)
+
+    def outputs(n, S):
+        if gs.numel() != n:
+            raise ValueError('g_sdf has %d entries for %d points' % (gs.numel(), n))
+        return (torch.empty(S, engine.latent_size, dtype=torch.float32, device=dev) if need_latent else None,
+                torch.empty(n, 3, dtype=torch.float32, device=dev) if need_points else None)
+
+    def call(head, tail, p0, s0, out):
+        g_l, g_x = out
+        return L.distr_mlp_backward_multi(*head, p(gs[p0:]), _clamp_arg(clamp_dist), p(None if g_x is None else g_x[p0:]),
+                                          p(None if g_l is None else g_l[s0:]), *tail)
+    return _multi_run(engine, latents, points, counts, L.distr_mlp_backward_multi_workspace_bytes, outputs, call)
+
+
+class DecodeSdfMultiFunction(torch.autograd.Function):
+    """mlp_eval_multi with autograd: (latents (S, C) or (1, C), points (sum counts, 3)) -> (sum counts, 1); backward =
+    distr_mlp_backward_multi, one launch sequence per 64 segments. Row s of the latent gradient is the stand-alone call's, bit for bit;
+    a shared code gets the sum of the rows."""
+
+    @staticmethod
+    def forward(ctx, latents, points, engine, counts, clamp_dist):
+        out = mlp_eval_multi(engine, latents, points, counts, clamp_dist)
+        ctx.engine, ctx.clamp, ctx.counts = engine, clamp_dist, [int(c) for c in counts]
+        ctx.save_for_backward(latents.detach(), points.detach())
+        ctx.need = (latents.requires_grad, points.requires_grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        engine = ctx.engine
+        latents, points = ctx.saved_tensors
+        g_rows, g_x = mlp_backward_multi(engine, latents, points, ctx.counts, g, ctx.clamp, need_latent=ctx.need[0], need_points=ctx.need[1])
+        if g_rows is not None:
+            g_rows = (g_rows.sum(0) if latents.numel() == engine.latent_size and g_rows.shape[0] > 1 else g_rows).reshape(latents.shape)
+        return g_rows, (None if g_x is None else g_x.reshape(points.shape)), None, None, None
+
+
+def mlp_eval_multi_autograd(engine, latents, points, counts, clamp_dist=None):
+    return DecodeSdfMultiFunction.apply(latents, points, engine, counts, clamp_dist)
+
+
 def depth_samples_count(engine, cfg, depth):
     """Valid pixels (0 < depth < 1e5) of V depth maps (V, H, W), compacted on the GPU in row-major order (distr_depth_samples_count: a
     fixed-order scan, one host read). Returns (depth as the f32 device tensor the kernels read, index (V, H*W) int32 whose first

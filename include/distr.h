@@ -369,5 +369,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_mesh.h"
 /* depth maps back-projected into SDF samples (SDFRenderer_deepsdf) */
 #include "distr_samples.h"
+/* the decoder on a segmented point list: many shape codes in one launch sequence */
+#include "distr_multi.h"
 
 #endif /* DISTR_H_ */

@@ -55,7 +55,8 @@ int distr_depth_samples_workspace_bytes(distr_ctx* ctx, const distr_samples_cfg*
 int distr_depth_samples_count(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const float* depth_dev, int32_t* index_dev,
                               int64_t* counts, void* ws_dev, size_t ws_bytes, void* stream);
 
-/* Point list, ONE decoder evaluation over the whole list (one per view when every view has a code of its own), epilogue.
+/* Point list, ONE decoder evaluation over the whole list, epilogue. With a code per view the evaluation is the segmented one of
+ * distr_multi.h, a segment per view: still one launch sequence, every view's slice byte for byte its own call.
  *   latent_dev + v * latent_stride (floats; 0 = one code shared by all views)
  *   normal_dev   SURFACE only (FREESPACE: may be NULL)
  *   xyz_dev[L][3]  the point list in the decoder's frame (output; the backward reads it)
@@ -67,7 +68,8 @@ int distr_depth_samples_forward(distr_ctx* ctx, const distr_samples_cfg* cfg, in
 
 /* g_out_dev[L] (upstream gradient of out_dev) -> g_latent_dev[nviews][C] (per view: a shared code's gradient is the sum over v, left
  * to the caller) and g_RT_dev[nviews][3][4]; either may be NULL. depth and normal are observations: no gradient. index_dev, xyz_dev
- * and all inputs as in the forward. */
+ * and all inputs as in the forward. The decoder's backward is one segmented launch sequence too (distr_mlp_backward_multi's), for a
+ * shared code and a code per view alike. */
 int distr_depth_samples_backward(distr_ctx* ctx, const distr_samples_cfg* cfg, int32_t nviews, const int64_t* counts,
                                  const int32_t* index_dev, const float* latent_dev, int64_t latent_stride, const float* RT_dev,
                                  const float* depth_dev, const float* draws_dev, const float* xyz_dev, const float* g_out_dev,
