@@ -513,17 +513,82 @@ struct WsCarve {
   size_t bytes() const { return used + 256; }
 };
 
-// Prologue of the entry points that run a decoder on a point list: the caller's own argument check (args_ok, with its text), the
-// workspace size, then the constants the tiles read instead of the latent columns of lin0 / lin4 (k_latent_consts), at the 256-byte
-// aligned start of the workspace. An empty list (n == 0) gets the checks only.
-int point_list_prologue(distr_ctx* ctx, const DecoderDev& D, const float* latent, int64_t n, bool args_ok, void* ws, size_t ws_bytes, size_t ws_need,
-                        hipStream_t s, float** c0c4, const char* bad_args = "bad argument", const char* small_ws = "workspace too small") {
-  if (!args_ok) return fail(ctx, DISTR_ERR_INVALID_ARG, "%s", bad_args);
-  if (ws_bytes < ws_need) return fail(ctx, DISTR_ERR_WORKSPACE, "%s", small_ws);
-  *c0c4 = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  if (n == 0) return DISTR_OK;
-  hipLaunchKernelGGL(k_latent_consts, dim3(4), dim3(256), 0, s, *c0c4, D, latent, (int64_t)0, (SegTable*)nullptr, SegCounts{});
+// ---- point lists: n points decoded with one code (plain), or S segments with a code each (segmented), one launch sequence either way
+struct PointList {
+  int64_t n;                 // points (of all segments)
+  unsigned tiles;            // 64-point tiles (every segment's count rounded up on its own)
+  int32_t nseg;              // 0: the plain list -- one code, null table, zero SegCounts
+  SegCounts cnt;
+  float* c0c4;               // workspace: [codes][2 * HID] latent constants | (segmented) tile table | (backward) [tiles][PSTRIDE] partials
+  SegTable* tab;
+  float* partial;
+  const char *bad_args, *small_ws;     // texts of the two refusals of point_list_prologue
+};
+
+PointList plain_list(int64_t n) {
+  PointList pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.n = n; pl.tiles = (unsigned)((n + 63) / 64);
+  pl.bad_args = "bad argument"; pl.small_ws = "workspace too small";
+  return pl;
+}
+
+// the plan of a segmented list, or why the list is refused: the error code, and the text through fail() (ctx may be null: the workspace sizes)
+int seg_list(distr_ctx* ctx, int32_t nseg, const int64_t* counts, PointList& pl) {
+  memset(&pl, 0, sizeof(pl));
+  if (nseg < 1 || nseg > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nseg %d: 1..%d", nseg, DISTR_MAX_VIEWS);
+  if (!counts) return fail(ctx, DISTR_ERR_INVALID_ARG, "null counts (host array of nseg)");
+  int64_t tiles = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (counts[s] < 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "counts[%d] = %lld: negative", s, (long long)counts[s]);
+    if (counts[s] > ((int64_t)1 << 30) || (pl.n += counts[s]) > ((int64_t)1 << 30))
+      return fail(ctx, DISTR_ERR_UNSUPPORTED, "segmented point list: more than 2^30 points");
+    pl.cnt.n[s] = counts[s];
+    tiles += (counts[s] + SEG_TILE - 1) / SEG_TILE;
+  }
+  pl.tiles = (unsigned)tiles; pl.nseg = nseg;
+  pl.bad_args = "null device pointer"; pl.small_ws = "segmented point list: workspace too small";
+  return DISTR_OK;
+}
+
+// Lays the workspace of a list out (base == nullptr: sizes only) and returns the bytes the layout takes. The plain list: c0c4 at the
+// 256-byte aligned base and, 2 * HID * sizeof(float) = 4096 being a multiple of 256, partial at c0c4 + 2 * HID floats with no table between
+// them -- the layout distr_mlp_workspace_bytes / distr_mlp_backward_workspace_bytes size (the latter for ceil(n / 32) tiles: more than the
+// ceil(n / 64) taken here, and that size is ABI).
+static_assert(2 * HID * sizeof(float) % 256 == 0, "plain point list: partial follows c0c4 without padding");
+size_t carve_list(void* base, PointList& pl, bool backward) {
+  WsCarve c(base);
+  pl.c0c4 = c.take<float>((size_t)std::max(pl.nseg, 1) * 2 * HID);
+  pl.tab = pl.nseg ? c.take<SegTable>(1) : nullptr;
+  pl.partial = backward ? c.take<float>((size_t)pl.tiles * PSTRIDE) : nullptr;
+  return c.bytes();
+}
+
+// Prologue of the entry points that run decoder D on a point list: the null-pointer check (ptrs_ok: the caller's per-point arrays are
+// there; an empty list needs none), the workspace size, the carve, then the constants the tiles read instead of the latent columns of
+// lin0 / lin4 and the tile table of a segmented list (k_latent_consts). An empty list gets the checks and the carve only.
+int point_list_prologue(distr_ctx* ctx, const DecoderDev& D, PointList& pl, const float* latent, int64_t latent_stride, bool ptrs_ok, void* ws,
+                        size_t ws_bytes, bool backward, hipStream_t s) {
+  if (pl.n < 0 || !latent || !ws || (pl.n > 0 && !ptrs_ok)) return fail(ctx, DISTR_ERR_INVALID_ARG, "%s", pl.bad_args);
+  const size_t need = pl.nseg ? carve_list(nullptr, pl, backward) : backward ? distr_mlp_backward_workspace_bytes(pl.n) : distr_mlp_workspace_bytes(pl.n);
+  if (ws_bytes < need) return fail(ctx, DISTR_ERR_WORKSPACE, "%s", pl.small_ws);
+  carve_list(ws, pl, backward);
+  if (pl.n == 0) return DISTR_OK;
+  hipLaunchKernelGGL(k_latent_consts, pl.nseg ? dim3(4, (unsigned)pl.nseg) : dim3(4), dim3(256), 0, s, pl.c0c4, D, latent, latent_stride, pl.tab, pl.cnt);
   LAUNCH_CHECK("k_latent_consts");
+  return DISTR_OK;
+}
+
+// Tail of every point-list backward: the code gradient(s) from the tiles' partial sums, a row per segment; zeros for an empty list.
+int list_latent_grad(distr_ctx* ctx, const DecoderDev& D, const PointList& pl, float* g_latent, hipStream_t s) {
+  if (!g_latent) return DISTR_OK;
+  if (pl.n == 0) {
+    HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)std::max(pl.nseg, 1) * D.nlat * sizeof(float), s));
+    return DISTR_OK;
+  }
+  hipLaunchKernelGGL(k_points_latent_grad, dim3((unsigned)std::max(pl.nseg, 1)), dim3(256), 0, s, (const float*)pl.partial, pl.nseg ? 0 : (int)pl.tiles, D,
+                     g_latent, (const SegTable*)pl.tab);
+  LAUNCH_CHECK("k_points_latent_grad");
   return DISTR_OK;
 }
 
@@ -783,11 +848,11 @@ int distr_color_eval(distr_ctx* ctx, const float* latent_cat, const float* xyz, 
   EntryGuard guard_(ctx);
   if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4;
-  const int rc = point_list_prologue(ctx, ctx->DC, latent_cat, n, !(n < 0 || !latent_cat || (n > 0 && (!xyz || !rgb)) || !ws), ws, ws_bytes,
-                                     distr_mlp_workspace_bytes(n), s, &c0c4, "null device pointer", "colour workspace too small");
+  PointList pl = plain_list(n);
+  pl.bad_args = "null device pointer"; pl.small_ws = "colour workspace too small";
+  const int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, 0, xyz && rgb, ws, ws_bytes, false, s);
   if (rc || n == 0) return rc;
-  hipLaunchKernelGGL(k_color, dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, rgb, ctx->DC);
+  hipLaunchKernelGGL(k_color, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, rgb, ctx->DC);
   LAUNCH_CHECK("k_color");
   return DISTR_OK;
 }
@@ -799,23 +864,15 @@ int distr_color_backward(distr_ctx* ctx, const float* latent_cat, const float* x
   EntryGuard guard_(ctx);
   if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4;
-  const int rc = point_list_prologue(ctx, ctx->DC, latent_cat, n, !(n < 0 || !latent_cat || (n > 0 && (!xyz || !g_rgb)) || !ws), ws, ws_bytes,
-                                     distr_mlp_backward_workspace_bytes(n), s, &c0c4, "null device pointer", "colour backward workspace too small");
+  PointList pl = plain_list(n);
+  pl.bad_args = "null device pointer"; pl.small_ws = "colour backward workspace too small";
+  const int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, 0, xyz && g_rgb, ws, ws_bytes, true, s);
   if (rc) return rc;
-  if (n == 0) {
-    if (g_latent_cat) HIP_TRY(hipMemsetAsync(g_latent_cat, 0, (size_t)ctx->DC.nlat * sizeof(float), s));
-    return DISTR_OK;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_color_bwd, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, g_rgb, g_xyz, pl.partial, ctx->DC);
+    LAUNCH_CHECK("k_color_bwd");
   }
-  float* partial = (float*)(((uintptr_t)(c0c4 + 2 * HID) + 255) & ~(uintptr_t)255);
-  const unsigned tiles = (unsigned)((n + 63) / 64);
-  hipLaunchKernelGGL(k_color_bwd, dim3(tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, g_rgb, g_xyz, partial, ctx->DC);
-  LAUNCH_CHECK("k_color_bwd");
-  if (g_latent_cat) {
-    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->DC, g_latent_cat, (const SegTable*)nullptr);
-    LAUNCH_CHECK("k_points_latent_grad");
-  }
-  return DISTR_OK;
+  return list_latent_grad(ctx, ctx->DC, pl, g_latent_cat, s);
 }
 
 int distr_workspace_bytes(distr_ctx* ctx, const distr_render_cfg* cfg, size_t* fwd, size_t* bwd) {
@@ -1223,32 +1280,105 @@ int distr_render_normal_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32
 
 size_t distr_mlp_workspace_bytes(int64_t n) { (void)n; return 2 * HID * sizeof(float) + 256; }
 
-// decode_sdf on a point list (distr_mlp_eval, and the list of distr_depth_samples_forward); the caller holds the EntryGuard
-static int mlp_eval_impl(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
-                         size_t ws_bytes, hipStream_t s) {
+size_t distr_mlp_backward_workspace_bytes(int64_t n) {
+  const size_t tiles = (size_t)((n + 31) / 32);
+  return distr_mlp_workspace_bytes(n) + tiles * PSTRIDE * sizeof(float) + 256;
+}
+
+size_t distr_mlp_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  PointList pl;
+  return seg_list(nullptr, nseg, counts_host, pl) == DISTR_OK ? carve_list(nullptr, pl, false) : 0;
+}
+
+size_t distr_mlp_backward_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  PointList pl;
+  return seg_list(nullptr, nseg, counts_host, pl) == DISTR_OK ? carve_list(nullptr, pl, true) : 0;
+}
+
+}  // extern "C"
+
+// ---- decode_sdf on a point list, plain or segmented: the entry points below and the lists of distr_depth_samples_*
+namespace {
+
+// the two ways to a list of the SDF decoder, each with the checks that come before the pointers'; the caller holds the EntryGuard
+int sdf_plain_list(distr_ctx* ctx, int64_t n, PointList& pl) {
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  float* c0c4;
-  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
-  if (rc || n == 0) return rc;
+  pl = plain_list(n);
+  return DISTR_OK;
+}
+
+int sdf_seg_list(distr_ctx* ctx, int32_t nseg, const int64_t* counts, int64_t latent_stride, PointList& pl) {
+  if (int rc = seg_list(ctx, nseg, counts, pl)) return rc;
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->D.nlat);
+  return DISTR_OK;
+}
+
+// sdf of every point
+int mlp_eval_list(distr_ctx* ctx, PointList& pl, const float* latent, int64_t latent_stride, const float* xyz, float clamp, float* sdf, void* ws,
+                  size_t ws_bytes, hipStream_t s) {
+  int rc = point_list_prologue(ctx, ctx->D, pl, latent, latent_stride, xyz && sdf, ws, ws_bytes, false, s);
+  if (rc || pl.n == 0) return rc;
   MarchArgs A;
   memset(&A, 0, sizeof(A));
-  A.xyz = xyz; A.sdf_out = sdf; A.c0c4 = c0c4; A.n = n; A.clamp = clamp;
+  A.xyz = xyz; A.sdf_out = sdf; A.c0c4 = pl.c0c4; A.seg = pl.tab; A.n = pl.nseg ? 0 : pl.n; A.clamp = clamp;
   MarchTimer timer(ctx, s);
   timer.begin();
-  // a point list that fits one wave of 16-ray tiles runs on those (107 us instead of a 380 us 64-ray tile: decode_sdf on a few
+  // a plain list that fits one wave of 16-ray tiles runs on those (107 us instead of a 380 us 64-ray tile: decode_sdf on a few
   // thousand points is latency-bound); same values bit for bit
   const bool wide = wide_decoder(ctx);
-  if (!wide && n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold)) rc = launch_march16(ctx, "k_march<eval>", MODE_EVAL, false, (unsigned)((n + 15) / 16), s, A);
-  else rc = launch_march(ctx, "k_march<eval>", MODE_EVAL, 2, false, 0, wide, (unsigned)((n + 63) / 64), s, A);
+  if (!pl.nseg && !wide && pl.n <= std::min(ctx->tail16_threshold, ctx->hybrid_threshold))
+    rc = launch_march16(ctx, "k_march<eval>", MODE_EVAL, false, (unsigned)((pl.n + 15) / 16), s, A);
+  else rc = launch_march(ctx, "k_march<eval>", MODE_EVAL, 2, false, 0, wide, pl.tiles, s, A);
   timer.end();
   return rc;
 }
+
+// (sdf, d sdf / d xyz) of every point of the unclamped decoder
+int mlp_grad_list(distr_ctx* ctx, PointList& pl, const float* latent, int64_t latent_stride, const float* xyz, float* sdf, float* grad, void* ws,
+                  size_t ws_bytes, hipStream_t s) {
+  const int rc = point_list_prologue(ctx, ctx->D, pl, latent, latent_stride, xyz && sdf && grad, ws, ws_bytes, false, s);
+  if (rc || pl.n == 0) return rc;
+  BwdArgs B;
+  memset(&B, 0, sizeof(B));
+  B.n = pl.nseg ? 0 : pl.n; B.xyz = xyz; B.c0c4 = pl.c0c4; B.seg = pl.tab; B.out_sdf = sdf; B.out_g = grad;
+  return launch_bwd(ctx, "k_bwd<pointgrad>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), pl.tiles, s, B);
+}
+
+// backward of mlp_eval_list: g_xyz and / or one g_latent row per code
+int mlp_backward_list(distr_ctx* ctx, PointList& pl, const float* latent, int64_t latent_stride, const float* xyz, const float* g_sdf, float clamp,
+                      float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, hipStream_t s) {
+  int rc = point_list_prologue(ctx, ctx->D, pl, latent, latent_stride, xyz && g_sdf, ws, ws_bytes, true, s);
+  if (rc) return rc;
+  if (pl.n > 0) {
+    BwdArgs B;
+    memset(&B, 0, sizeof(B));
+    B.n = pl.nseg ? 0 : pl.n; B.xyz = xyz; B.c0c4 = pl.c0c4; B.seg = pl.tab; B.coef = g_sdf; B.clamp = clamp; B.partial = pl.partial; B.out_g = g_xyz;
+    if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), pl.tiles, s, B))) return rc;
+  }
+  return list_latent_grad(ctx, ctx->D, pl, g_latent, s);
+}
+
+}  // namespace
+
+extern "C" {
 
 int distr_mlp_eval(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float clamp, float* sdf, void* ws,
                    size_t ws_bytes, void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
-  return mlp_eval_impl(ctx, latent, xyz, n, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
+  PointList pl;
+  if (int rc = sdf_plain_list(ctx, n, pl)) return rc;
+  return mlp_eval_list(ctx, pl, latent, 0, xyz, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int distr_mlp_eval_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride, const float* xyz,
+                         float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  PointList pl;
+  if (int rc = sdf_seg_list(ctx, nseg, counts_host, latent_stride, pl)) return rc;
+  return mlp_eval_list(ctx, pl, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // decode_sdf in one of the split arithmetics (h3: f16x3, else bf16x6)
@@ -1260,14 +1390,13 @@ static int mlp_eval_split(distr_ctx* ctx, bool h3, const float* latent, const fl
   if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "%s: built for code length %d only (this decoder: %d); use f32", h3 ? "f16x3" : "bf16x6", LAT, ctx->D.nlat);
   if (h3 && !ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4;      // (exact f32: the latent columns stay a per-call constant)
-  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  PointList pl = plain_list(n);      // (exact f32: the latent columns stay a per-call constant)
+  const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, xyz && sdf, ws, ws_bytes, false, s);
   if (rc || n == 0) return rc;
-  const dim3 grid((unsigned)((n + 63) / 64));
   MarchTimer timer(ctx, s);
   timer.begin();
-  if (h3) hipLaunchKernelGGL(k_eval_h3, grid, dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->H3);
-  else hipLaunchKernelGGL(k_eval_b6, grid, dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, clamp, sdf, ctx->D, ctx->B6);
+  if (h3) hipLaunchKernelGGL(k_eval_h3, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, clamp, sdf, ctx->D, ctx->H3);
+  else hipLaunchKernelGGL(k_eval_b6, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, clamp, sdf, ctx->D, ctx->B6);
   timer.end();
   LAUNCH_CHECK(h3 ? "k_eval_h3" : "k_eval_b6");
   return DISTR_OK;
@@ -1287,181 +1416,27 @@ int distr_mlp_grad(distr_ctx* ctx, const float* latent, const float* xyz, int64_
                    size_t ws_bytes, void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
-  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  hipStream_t s = (hipStream_t)stream;
-  float* c0c4;
-  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !sdf || !grad)) || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
-  if (rc || n == 0) return rc;
-  BwdArgs B;
-  memset(&B, 0, sizeof(B));
-  B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.out_sdf = sdf; B.out_g = grad;
-  return launch_bwd(ctx, "k_bwd<pointgrad>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), (unsigned)((n + 63) / 64), s, B);
-}
-
-size_t distr_mlp_backward_workspace_bytes(int64_t n) {
-  const size_t tiles = (size_t)((n + 31) / 32);
-  return distr_mlp_workspace_bytes(n) + tiles * PSTRIDE * sizeof(float) + 256;
-}
-
-// backward of decode_sdf on a point list (distr_mlp_backward, distr_depth_samples_backward); the caller holds the EntryGuard
-static int mlp_backward_impl(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
-                             float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  float* c0c4;
-  int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n < 0 || (n > 0 && (!xyz || !g_sdf)) || !latent || !ws), ws, ws_bytes, distr_mlp_backward_workspace_bytes(n), s, &c0c4);
-  if (rc) return rc;
-  if (n == 0) {
-    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)ctx->D.nlat * sizeof(float), s));
-    return DISTR_OK;
-  }
-  float* partial = (float*)(((uintptr_t)(c0c4 + 2 * HID) + 255) & ~(uintptr_t)255);
-  BwdArgs B;
-  memset(&B, 0, sizeof(B));
-  B.n = n; B.xyz = xyz; B.c0c4 = c0c4; B.coef = g_sdf; B.clamp = clamp; B.partial = partial; B.out_g = g_xyz;
-  const unsigned tiles = (unsigned)((n + 63) / 64);
-  if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), tiles, s, B))) return rc;
-  if (g_latent) {
-    hipLaunchKernelGGL(k_points_latent_grad, dim3(1), dim3(256), 0, s, (const float*)partial, (int)tiles, ctx->D, g_latent, (const SegTable*)nullptr);
-    LAUNCH_CHECK("k_points_latent_grad");
-  }
-  return DISTR_OK;
-}
-
-int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
-                       float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  return mlp_backward_impl(ctx, latent, xyz, n, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- segmented point lists (distr_mlp_*_multi): S segments with a code each, one launch sequence for all of them
-namespace {
-
-struct MultiPlan {
-  SegCounts cnt;
-  int64_t ntot;              // points of all segments
-  unsigned tiles;            // 64-point tiles of all segments (every segment's count rounded up on its own)
-};
-
-// the plan of a segmented list, or why the list is refused: the error code, and the text through fail() (ctx may be null: the workspace sizes)
-int multi_plan(distr_ctx* ctx, int32_t nseg, const int64_t* counts, MultiPlan& p) {
-  memset(&p, 0, sizeof(p));
-  if (nseg < 1 || nseg > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nseg %d: 1..%d", nseg, DISTR_MAX_VIEWS);
-  if (!counts) return fail(ctx, DISTR_ERR_INVALID_ARG, "null counts (host array of nseg)");
-  int64_t tiles = 0;
-  for (int s = 0; s < nseg; ++s) {
-    if (counts[s] < 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "counts[%d] = %lld: negative", s, (long long)counts[s]);
-    if (counts[s] > ((int64_t)1 << 30) || (p.ntot += counts[s]) > ((int64_t)1 << 30))
-      return fail(ctx, DISTR_ERR_UNSUPPORTED, "segmented point list: more than 2^30 points");
-    p.cnt.n[s] = counts[s];
-    tiles += (counts[s] + SEG_TILE - 1) / SEG_TILE;
-  }
-  p.tiles = (unsigned)tiles;
-  return DISTR_OK;
-}
-
-// workspace of a segmented call: [segments][1024] latent constants | tile table | (backward) [tiles][PSTRIDE] partials
-struct MultiWs { float* c0c4; SegTable* tab; float* partial; size_t bytes; };
-MultiWs multi_ws(void* base, int32_t nseg, const MultiPlan& p, bool backward) {
-  WsCarve c(base);
-  MultiWs w;
-  w.c0c4 = c.take<float>((size_t)nseg * 2 * HID);
-  w.tab = c.take<SegTable>(1);
-  w.partial = backward ? c.take<float>((size_t)p.tiles * PSTRIDE) : nullptr;
-  w.bytes = c.bytes();
-  return w;
-}
-
-// checks (ptrs_ok: the caller's per-point arrays are there; an empty list needs none) + the constants and the tile table of every segment
-int multi_prologue(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, bool ptrs_ok, void* ws,
-                   size_t ws_bytes, bool backward, hipStream_t s, MultiPlan& p, MultiWs& w) {
-  if (int rc = multi_plan(ctx, nseg, counts, p)) return rc;
-  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
-  if (latent_stride != 0 && latent_stride < ctx->D.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->D.nlat);
-  if (!latent || !ws || (p.ntot > 0 && !ptrs_ok)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  if (ws_bytes < multi_ws(nullptr, nseg, p, backward).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "segmented point list: workspace too small");
-  w = multi_ws(ws, nseg, p, backward);
-  if (p.ntot == 0) return DISTR_OK;
-  hipLaunchKernelGGL(k_latent_consts, dim3(4, (unsigned)nseg), dim3(256), 0, s, w.c0c4, ctx->D, latent, latent_stride, w.tab, p.cnt);
-  LAUNCH_CHECK("k_latent_consts<segments>");
-  return DISTR_OK;
-}
-
-// decode_sdf of a segmented list (distr_mlp_eval_multi, distr_depth_samples_forward with a code per view); the caller holds the EntryGuard
-int mlp_eval_multi_impl(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, const float* xyz,
-                        float clamp, float* sdf, void* ws, size_t ws_bytes, hipStream_t s) {
-  MultiPlan p;
-  MultiWs w;
-  int rc = multi_prologue(ctx, nseg, counts, latent, latent_stride, xyz && sdf, ws, ws_bytes, false, s, p, w);
-  if (rc || p.ntot == 0) return rc;
-  MarchArgs A;
-  memset(&A, 0, sizeof(A));
-  A.xyz = xyz; A.sdf_out = sdf; A.c0c4 = w.c0c4; A.seg = w.tab; A.clamp = clamp;
-  MarchTimer timer(ctx, s);
-  timer.begin();
-  rc = launch_march(ctx, "k_march<eval, segments>", MODE_EVAL, 2, false, 0, wide_decoder(ctx), p.tiles, s, A);
-  timer.end();
-  return rc;
-}
-
-// its backward (distr_mlp_backward_multi, distr_depth_samples_backward): g_xyz and / or one g_latent row per segment
-int mlp_backward_multi_impl(distr_ctx* ctx, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride, const float* xyz,
-                            const float* g_sdf, float clamp, float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, hipStream_t s) {
-  MultiPlan p;
-  MultiWs w;
-  int rc = multi_prologue(ctx, nseg, counts, latent, latent_stride, xyz && g_sdf, ws, ws_bytes, true, s, p, w);
-  if (rc) return rc;
-  if (p.ntot == 0) {
-    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * ctx->D.nlat * sizeof(float), s));
-    return DISTR_OK;
-  }
-  BwdArgs B;
-  memset(&B, 0, sizeof(B));
-  B.xyz = xyz; B.c0c4 = w.c0c4; B.seg = w.tab; B.coef = g_sdf; B.clamp = clamp; B.partial = w.partial; B.out_g = g_xyz;
-  if ((rc = launch_bwd(ctx, "k_bwd<pointgrad+latent, segments>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), p.tiles, s, B))) return rc;
-  if (g_latent) {
-    hipLaunchKernelGGL(k_points_latent_grad, dim3((unsigned)nseg), dim3(256), 0, s, (const float*)w.partial, 0, ctx->D, g_latent, (const SegTable*)w.tab);
-    LAUNCH_CHECK("k_points_latent_grad<segments>");
-  }
-  return DISTR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t distr_mlp_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
-  MultiPlan p;
-  return multi_plan(nullptr, nseg, counts_host, p) == DISTR_OK ? multi_ws(nullptr, nseg, p, false).bytes : 0;
-}
-
-size_t distr_mlp_backward_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
-  MultiPlan p;
-  return multi_plan(nullptr, nseg, counts_host, p) == DISTR_OK ? multi_ws(nullptr, nseg, p, true).bytes : 0;
-}
-
-int distr_mlp_eval_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride, const float* xyz,
-                         float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  return mlp_eval_multi_impl(ctx, nseg, counts_host, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, (hipStream_t)stream);
+  PointList pl;
+  if (int rc = sdf_plain_list(ctx, n, pl)) return rc;
+  return mlp_grad_list(ctx, pl, latent, 0, xyz, sdf, grad, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_mlp_grad_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride, const float* xyz,
                          float* sdf, float* grad, void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  MultiPlan p;
-  MultiWs w;
-  const int rc = multi_prologue(ctx, nseg, counts_host, latent, latent_stride, xyz && sdf && grad, ws, ws_bytes, false, s, p, w);
-  if (rc || p.ntot == 0) return rc;
-  BwdArgs B;
-  memset(&B, 0, sizeof(B));
-  B.xyz = xyz; B.c0c4 = w.c0c4; B.seg = w.tab; B.out_sdf = sdf; B.out_g = grad;
-  return launch_bwd(ctx, "k_bwd<pointgrad, segments>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), p.tiles, s, B);
+  PointList pl;
+  if (int rc = sdf_seg_list(ctx, nseg, counts_host, latent_stride, pl)) return rc;
+  return mlp_grad_list(ctx, pl, latent, latent_stride, xyz, sdf, grad, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int distr_mlp_backward(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, const float* g_sdf, float clamp,
+                       float* g_xyz, float* g_latent, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  PointList pl;
+  if (int rc = sdf_plain_list(ctx, n, pl)) return rc;
+  return mlp_backward_list(ctx, pl, latent, 0, xyz, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_mlp_backward_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
@@ -1469,7 +1444,9 @@ int distr_mlp_backward_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts
                              void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
-  return mlp_backward_multi_impl(ctx, nseg, counts_host, latent, latent_stride, xyz, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
+  PointList pl;
+  if (int rc = sdf_seg_list(ctx, nseg, counts_host, latent_stride, pl)) return rc;
+  return mlp_backward_list(ctx, pl, latent, latent_stride, xyz, g_sdf, clamp, g_xyz, g_latent, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, int layer, float* out, void* ws,
@@ -1478,11 +1455,12 @@ int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz,
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
   if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
+  if (n == 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");      // (no empty list here: there is nothing to look at)
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4;
-  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n <= 0 || !xyz || !out || !latent || !ws || layer < 0 || layer > 7), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  PointList pl = plain_list(n);
+  const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, n > 0 && xyz && out && layer >= 0 && layer <= 7, ws, ws_bytes, false, s);
   if (rc) return rc;
-  hipLaunchKernelGGL((k_debug_layer<2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, layer, out, ctx->D, (long long*)nullptr);
+  hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, layer, out, ctx->D, (long long*)nullptr);
   LAUNCH_CHECK("k_debug_layer");
   return DISTR_OK;
 }
@@ -1493,11 +1471,12 @@ int distr_debug_tile_timing(distr_ctx* ctx, const float* latent, const float* xy
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
   if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
+  if (n == 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");      // (no empty list here: there is nothing to look at)
   hipStream_t s = (hipStream_t)stream;
-  float* c0c4;
-  const int rc = point_list_prologue(ctx, ctx->D, latent, n, !(n <= 0 || !xyz || !sdf_out || !ts_out || !latent || !ws), ws, ws_bytes, distr_mlp_workspace_bytes(n), s, &c0c4);
+  PointList pl = plain_list(n);
+  const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, n > 0 && xyz && sdf_out && ts_out, ws, ws_bytes, false, s);
   if (rc) return rc;
-  hipLaunchKernelGGL((k_debug_layer<2>), dim3((unsigned)((n + 63) / 64)), dim3(NTHREADS), 0, s, xyz, n, (const float*)c0c4, 8, sdf_out, ctx->D, ts_out);
+  hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, 8, sdf_out, ctx->D, ts_out);
   LAUNCH_CHECK("k_debug_layer<timing>");
   return DISTR_OK;
 }
@@ -2023,11 +2002,11 @@ int distr_depth_samples_forward(distr_ctx* ctx, const distr_samples_cfg* cfg, in
   const dim3 grid((unsigned)((p.nmax + samples::MB - 1) / samples::MB), (unsigned)nviews);
   hipLaunchKernelGGL(samples::k_samp_points, grid, dim3(samples::MB), 0, s, p.G, p.VW, index, RT, depth, normal, draws, xyz);
   LAUNCH_CHECK("k_samp_points");
-  if (latent_stride == 0 || nviews == 1) {
-    if (int rc = mlp_eval_impl(ctx, latent, xyz, L, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
-  } else {           // a code per view: one segmented evaluation, a segment (with tiles of its own) per view
-    if (int rc = mlp_eval_multi_impl(ctx, nviews, p.seg, latent, latent_stride, xyz, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
+  PointList pl = plain_list(L);
+  if (latent_stride != 0 && nviews > 1) {           // a code per view: one segmented evaluation, a segment (with tiles of its own) per view
+    if (int rc = seg_list(ctx, nviews, p.seg, pl)) return rc;
   }
+  if (int rc = mlp_eval_list(ctx, pl, latent, pl.nseg ? latent_stride : 0, xyz, cfg->clamp_dist, out, ws, ws_bytes, s)) return rc;
   if (p.G.mode == DISTR_SAMPLES_SURFACE) {
     hipLaunchKernelGGL(samples::k_samp_epilogue, grid, dim3(samples::MB), 0, s, p.VW, draws, out);
     LAUNCH_CHECK("k_samp_epilogue");
@@ -2052,8 +2031,9 @@ int distr_depth_samples_backward(distr_ctx* ctx, const distr_samples_cfg* cfg, i
   const SampBwdWs w = samp_bwd_ws(ws, p);
   // one segmented point-list backward, a segment per view: every view keeps the tiles and the reduction order of its stand-alone call
   if (p.ntot > 0 || g_latent) {
-    if (int rc = mlp_backward_multi_impl(ctx, nviews, p.seg, latent, latent_stride, xyz, g_out, cfg->clamp_dist, g_RT ? w.g_xyz : nullptr, g_latent,
-                                         w.mlp, w.mlp_bytes, s))
+    PointList pl;
+    if (int rc = seg_list(ctx, nviews, p.seg, pl)) return rc;
+    if (int rc = mlp_backward_list(ctx, pl, latent, latent_stride, xyz, g_out, cfg->clamp_dist, g_RT ? w.g_xyz : nullptr, g_latent, w.mlp, w.mlp_bytes, s))
       return rc;
   }
   if (g_RT) {

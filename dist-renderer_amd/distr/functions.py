@@ -28,25 +28,38 @@ def _check_eval(module):
 
 
 class DecoderEngine(object):
-    """Packed decoder on one device (distr_ctx). One per (decoder module, device)."""
+    """Packed decoder on one device (distr_ctx). One per (decoder module, device); `weights=(Ws, bs)` instead of a module: an engine
+    straight from numpy weights, never re-synchronised."""
 
-    def __init__(self, decoder, device_index):
+    def __init__(self, decoder=None, device_index=0, weights=None):
         self.ctx = binding.Context(device_index)
         self.device = torch.device('cuda', device_index)
         self._key = None
-        self.refresh(decoder)
+        self.generation = 0    # number of weight uploads so far: a forward remembers it, its backward refuses to run on newer weights
+        self._f16_state = {'gen': None, 'n': 0}      # _check_f16_range: the upload last checked, renders since
+        if weights is None:
+            self.refresh(decoder)
+        else:
+            self._upload(*self._flatten(*weights))
 
-    generation = 0     # number of weight uploads so far: a forward remembers it, its backward refuses to run on newer weights
+    _pack = staticmethod(decoder_pack.pack_module_sized)
 
-    latent_size = 256  # code length C of the uploaded decoder: every latent buffer of this engine has C entries per view
+    @staticmethod
+    def _flatten(Ws, bs):
+        return decoder_pack.flatten(Ws, bs), decoder_pack.latent_size_of(Ws)
+
+    def _set(self, flat, nlat):
+        self.ctx.set_decoder(flat, nlat)
+
+    def _upload(self, flat, nlat):
+        self._set(flat, nlat)
+        self.latent_size = nlat     # code length C of the uploaded decoder: every latent buffer of this engine has C entries per view
+        self.generation += 1
 
     def refresh(self, decoder):
         """(Re)uploads the weights."""
-        flat, nlat = decoder_pack.pack_module_sized(decoder)
-        self.ctx.set_decoder(flat, nlat)
-        self.latent_size = nlat
+        self._upload(*self._pack(decoder))
         self._key = _param_key(decoder)
-        self.generation += 1
 
     def sync(self, decoder):
         """The reference reads the live module on every call (decoder_utils.py:53-74); the packed copy follows it: re-packed
@@ -57,25 +70,33 @@ class DecoderEngine(object):
         return self
 
 
-_engines = weakref.WeakKeyDictionary()
+class ColorEngine(DecoderEngine):
+    """Packed colour decoder on one device (decode_color / SDFRenderer_color, SURVEY.md row f4)."""
+    _pack = staticmethod(decoder_pack.pack_color_module)
+    _flatten = staticmethod(decoder_pack.flatten_color)
+
+    def _set(self, flat, nlat):
+        self.ctx.set_color_decoder(flat, nlat)
 
 
-def get_engine(decoder, device_index):
-    per_dec = _engines.setdefault(decoder, {})
+_engines = {DecoderEngine: weakref.WeakKeyDictionary(), ColorEngine: weakref.WeakKeyDictionary()}
+
+
+def get_engine(decoder, device_index, kind=DecoderEngine):
+    per_dec = _engines[kind].setdefault(decoder, {})
     if device_index not in per_dec:
         _check_eval(decoder)
-        per_dec[device_index] = DecoderEngine(decoder, device_index)
+        per_dec[device_index] = kind(decoder, device_index)
     return per_dec[device_index].sync(decoder)
+
+
+def get_color_engine(decoder_color, device_index):
+    return get_engine(decoder_color, device_index, ColorEngine)
 
 
 def engine_from_weights(Ws, bs, device_index=0):
     """Engine straight from numpy weights (tests / bench; no nn.Module needed)."""
-    eng = DecoderEngine.__new__(DecoderEngine)
-    eng.ctx = binding.Context(device_index)
-    eng.device = torch.device('cuda', device_index)
-    eng.ctx.set_decoder(decoder_pack.flatten(Ws, bs), decoder_pack.latent_size_of(Ws))
-    eng.latent_size = decoder_pack.latent_size_of(Ws)
-    return eng
+    return DecoderEngine(device_index=device_index, weights=(Ws, bs))
 
 
 def check_split_arith(engine, arith):
@@ -94,57 +115,43 @@ def _code(engine, latent, dev, views=False):
     return lat.reshape(-1, C) if views else lat.reshape(-1)
 
 
-class ColorEngine(object):
-    """Packed colour decoder on one device (decode_color / SDFRenderer_color, SURVEY.md row f4)."""
-
-    def __init__(self, decoder_color=None, device_index=0, weights=None):
-        self.ctx = binding.Context(device_index)
-        self.device = torch.device('cuda', device_index)
-        self._key = None
-        if weights is None:
-            self.refresh(decoder_color)
-        else:
-            flat, nlat = decoder_pack.flatten_color(*weights)
-            self.latent_size = nlat
-            self.ctx.set_color_decoder(flat, nlat)
-
-    def refresh(self, decoder_color):
-        flat, nlat = decoder_pack.pack_color_module(decoder_color)
-        self.latent_size = nlat
-        self.ctx.set_color_decoder(flat, nlat)
-        self._key = _param_key(decoder_color)
-
-    def sync(self, decoder_color):
-        _check_eval(decoder_color)
-        if _param_key(decoder_color) != self._key:
-            self.refresh(decoder_color)
-        return self
+def _point_list(engine, latent, points, color_code=None):
+    """(code, points (n, 3), n) of a plain point-list call as f32 device buffers; with color_code the colour decoder's input
+    [shape_code | color_code] (decoder_utils.py:101-103)."""
+    dev = engine.device
+    if color_code is None:
+        lat = _code(engine, latent, dev)
+    else:
+        lat = torch.cat([_f32c(latent, dev).reshape(-1), _f32c(color_code, dev).reshape(-1)])
+        if lat.numel() != engine.latent_size:
+            raise ValueError('shape code + colour code have %d entries, the colour decoder expects %d' % (lat.numel(), engine.latent_size))
+    x = _f32c(points, dev).reshape(-1, 3)
+    return lat, x, x.shape[0]
 
 
-_color_engines = weakref.WeakKeyDictionary()
+def _ws(engine, size_fn, *args):
+    """Workspace of size_fn(*args) bytes on the engine's device."""
+    return torch.empty(size_fn(*args), dtype=torch.uint8, device=engine.device)
 
 
-def get_color_engine(decoder_color, device_index):
-    per_dec = _color_engines.setdefault(decoder_color, {})
-    if device_index not in per_dec:
-        _check_eval(decoder_color)
-        per_dec[device_index] = ColorEngine(decoder_color, device_index)
-    return per_dec[device_index].sync(decoder_color)
+def _list_call(engine, fn, size_fn, lat, x, n, *mid):
+    """fn(handle, code, points, n, *mid (tensors as pointers), workspace of size_fn(n) bytes, its size, stream), checked."""
+    ws = _ws(engine, size_fn, n)
+    mid = [binding.ptr(a) if a is None or torch.is_tensor(a) else a for a in mid]
+    engine.ctx.check(fn(engine.ctx.h, binding.ptr(lat), binding.ptr(x), n, *mid, binding.ptr(ws), ws.numel(), engine.ctx.stream()))
+
+
+def _clamp_arg(clamp_dist):
+    return -1.0 if clamp_dist is None else float(clamp_dist)
 
 
 def color_eval(engine, color_code, shape_code, points):
     """decode_color forward (core/utils/decoder_utils.py:94-112): points (n,3) -> rgb (n,3); the decoder input is
     [shape_code | color_code | xyz] (decoder_utils.py:101-103)."""
-    dev = engine.device
-    lat = torch.cat([_f32c(shape_code, dev).reshape(-1), _f32c(color_code, dev).reshape(-1)])
-    if lat.numel() != engine.latent_size:
-        raise ValueError('shape code + colour code have %d entries, the colour decoder expects %d' % (lat.numel(), engine.latent_size))
-    x = _f32c(points, dev).reshape(-1, 3)
-    n = x.shape[0]
-    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    ws = torch.empty(engine.ctx.L.distr_mlp_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_color_eval(engine.ctx.h, p(lat), p(x), n, p(out), p(ws), ws.numel(), engine.ctx.stream()))
+    L = engine.ctx.L
+    lat, x, n = _point_list(engine, shape_code, points, color_code)
+    out = torch.empty(n, 3, dtype=torch.float32, device=engine.device)
+    _list_call(engine, L.distr_color_eval, L.distr_mlp_workspace_bytes, lat, x, n, out)
     return out
 
 
@@ -164,17 +171,13 @@ class ColorDecodeFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         engine = ctx.engine
-        dev = engine.device
+        dev, L = engine.device, engine.ctx.L
         color_code, shape_code, points = ctx.saved_tensors
-        lat = torch.cat([_f32c(shape_code, dev).reshape(-1), _f32c(color_code, dev).reshape(-1)])
-        x = _f32c(points, dev).reshape(-1, 3)
-        n = x.shape[0]
+        lat, x, n = _point_list(engine, shape_code, points, color_code)
         gs = _f32c(g, dev).reshape(-1, 3)
         g_x = torch.empty(n, 3, dtype=torch.float32, device=dev) if ctx.need[2] else None
         g_l = torch.empty(engine.latent_size, dtype=torch.float32, device=dev) if (ctx.need[0] or ctx.need[1]) else None
-        ws = torch.empty(engine.ctx.L.distr_mlp_backward_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        p = binding.ptr
-        engine.ctx.check(engine.ctx.L.distr_color_backward(engine.ctx.h, p(lat), p(x), n, p(gs), p(g_x), p(g_l), p(ws), ws.numel(), engine.ctx.stream()))
+        _list_call(engine, L.distr_color_backward, L.distr_mlp_backward_workspace_bytes, lat, x, n, gs, g_x, g_l)
         ns = shape_code.numel()
         return ((g_l[ns:].reshape(color_code.shape) if ctx.need[0] else None), (g_l[:ns].reshape(shape_code.shape) if ctx.need[1] else None),
                 (g_x.reshape(points.shape) if ctx.need[2] else None), None)
@@ -192,7 +195,7 @@ def _check_generation(ctx):
     """A backward must run on the decoder weights its forward used: the saved ReLU masks (and every selected row) belong to THAT
     evaluation. Rendering A, updating the decoder, rendering B, then back-propagating A would silently mix new weights with old
     masks -- refuse instead."""
-    if getattr(ctx.engine, 'generation', 0) != ctx.generation:
+    if ctx.engine.generation != ctx.generation:
         raise RuntimeError('the decoder weights were re-uploaded (load_state_dict / optimiser step / refresh) between this render\'s '
                            'forward and its backward; back-propagate before changing the decoder, or render again')
 
@@ -213,8 +216,7 @@ def _check_f16_range(engine, cfg, ws, nviews=1, view_bytes=0, needs_grad=False):
         return
     import os
     every = int(os.environ.get('DISTR_F16_CHECK_EVERY', F16_CHECK_EVERY))
-    gen = getattr(engine, 'generation', 0)
-    st = engine.__dict__.setdefault('_f16_state', {'gen': None, 'n': 0})
+    gen, st = engine.generation, engine._f16_state
     first = st['gen'] != gen
     if first:
         st['gen'], st['n'] = gen, 0
@@ -229,81 +231,27 @@ def _check_f16_range(engine, cfg, ws, nviews=1, view_bytes=0, needs_grad=False):
                                  "render is not to be trusted. Use arith='bf16x6' or 'f32' for this decoder / shape code." % bad)
 
 
-class RenderFunction(torch.autograd.Function):
-    """(latent, R, T) -> (zdepth[P], mask[P] uint8, min_sdf[P], depth[H,W], normal[H,W,3])"""
-
-    @staticmethod
-    def forward(ctx, latent, R, T, engine, cfg):
-        dev = engine.device
-        H, W = cfg.band_rows, cfg.W
-        P = H * W
-        lat, Rc, Tc = _code(engine, latent, dev), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
-        if Rc.numel() != 9 or Tc.numel() != 3:
-            raise ValueError('expected latent (1,%d), R (3,3), T (3)' % engine.latent_size)
-        fwd_bytes, bwd_bytes = engine.ctx.workspace_bytes(cfg)
-        ws = torch.empty(fwd_bytes, dtype=torch.uint8, device=dev)
-        zdepth = torch.empty(P, dtype=torch.float32, device=dev)
-        mask = torch.empty(P, dtype=torch.uint8, device=dev)
-        min_sdf = torch.empty(P, dtype=torch.float32, device=dev)
-        if cfg.want_normal:
-            depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-            normal = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
-        else:
-            depth = torch.empty(0, dtype=torch.float32, device=dev)
-            normal = torch.empty(0, dtype=torch.float32, device=dev)
-        p = binding.ptr
-        engine.ctx.check(engine.ctx.L.distr_render_forward(
-            engine.ctx.h, C.byref(cfg), p(lat), p(Rc), p(Tc), p(zdepth), p(mask), p(min_sdf),
-            p(depth) if cfg.want_normal else None, p(normal) if cfg.want_normal else None,
-            p(ws), ws.numel(), engine.ctx.stream()))
-        _check_f16_range(engine, cfg, ws, needs_grad=any(ctx.needs_input_grad[:3]))
-        ctx.engine, ctx.cfg, ctx.ws, ctx.bwd_bytes = engine, cfg, ws, bwd_bytes
-        ctx.generation = getattr(engine, 'generation', 0)
-        ctx.shapes = (latent.shape, R.shape, T.shape)
-        ctx.in_meta = tuple((t.device, t.dtype) for t in (latent, R, T))
-        ctx.mark_non_differentiable(mask)
-        return zdepth, mask, min_sdf, depth, normal
-
-    @staticmethod
-    def backward(ctx, g_zdepth, g_mask, g_min_sdf, g_depth, g_normal):
-        engine, cfg, ws = ctx.engine, ctx.cfg, ctx.ws
-        _check_generation(ctx)
-        dev = engine.device
-
-        def prep(g, n):
-            if g is None or g.numel() != n:
-                return None
-            return g.to(dtype=torch.float32).contiguous()
-        P = cfg.band_rows * cfg.W
-        gz, gq = prep(g_zdepth, P), prep(g_min_sdf, P)
-        gd, gn = (prep(g_depth, P), prep(g_normal, 3 * P)) if cfg.want_normal else (None, None)
-        g_lat = torch.empty(engine.latent_size, dtype=torch.float32, device=dev)
-        g_R = torch.empty(9, dtype=torch.float32, device=dev)
-        g_T = torch.empty(3, dtype=torch.float32, device=dev)
-        ws_b = torch.empty(ctx.bwd_bytes, dtype=torch.uint8, device=dev)
-        p = binding.ptr
-        engine.ctx.check(engine.ctx.L.distr_render_backward(
-            engine.ctx.h, C.byref(cfg), p(ws), ws.numel(), p(gz), p(gq), p(gd), p(gn), p(g_lat), p(g_R), p(g_T),
-            p(ws_b), ws_b.numel(), engine.ctx.stream()))
-        ctx.last_ws = ws
-        ls, rs, ts = ctx.shapes
-        # gradients go back in the inputs' own device / dtype (a host-resident or f64 camera tensor keeps working)
-        return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None)
+def _single_view(engine, latent, R, T):
+    """The single-view calls take one code and one camera: ValueError naming (1, C), (3,3), (3) otherwise."""
+    if latent.numel() != engine.latent_size:
+        raise ValueError('latent has shape %s; this decoder takes (1, %d)' % (tuple(latent.shape), engine.latent_size))
+    if R.numel() != 9 or T.numel() != 3:
+        raise ValueError('expected latent (1,%d), R (3,3), T (3)' % engine.latent_size)
 
 
-def render_call(engine, cfg, latent, R, T):
-    # inference (torch.no_grad() or no input requires grad): skip saving the ReLU masks for the backward pass
-    need_bwd = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in (latent, R, T))
-    cfg = cfg.clone()          # the autograd node keeps ITS cfg: a caller reusing one cfg object for a later no-grad render must
-    cfg.save_for_backward = 1 if need_bwd else 0      # not flip save_for_backward under a pending backward
-    return RenderFunction.apply(latent, R, T, engine, cfg)
+def _grad_arg(g, n):
+    """Upstream gradient of a render output as the backward kernels read it; None for an output that was not produced."""
+    if g is None or g.numel() != n:
+        return None
+    return g.to(dtype=torch.float32).contiguous()
 
 
 class RenderBatchFunction(torch.autograd.Function):
     """Several views in one launch sequence (distr_render_forward_batch): (latent (1,C) shared by all views or (B,C), R (B,3,3),
-    T (B,3)) -> (zdepth (B,P), mask (B,P) uint8, min_sdf (B,P), depth (B,H,W), normal (B,H,W,3)). Every view's values and
-    gradients are bit-identical to its own RenderFunction call; what changes is the schedule (one march launch per step for all
-    views: the views' latency-bound tails overlap). `view_flags`: per-view DISTR_VIEW_GRAD_* (the no_grad_* options of each view)."""
+    T (B,3)) -> (zdepth (B,P), mask (B,P) uint8, min_sdf (B,P), depth (B,H,W), normal (B,H,W,3)). The one render node: render_call is
+    B = 1. Every view's values and gradients are bit-identical to its own B = 1 call; what changes is the schedule (one march launch
+    per step for all views: the views' latency-bound tails overlap). `view_flags`: per-view DISTR_VIEW_GRAD_* (the no_grad_* options of
+    each view)."""
 
     @staticmethod
     def forward(ctx, latent, R, T, engine, cfg, view_flags):
@@ -335,7 +283,7 @@ class RenderBatchFunction(torch.autograd.Function):
             p(depth) if cfg.want_normal else None, p(normal) if cfg.want_normal else None, p(ws), ws.numel(), engine.ctx.stream()))
         _check_f16_range(engine, cfg, ws, B, fwd_bytes, needs_grad=any(ctx.needs_input_grad[:3]))
         ctx.engine, ctx.cfg, ctx.ws, ctx.bwd_bytes, ctx.B, ctx.shared = engine, cfg, ws, bwd_bytes, B, shared
-        ctx.generation = getattr(engine, 'generation', 0)
+        ctx.generation = engine.generation
         ctx.shapes = (latent.shape, R.shape, T.shape)
         ctx.in_meta = tuple((t.device, t.dtype) for t in (latent, R, T))
         ctx.view_bytes = fwd_bytes
@@ -347,14 +295,9 @@ class RenderBatchFunction(torch.autograd.Function):
         engine, cfg, ws, B = ctx.engine, ctx.cfg, ctx.ws, ctx.B
         _check_generation(ctx)
         dev = engine.device
-
-        def prep(g, n):
-            if g is None or g.numel() != n:
-                return None
-            return g.to(dtype=torch.float32).contiguous()
         P = cfg.band_rows * cfg.W
-        gz, gq = prep(g_zdepth, B * P), prep(g_min_sdf, B * P)
-        gd, gn = (prep(g_depth, B * P), prep(g_normal, 3 * B * P)) if cfg.want_normal else (None, None)
+        gz, gq = _grad_arg(g_zdepth, B * P), _grad_arg(g_min_sdf, B * P)
+        gd, gn = (_grad_arg(g_depth, B * P), _grad_arg(g_normal, 3 * B * P)) if cfg.want_normal else (None, None)
         g_lat = torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev)
         g_R = torch.empty(B, 9, dtype=torch.float32, device=dev)
         g_T = torch.empty(B, 3, dtype=torch.float32, device=dev)
@@ -364,7 +307,7 @@ class RenderBatchFunction(torch.autograd.Function):
             engine.ctx.h, C.byref(cfg), B, p(ws), ws.numel(), p(gz), p(gq), p(gd), p(gn), p(g_lat), p(g_R), p(g_T),
             p(ws_b), ws_b.numel(), engine.ctx.stream()))
         ls, rs, ts = ctx.shapes
-        if ctx.shared:
+        if ctx.shared and B > 1:
             g_lat = g_lat.sum(0)                   # one shape code rendered from B cameras: the views' gradients add up (fixed order)
         return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None, None)
 
@@ -375,6 +318,16 @@ def render_batch_call(engine, cfg, latent, R, T, view_flags=None):
     cfg = cfg.clone()
     cfg.save_for_backward = 1 if need_bwd else 0
     return RenderBatchFunction.apply(latent, R, T, engine, cfg, view_flags)
+
+
+def render_call(engine, cfg, latent, R, T):
+    """One view: latent (1,C), R (3,3), T (3) -> (zdepth (P), mask (P) uint8, min_sdf (P), depth (H,W), normal (H,W,3))."""
+    _single_view(engine, latent, R, T)
+    H, W = cfg.band_rows, cfg.W
+    z, mask, q, depth, normal = render_batch_call(engine, cfg, latent, R, T)
+    if cfg.want_normal:
+        depth, normal = depth.reshape(H, W), normal.reshape(H, W, 3)
+    return z.reshape(-1), mask.reshape(-1), q.reshape(-1), depth, normal
 
 
 def render_normal_batch_call(engine, cfg, latent, R, T, zdepth, mask):
@@ -434,18 +387,8 @@ def render_normal_call(engine, cfg, latent, R, T, zdepth, mask):
     """SDFRenderer.render_normal forward (renderer.py:880-910) -> (3, P). Gradient-free: for ReLU decoders the
     normalised SDF gradient is piecewise constant in (latent, point), its autograd contribution is identically ~0
     (SURVEY.md A.6-1)."""
-    dev = engine.device
-    P = cfg.band_rows * cfg.W
-    lat, Rc, Tc = _code(engine, latent, dev), _f32c(R, dev).reshape(-1), _f32c(T, dev).reshape(-1)
-    z = _f32c(zdepth, dev).reshape(-1)
-    m = mask.detach().to(device=dev).reshape(-1).to(torch.uint8).contiguous()
-    fwd_bytes, _ = engine.ctx.workspace_bytes(cfg)
-    ws = torch.empty(fwd_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(3, P, dtype=torch.float32, device=dev)
-    p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_render_normal(engine.ctx.h, C.byref(cfg), p(lat), p(Rc), p(Tc), p(z), p(m), p(out),
-                                                      p(ws), ws.numel(), engine.ctx.stream()))
-    return out
+    _single_view(engine, latent, R, T)
+    return render_normal_batch_call(engine, cfg, latent, R, T, zdepth, mask)[0]
 
 
 def mlp_eval(engine, latent, points, clamp_dist=None, arith='f32'):
@@ -456,16 +399,11 @@ def mlp_eval(engine, latent, points, clamp_dist=None, arith='f32'):
     if arith not in binding.ARITH:
         raise ValueError("arith must be one of %s" % sorted(binding.ARITH))
     check_split_arith(engine, arith)
-    dev = engine.device
-    lat = _code(engine, latent, dev)
-    x = _f32c(points, dev).reshape(-1, 3)
-    n = x.shape[0]
-    out = torch.empty(n, 1, dtype=torch.float32, device=dev)
-    ws = torch.empty(engine.ctx.L.distr_mlp_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    p = binding.ptr
-    fn = {'f32': engine.ctx.L.distr_mlp_eval, 'bf16x6': engine.ctx.L.distr_mlp_eval_bf16x6, 'f16x3': engine.ctx.L.distr_mlp_eval_f16x3}[arith]
-    engine.ctx.check(fn(engine.ctx.h, p(lat), p(x), n, -1.0 if clamp_dist is None else float(clamp_dist), p(out), p(ws), ws.numel(),
-                        engine.ctx.stream()))
+    L = engine.ctx.L
+    lat, x, n = _point_list(engine, latent, points)
+    out = torch.empty(n, 1, dtype=torch.float32, device=engine.device)
+    fn = {'f32': L.distr_mlp_eval, 'bf16x6': L.distr_mlp_eval_bf16x6, 'f16x3': L.distr_mlp_eval_f16x3}[arith]
+    _list_call(engine, fn, L.distr_mlp_workspace_bytes, lat, x, n, _clamp_arg(clamp_dist), out)
     return out
 
 
@@ -484,18 +422,13 @@ class DecodeSdfFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         engine = ctx.engine
-        dev = engine.device
+        dev, L = engine.device, engine.ctx.L
         latent, points = ctx.saved_tensors
-        lat = _code(engine, latent, dev)
-        x = _f32c(points, dev).reshape(-1, 3)
-        n = x.shape[0]
+        lat, x, n = _point_list(engine, latent, points)
         gs = _f32c(g, dev).reshape(-1)
         g_x = torch.empty(n, 3, dtype=torch.float32, device=dev) if ctx.need[1] else None
         g_l = torch.empty(engine.latent_size, dtype=torch.float32, device=dev) if ctx.need[0] else None
-        ws = torch.empty(engine.ctx.L.distr_mlp_backward_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        p = binding.ptr
-        engine.ctx.check(engine.ctx.L.distr_mlp_backward(engine.ctx.h, p(lat), p(x), n, p(gs), -1.0 if ctx.clamp is None else float(ctx.clamp),
-                                                        p(g_x), p(g_l), p(ws), ws.numel(), engine.ctx.stream()))
+        _list_call(engine, L.distr_mlp_backward, L.distr_mlp_backward_workspace_bytes, lat, x, n, gs, _clamp_arg(ctx.clamp), g_x, g_l)
         return (None if g_l is None else g_l.reshape(latent.shape)), (None if g_x is None else g_x.reshape(points.shape)), None, None
 
 
@@ -554,13 +487,9 @@ def _multi_run(engine, latents, points, counts, ws_bytes, outputs, call):
     ctx, p = engine.ctx, binding.ptr
     for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
         cnt = (C.c_int64 * ns)(*plan['counts'][s0:s0 + ns])
-        ws = torch.empty(ws_bytes(ns, cnt), dtype=torch.uint8, device=engine.device)
+        ws = _ws(engine, ws_bytes, ns, cnt)
         ctx.check(call((ctx.h, ns, cnt, p(lat[row:]), stride, p(x[p0:])), (p(ws), ws.numel(), ctx.stream()), p0, s0, out))
     return out
-
-
-def _clamp_arg(clamp_dist):
-    return -1.0 if clamp_dist is None else float(clamp_dist)
 
 
 def mlp_eval_multi(engine, latents, points, counts, clamp_dist=None):
@@ -727,45 +656,30 @@ def freespace_call(engine, cfg, latent, RT, depth, ratio, index, counts):
 
 def mlp_grad(engine, latent, points):
     """(sdf (n,), d sdf/d xyz (n,3)) of the unclamped decoder."""
-    dev = engine.device
-    lat = _code(engine, latent, dev)
-    x = _f32c(points, dev).reshape(-1, 3)
-    n = x.shape[0]
+    L, dev = engine.ctx.L, engine.device
+    lat, x, n = _point_list(engine, latent, points)
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
     g = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    ws = torch.empty(engine.ctx.L.distr_mlp_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_mlp_grad(engine.ctx.h, p(lat), p(x), n, p(sdf), p(g), p(ws), ws.numel(), engine.ctx.stream()))
+    _list_call(engine, L.distr_mlp_grad, L.distr_mlp_workspace_bytes, lat, x, n, sdf, g)
     return sdf, g
 
 
 def debug_mlp_layer(engine, latent, points, layer):
     """Test aid: post-activation of hidden layer `layer` -> (n,512)."""
-    dev = engine.device
-    lat = _code(engine, latent, dev)
-    x = _f32c(points, dev).reshape(-1, 3)
-    n = x.shape[0]
-    out = torch.empty(n, 512, dtype=torch.float32, device=dev)
-    ws = torch.empty(engine.ctx.L.distr_mlp_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_debug_mlp_layer(engine.ctx.h, p(lat), p(x), n, int(layer), p(out), p(ws), ws.numel(),
-                                                       engine.ctx.stream()))
+    L = engine.ctx.L
+    lat, x, n = _point_list(engine, latent, points)
+    out = torch.empty(n, 512, dtype=torch.float32, device=engine.device)
+    _list_call(engine, L.distr_debug_mlp_layer, L.distr_mlp_workspace_bytes, lat, x, n, int(layer), out)
     return out
 
 
 def debug_tile_timing(engine, latent, points, tile):
     """Test aid: (sdf (n,), stamps (tiles, 20, 2) int64 [shader clock, 100 MHz wall clock]) of the decoder tile phases."""
-    dev = engine.device
-    lat = _code(engine, latent, dev)
-    x = _f32c(points, dev).reshape(-1, 3)
-    n = x.shape[0]
-    tiles = (n + tile - 1) // tile
+    L, dev = engine.ctx.L, engine.device
+    lat, x, n = _point_list(engine, latent, points)
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
-    ts = torch.zeros(tiles, 20, 2, dtype=torch.int64, device=dev)
-    ws = torch.empty(engine.ctx.L.distr_mlp_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    p = binding.ptr
-    engine.ctx.check(engine.ctx.L.distr_debug_tile_timing(engine.ctx.h, p(lat), p(x), n, p(sdf), p(ts), p(ws), ws.numel(),
-                                                         engine.ctx.stream()))
+    ts = torch.zeros((n + tile - 1) // tile, 20, 2, dtype=torch.int64, device=dev)
+    _list_call(engine, L.distr_debug_tile_timing, L.distr_mlp_workspace_bytes, lat, x, n, sdf, ts)
     return sdf, ts
 
 
@@ -776,7 +690,7 @@ def _u8c(t, device):
 
 
 def _loss_ws(engine, H, W):
-    return torch.empty(engine.ctx.L.distr_loss_workspace_bytes(H, W), dtype=torch.uint8, device=engine.device)
+    return _ws(engine, engine.ctx.L.distr_loss_workspace_bytes, H, W)
 
 
 class SingleViewLossFunction(torch.autograd.Function):
