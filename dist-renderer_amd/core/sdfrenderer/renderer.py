@@ -27,10 +27,14 @@ class SDFRenderer(object):
     # reference: renderer.py:13
     def __init__(self, decoder, intrinsic, img_hw=None, transform_matrix=None, march_step=50, buffer_size=5,
                  ray_marching_ratio=1.5, use_depth2normal=False, max_sample_dist=0.2, radius=1.0, threshold=5e-5,
-                 scale_list=[4, 2, 1], march_step_list=[3, 3, -1], use_gpu=True, is_eval=True, arith=None):
+                 scale_list=[4, 2, 1], march_step_list=[3, 3, -1], use_gpu=True, is_eval=True, arith=None, normal_decoder_grad=False):
         # arith (not in the reference): 'f32' = exact f32 decoder evaluations (default); 'bf16x6' / 'f16x3' = the opt-in split-bf16 /
         # split-f16 march tiles (values within ~1e-6, 1.5x / 2x the step rate, no cluster tiles: for large dense renders; f16x3 only for
         # decoders inside the f16 range, see distr_render_stats.f16_overflows); None = default_arith(); also settable later (self.arith)
+        # normal_decoder_grad (not in the reference, where it is always on): render() also back-propagates a loss on raw autograd normals
+        # (normalize_normal=False) through the decoder's second path (decode_sdf_gradient with create_graph=True, decoder_utils.py:76-92),
+        # the term the backward omits by default (DESIGN.md sections 5 and 8d); also settable later (self.normal_decoder_grad)
+        self.normal_decoder_grad = bool(normal_decoder_grad)
         if arith is None:
             arith = default_arith()
         if arith not in binding.ARITH:
@@ -271,7 +275,9 @@ class SDFRenderer(object):
                         no_grad_camera=no_grad_camera)
         if profile:
             self._engine.ctx.profile_enable(True)
-        zdepth, mask, min_sdf, depth, normal = functions.render_call(self._engine, cfg, latent, R, T)
+        # (no_grad_normal detaches the normals inside render_normal, renderer.py:908-909: the decoder-path term goes with them)
+        zdepth, mask, min_sdf, depth, normal = functions.render_call(self._engine, cfg, latent, R, T,
+                                                                     normal_decoder_grad=self.normal_decoder_grad and not no_grad_normal)
         if profile:
             n, ms = self._engine.ctx.profile_read()
             self._engine.ctx.profile_enable(False)
@@ -283,8 +289,8 @@ class SDFRenderer(object):
         # The autograd normal of this build carries exactly that term and nothing else (the terms through the decoder are identically
         # ~0 for a ReLU decoder after normalisation), so the flag has nothing left to remove here. (Round 3 detached the
         # whole image, which also dropped the R term: found by G18.) With normalize_normal=False the decoder-path terms are not
-        # identically zero in the reference, but this build omits them BY DESIGN for both settings (the autograd normal is a
-        # gradient-free pass, render_normal: save_for_backward = 0), so the flag is a no-op there too.
+        # identically zero in the reference; this build returns them with normal_decoder_grad=True only, and then the flag switches them
+        # off again (above); by default they are omitted for both settings, so the flag is a no-op there too.
         if no_grad_mask and no_grad_camera:
             min_sdf = min_sdf.detach()
         if num_forward_sampling != 0:

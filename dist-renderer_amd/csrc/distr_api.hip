@@ -18,6 +18,7 @@
 #include "distr_mesh.hpp"
 #include "distr_mlp_b6.hpp"
 #include "distr_samples.hpp"
+#include "distr_normal_grad.hpp"
 
 using namespace distr;
 
@@ -2042,6 +2043,139 @@ int distr_depth_samples_backward(distr_ctx* ctx, const distr_samples_cfg* cfg, i
     LAUNCH_CHECK("k_samp_cam_bwd");
     hipLaunchKernelGGL(samples::k_samp_cam_fin, dim3((unsigned)nviews), dim3(samples::MB), 0, s, p.VW, RT, (const float*)w.part, p.nblk_cam, g_RT);
     LAUNCH_CHECK("k_samp_cam_fin");
+  }
+  return DISTR_OK;
+}
+
+}  // extern "C"
+
+// ---- normal-map losses through the decoder's second path (include/distr_normal_grad.h, kernels: distr_normal_grad.hpp)
+namespace {
+
+struct NgWs {
+  int *btot, *boff, *totals;
+  int32_t* index;
+  double* c64;               // [nviews][1024] lin0 / lin4 start values in float64 (k_ng_consts64)
+  float *xyz, *gf, *g_xyz, *part;
+  void* mlp;
+  size_t mlp_bytes, bytes;
+};
+
+struct NgPlan {
+  int nviews, P, nblk;       // nblk: blocks of MTILE pixels per view (count / compact / camera sums)
+  PointList pl;              // the segmented list at its capacity: a segment of P points per view (the table holds the real counts)
+};
+
+// what the term is defined for, before any pointer is looked at (the workspace size and the call refuse alike)
+int ng_plan(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, NgPlan& p) {
+  if (int rc = check_cfg(ctx, cfg)) return rc;
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
+  if (cfg->use_depth2normal) return fail(ctx, DISTR_ERR_INVALID_ARG, "normal decoder gradient: use_depth2normal renders have no autograd normals, the term does not exist");
+  if (!cfg->want_normal) return fail(ctx, DISTR_ERR_INVALID_ARG, "normal decoder gradient: the forward was run with want_normal=0");
+  if (!cfg->save_for_backward) return fail(ctx, DISTR_ERR_INVALID_ARG, "normal decoder gradient: the forward was run with save_for_backward=0");
+  if (cfg->rows != 0) return fail(ctx, DISTR_ERR_UNSUPPORTED, "normal decoder gradient: row bands (rows != 0) are not implemented");
+  if (cfg->arith != DISTR_ARITH_F32) return fail(ctx, DISTR_ERR_UNSUPPORTED, "normal decoder gradient: arith f32 only");
+  memset(&p, 0, sizeof(p));
+  p.nviews = nviews;
+  p.P = cfg->H * cfg->W;
+  p.nblk = (p.P + ngrad::MTILE - 1) / ngrad::MTILE;
+  int64_t cap[DISTR_MAX_VIEWS];
+  for (int v = 0; v < nviews; ++v) cap[v] = p.P;
+  return seg_list(ctx, nviews, cap, p.pl);         // (refuses more than 2^30 pixels in all)
+}
+
+NgWs ng_ws(void* base, NgPlan& p) {
+  WsCarve c(base);
+  NgWs w;
+  const size_t NP = (size_t)p.nviews * p.P;
+  w.btot = c.take<int>((size_t)p.nviews * p.nblk);
+  w.boff = c.take<int>((size_t)p.nviews * p.nblk);
+  w.totals = c.take<int>(DISTR_MAX_VIEWS);
+  w.index = c.take<int32_t>(NP);
+  w.c64 = c.take<double>((size_t)p.nviews * 2 * HID);
+  w.xyz = c.take<float>(3 * NP);
+  w.gf = c.take<float>(NP);
+  w.g_xyz = c.take<float>(3 * NP);
+  w.part = c.take<float>((size_t)p.nviews * p.nblk * 12);
+  w.mlp_bytes = carve_list(nullptr, p.pl, true);
+  w.mlp = c.take<char>(w.mlp_bytes);
+  w.bytes = c.bytes();
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int distr_render_normal_grad_workspace_bytes(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, size_t* bytes) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  NgPlan p;
+  if (int rc = ng_plan(ctx, cfg, nviews, p)) return rc;
+  if (!bytes) return fail(ctx, DISTR_ERR_INVALID_ARG, "null pointer");
+  *bytes = ng_ws(nullptr, p).bytes;
+  return DISTR_OK;
+}
+
+int distr_render_normal_grad_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const int32_t* view_flags,
+                                            const void* ws_fwd, size_t ws_fwd_bytes, const float* g_normal, float* g_latent, float* g_R,
+                                            float* g_T, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  NgPlan p;
+  if (int rc = ng_plan(ctx, cfg, nviews, p)) return rc;
+  ViewFlags vf;      // checked, not used: render_normal takes no no_grad_camera (renderer.py:881-882, 977)
+  if (int rc = make_view_flags(ctx, *cfg, nviews, view_flags, vf)) return rc;
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (!ws_fwd || !g_normal || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  View V;
+  const size_t single = make_view(*cfg, const_cast<void*>(ws_fwd), V, ctx->save_masks, nviews);
+  if (ws_fwd_bytes < single * nviews) return fail(ctx, DISTR_ERR_WORKSPACE, "forward workspace too small: %zu < %zu", ws_fwd_bytes, single * nviews);
+  if (ws_bytes < ng_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "normal decoder gradient: workspace too small: %zu < %zu", ws_bytes, ng_ws(nullptr, p).bytes);
+  hipStream_t s = (hipStream_t)stream;
+  const DecoderDev& D = ctx->D;
+  const unsigned NV = (unsigned)nviews;
+  if (cfg->normalize_normal) {      // unit normals are scale invariant: no term
+    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nviews * D.nlat * sizeof(float), s));
+    if (g_R) HIP_TRY(hipMemsetAsync(g_R, 0, (size_t)nviews * 9 * sizeof(float), s));
+    if (g_T) HIP_TRY(hipMemsetAsync(g_T, 0, (size_t)nviews * 3 * sizeof(float), s));
+    return DISTR_OK;
+  }
+  const NgWs w = ng_ws(ws, p);
+  carve_list(w.mlp, p.pl, true);
+  const dim3 gpx((unsigned)p.nblk, NV), gpt((unsigned)((p.P + ngrad::MB - 1) / ngrad::MB), NV), blk(ngrad::MB);
+  hipLaunchKernelGGL(ngrad::k_ng_count, gpx, blk, 0, s, V, p.nblk, w.btot);
+  LAUNCH_CHECK("k_ng_count");
+  hipLaunchKernelGGL(samples::k_samp_top_scan, dim3(NV), blk, 0, s, (const int*)w.btot, p.nblk, w.boff, w.totals);
+  LAUNCH_CHECK("k_samp_top_scan");
+  hipLaunchKernelGGL(ngrad::k_ng_compact, gpx, blk, 0, s, V, p.nblk, (const int*)w.boff, w.index);
+  LAUNCH_CHECK("k_ng_compact");
+  const ngrad::Lists L{w.index, w.totals, w.xyz, w.gf, w.g_xyz};
+  hipLaunchKernelGGL(ngrad::k_ng_gather, gpt, blk, 0, s, V, L, g_normal);
+  LAUNCH_CHECK("k_ng_gather");
+  hipLaunchKernelGGL(ngrad::k_ng_consts64, dim3(4, NV), dim3(256), 0, s, V, D, w.c64);
+  LAUNCH_CHECK("k_ng_consts64");
+  hipLaunchKernelGGL(ngrad::k_ng_f64, dim3((unsigned)((p.P + ngrad::FP - 1) / ngrad::FP), NV), dim3(256), 0, s, V, L, D, (const double*)w.c64,
+                     (int)wide_decoder(ctx));
+  LAUNCH_CHECK("k_ng_f64");
+  // one segmented point-list backward, a segment per view (also for one view: the same tiles either way). The latent constants come
+  // from the codes the forward saved (Consts::latent, a view every vstride bytes); the tile table from the counts on the device.
+  const float* codes = reinterpret_cast<const float*>(reinterpret_cast<const char*>(V.C) + offsetof(Consts, latent));
+  hipLaunchKernelGGL(k_latent_consts, dim3(4, NV), dim3(256), 0, s, p.pl.c0c4, D, codes, (int64_t)(V.vstride / (int64_t)sizeof(float)), (SegTable*)nullptr, p.pl.cnt);
+  LAUNCH_CHECK("k_latent_consts");
+  hipLaunchKernelGGL(ngrad::k_ng_seg_table, dim3(1), dim3(64), 0, s, (const int*)w.totals, nviews, p.P, p.pl.tab);
+  LAUNCH_CHECK("k_ng_seg_table");
+  BwdArgs B;
+  memset(&B, 0, sizeof(B));
+  B.xyz = w.xyz; B.c0c4 = p.pl.c0c4; B.seg = p.pl.tab; B.coef = w.gf; B.clamp = -1.0f; B.partial = p.pl.partial;
+  B.out_g = (g_R || g_T) ? w.g_xyz : nullptr;
+  if (int rc = launch_bwd(ctx, "k_bwd<pointgrad+latent>", BWD_POINTGRAD, 2, 0, wide_decoder(ctx), p.pl.tiles, s, B)) return rc;
+  if (int rc = list_latent_grad(ctx, D, p.pl, g_latent, s)) return rc;
+  if (g_R || g_T) {
+    hipLaunchKernelGGL(ngrad::k_ng_cam_bwd, gpx, blk, 0, s, V, L, p.nblk, w.part);
+    LAUNCH_CHECK("k_ng_cam_bwd");
+    hipLaunchKernelGGL(ngrad::k_ng_cam_fin, dim3(NV), blk, 0, s, V, (const int*)w.totals, (const float*)w.part, p.nblk, g_R, g_T);
+    LAUNCH_CHECK("k_ng_cam_fin");
   }
   return DISTR_OK;
 }

@@ -34,6 +34,8 @@ SAMPLES_EXPORTS = ['distr_depth_samples_workspace_bytes', 'distr_depth_samples_c
 # the decoder on a segmented point list (include/distr_multi.h, included by distr.h): many shape codes in one launch sequence
 MULTI_EXPORTS = ['distr_mlp_multi_workspace_bytes', 'distr_mlp_backward_multi_workspace_bytes', 'distr_mlp_eval_multi',
                  'distr_mlp_grad_multi', 'distr_mlp_backward_multi']
+# normal-map losses through the decoder's second path (include/distr_normal_grad.h, included by distr.h)
+NORMAL_GRAD_EXPORTS = ['distr_render_normal_grad_workspace_bytes', 'distr_render_normal_grad_backward_batch']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -131,8 +133,8 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h')                    # include/: the C ABI
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp')
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h')                    # include/: the C ABI
 INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -356,6 +358,9 @@ def lib():
             L.distr_mlp_eval_multi.argtypes = [vp, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp]
             L.distr_mlp_grad_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, fp, vp, C.c_size_t, vp]
             L.distr_mlp_backward_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, C.c_float, fp, fp, vp, C.c_size_t, vp]
+            L.distr_render_normal_grad_workspace_bytes.argtypes = [vp, C.POINTER(RenderCfg), i32, szp]
+            L.distr_render_normal_grad_backward_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, C.POINTER(C.c_int32), vp, C.c_size_t, fp, fp, fp, fp,
+                                                                  vp, C.c_size_t, vp]
             _lib = L
     return _lib
 
@@ -474,6 +479,11 @@ class Context(object):
         f, b = C.c_size_t(), C.c_size_t()
         self.check(self.L.distr_workspace_bytes(self.h, C.byref(cfg), C.byref(f), C.byref(b)))
         return f.value, b.value
+
+    def normal_grad_workspace_bytes(self, cfg, nviews):
+        n = C.c_size_t()
+        self.check(self.L.distr_render_normal_grad_workspace_bytes(self.h, C.byref(cfg), int(nviews), C.byref(n)))
+        return n.value
 
     def stream(self):
         import torch

@@ -251,10 +251,12 @@ class RenderBatchFunction(torch.autograd.Function):
     T (B,3)) -> (zdepth (B,P), mask (B,P) uint8, min_sdf (B,P), depth (B,H,W), normal (B,H,W,3)). The one render node: render_call is
     B = 1. Every view's values and gradients are bit-identical to its own B = 1 call; what changes is the schedule (one march launch
     per step for all views: the views' latency-bound tails overlap). `view_flags`: per-view DISTR_VIEW_GRAD_* (the no_grad_* options of
-    each view)."""
+    each view). `normal_decoder_grad`: the backward also returns the term of a normal-map loss that reaches code and camera through the
+    decoder (distr_render_normal_grad_backward_batch), added to the gradients of the main backward; without it every
+    byte is what it was before the option existed."""
 
     @staticmethod
-    def forward(ctx, latent, R, T, engine, cfg, view_flags):
+    def forward(ctx, latent, R, T, engine, cfg, view_flags, normal_decoder_grad=False):
         dev = engine.device
         H, W = cfg.band_rows, cfg.W
         P = H * W
@@ -287,6 +289,8 @@ class RenderBatchFunction(torch.autograd.Function):
         ctx.shapes = (latent.shape, R.shape, T.shape)
         ctx.in_meta = tuple((t.device, t.dtype) for t in (latent, R, T))
         ctx.view_bytes = fwd_bytes
+        ctx.flags = flags
+        ctx.normal_grad = bool(normal_decoder_grad) and normal_grad_applies(cfg)
         ctx.mark_non_differentiable(mask)
         return zdepth, mask, min_sdf, depth, normal
 
@@ -306,25 +310,58 @@ class RenderBatchFunction(torch.autograd.Function):
         engine.ctx.check(engine.ctx.L.distr_render_backward_batch(
             engine.ctx.h, C.byref(cfg), B, p(ws), ws.numel(), p(gz), p(gq), p(gd), p(gn), p(g_lat), p(g_R), p(g_T),
             p(ws_b), ws_b.numel(), engine.ctx.stream()))
+        if ctx.normal_grad and gn is not None:
+            # the decoder-path term of the normal-map loss: outputs of its own, added here (the main backward's reduction order stays)
+            n_lat, n_R, n_T = normal_grad_term(engine, cfg, ws, gn, B, ctx.flags)
+            g_lat, g_R, g_T = g_lat + n_lat, g_R + n_R, g_T + n_T
         ls, rs, ts = ctx.shapes
         if ctx.shared and B > 1:
             g_lat = g_lat.sum(0)                   # one shape code rendered from B cameras: the views' gradients add up (fixed order)
-        return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None, None)
+        return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None, None, None)
 
 
-def render_batch_call(engine, cfg, latent, R, T, view_flags=None):
-    """Batched render_call: R (B,3,3), T (B,3), latent (1,C) (shared) or (B,C)."""
+def normal_grad_term(engine, cfg, ws, g_normal, B, view_flags=None):
+    """distr_render_normal_grad_backward_batch on the saved forward workspace `ws` of B views: the decoder-path term of the upstream
+    gradient g_normal (B, H, W, 3) alone -> (g_latent (B, C), g_R (B, 9), g_T (B, 3)), one row per view."""
+    dev = engine.device
+    gn = _f32c(g_normal, dev)
+    if gn.numel() != 3 * B * cfg.band_rows * cfg.W:
+        raise ValueError('g_normal has %d entries for %d views of %d x %d x 3' % (gn.numel(), B, cfg.band_rows, cfg.W))
+    out = (torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev), torch.empty(B, 9, dtype=torch.float32, device=dev),
+           torch.empty(B, 3, dtype=torch.float32, device=dev))
+    ws_n = torch.empty(engine.ctx.normal_grad_workspace_bytes(cfg, B), dtype=torch.uint8, device=dev)
+    p = binding.ptr
+    engine.ctx.check(engine.ctx.L.distr_render_normal_grad_backward_batch(
+        engine.ctx.h, C.byref(cfg), B, view_flags, p(ws), ws.numel(), p(gn), p(out[0]), p(out[1]), p(out[2]), p(ws_n), ws_n.numel(),
+        engine.ctx.stream()))
+    return out
+
+
+def normal_grad_applies(cfg):
+    """The decoder-path term of a normal-map loss exists for raw autograd normals only: depth2normal renders have no decoder in their
+    normals, and unit normals are scale invariant (the term is zero: golden G27, *_unit cases)."""
+    return bool(cfg.want_normal) and not cfg.use_depth2normal and not cfg.normalize_normal
+
+
+def render_batch_call(engine, cfg, latent, R, T, view_flags=None, normal_decoder_grad=False):
+    """Batched render_call: R (B,3,3), T (B,3), latent (1,C) (shared) or (B,C). normal_decoder_grad: see RenderBatchFunction; where the
+    term is zero or absent (normal_grad_applies) the option does nothing."""
     need_bwd = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in (latent, R, T))
     cfg = cfg.clone()
     cfg.save_for_backward = 1 if need_bwd else 0
-    return RenderBatchFunction.apply(latent, R, T, engine, cfg, view_flags)
+    if normal_decoder_grad and normal_grad_applies(cfg):
+        if cfg.rows != 0:
+            raise NotImplementedError('normal_decoder_grad: row bands are not implemented (render the whole image)')
+        if cfg.arith != binding.ARITH['f32']:
+            raise NotImplementedError("normal_decoder_grad: arith='f32' only")
+    return RenderBatchFunction.apply(latent, R, T, engine, cfg, view_flags, bool(normal_decoder_grad))
 
 
-def render_call(engine, cfg, latent, R, T):
+def render_call(engine, cfg, latent, R, T, normal_decoder_grad=False):
     """One view: latent (1,C), R (3,3), T (3) -> (zdepth (P), mask (P) uint8, min_sdf (P), depth (H,W), normal (H,W,3))."""
     _single_view(engine, latent, R, T)
     H, W = cfg.band_rows, cfg.W
-    z, mask, q, depth, normal = render_batch_call(engine, cfg, latent, R, T)
+    z, mask, q, depth, normal = render_batch_call(engine, cfg, latent, R, T, normal_decoder_grad=normal_decoder_grad)
     if cfg.want_normal:
         depth, normal = depth.reshape(H, W), normal.reshape(H, W, 3)
     return z.reshape(-1), mask.reshape(-1), q.reshape(-1), depth, normal

@@ -371,5 +371,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_samples.h"
 /* the decoder on a segmented point list: many shape codes in one launch sequence */
 #include "distr_multi.h"
+/* normal-map losses through the decoder's second path: the term distr_render_backward omits, opt-in */
+#include "distr_normal_grad.h"
 
 #endif /* DISTR_H_ */
