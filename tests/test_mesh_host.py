@@ -1,6 +1,7 @@
 """CPU-only checks of shape evaluation: the mesh part of the C ABI (include/distr_mesh.h) against the binding, the numpy PLY writer /
-reader, and how core.evaluation resolves Evaluator / latent_vec_to_points / the chamfer functions with and without a reference
-checkout next to this build."""
+reader, how core.evaluation resolves Evaluator / latent_vec_to_points / the chamfer functions with and without a reference
+checkout next to this build, and the numpy restatements (tests/mesh_restatement.py) that tests/test_gpu_mesh.py compares the sampling
+and nearest-distance kernels with bit for bit: checked here against independent statements of the same thing."""
 import json
 import os
 import re
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG, ROOT
+import mesh_restatement as R
 
 
 def test_mesh_abi_declared_exported_and_checked():
@@ -135,3 +137,70 @@ def test_reference_checkout_evaluator_lands_on_this_build(tmp_path):
         assert j[k].startswith(ours), (k, j[k])
     assert j['ev.latent_vec_to_points'] == os.path.join(ours, 'evaluation', 'transforms.py')
     assert j['ev.decode_sdf'] == os.path.join(ours, 'utils', 'decoder_utils.py')
+
+
+# ------------------------------------------------------------------------------------------------ restatements of the mesh kernels
+_M = 2 ** 64 - 1
+
+
+def _mix64_int(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M
+    return z ^ (z >> 31)
+
+
+def test_rnd_bits_restatement_against_python_ints():
+    assert int(R.mix64(0)[0]) == 0xE220A8397B1DCDAF                  # the first output of SplitMix64 seeded with 0
+    assert _mix64_int(0) == 0xE220A8397B1DCDAF
+    cases = [(0, 0, 0), (5, 1, 2), (2 ** 64 - 1, 7, 1), (2 ** 64 - 1, 2 ** 40 - 1, 2), (12345678901234567, 2 ** 40 + 3, 0),
+             (1, 2 ** 40, 1), (2 ** 63, 99999, 2), (6, 2 ** 62 - 1, 2)]      # the last: 4 * i + k wraps nowhere yet, just below 2^64
+    for seed, i, k in cases:
+        want = _mix64_int(_mix64_int(seed) ^ _mix64_int((4 * i + k) & _M))
+        assert int(R.rnd_bits(seed, i, k)[0]) == want, (seed, i, k)
+    i = np.array([c[1] for c in cases], dtype=np.uint64)
+    got = R.rnd_bits(2 ** 64 - 1, i, 1)
+    assert [int(x) for x in got] == [_mix64_int(_mix64_int(_M) ^ _mix64_int((4 * int(j) + 1) & _M)) for j in i]
+
+
+def test_nearest_restatement_against_float64():
+    """Three roundings of relative size u = 2^-24 on the differences, three on the squares, two on the sums: at most 5u to first order
+    on every candidate, and the minimum keeps a relative bound. Coordinates of ordinary magnitude, so no term is subnormal."""
+    rs = np.random.RandomState(4)
+    A = rs.randn(700, 3).astype(np.float32)
+    B = (rs.randn(1900, 3) * 0.8).astype(np.float32)
+    B[:50] = A[:50] + (rs.randn(50, 3) * 1e-3).astype(np.float32)      # close pairs, where an expansion of |a - b|^2 cancels
+    got = R.nearest_sq_dist_f32(A, B)
+    assert got.dtype == np.float32 and got.shape == (700,)
+    assert np.array_equal(got, R.nearest_sq_dist_f32(A, B, max_elems=4001))         # the row chunks do not matter
+    d = A.astype(np.float64)[:, None, :] - B.astype(np.float64)[None, :, :]
+    want = (d * d).sum(2).min(1)
+    assert want.min() > 1e-12
+    assert (np.abs(got.astype(np.float64) - want) <= 6 * 2.0 ** -24 * want).all()
+    assert R.nearest_sq_dist_f32(B[:3], B)[1] == 0.0
+
+
+def test_sample_surface_restatement_on_two_triangles():
+    """Two triangles of areas 3 and 1 in the plane z = 1: face frequencies inside 5 sigma, every point inside its triangle. The
+    barycentric coordinates solve [a b c] l = p (the plane misses the origin, so the system is regular): their sum tells whether the
+    point is in the plane. Float32 rounding of the point puts a coordinate up to about 1e-7 outside, hence 1e-6 on both checks."""
+    v = np.array([[0, 0, 1], [2, 0, 1], [0, 3, 1], [5, 5, 1], [6, 5, 1], [5, 7, 1]], np.float32)
+    f = np.array([[0, 1, 2], [3, 4, 5]], np.int32)
+    n = 200000
+    p, fi, band = R.sample_surface(v, f, n, 9)
+    assert p.dtype == np.float32 and p.shape == (n, 3) and fi.shape == (n,) and band.shape == (n,) and (band >= 0).all()
+    hits = np.bincount(fi, minlength=2)
+    assert abs(hits[0] - 0.75 * n) <= 5 * np.sqrt(n * 0.75 * 0.25), hits
+    for k in range(2):
+        m = v[f[k]].astype(np.float64).T                              # columns a, b, c
+        lam = np.linalg.solve(m, p[fi == k].astype(np.float64).T).T
+        assert lam.min() >= -1e-6 and np.abs(lam.sum(1) - 1).max() <= 1e-6, (k, lam.min())
+        assert np.abs(lam.mean(0) - 1.0 / 3).max() < 5e-3              # uniform inside the triangle
+    # a pure function of (seed, index): a shorter run is a prefix, another seed differs
+    q, qi, _ = R.sample_surface(v, f, 1000, 9)
+    assert np.array_equal(q, p[:1000]) and np.array_equal(qi, fi[:1000])
+    assert not np.array_equal(R.sample_surface(v, f, 1000, 10)[0], q)
+    # a face of area 0 or naming a vertex outside the array is never picked
+    f3 = np.array([[0, 1, 2], [0, 0, 1], [0, 1, 6], [-1, 1, 2], [3, 4, 5], [3, 3, 3]], np.int32)
+    _, fi3, _ = R.sample_surface(v, f3, 20000, 1)
+    assert set(np.unique(fi3)) == {0, 4}
