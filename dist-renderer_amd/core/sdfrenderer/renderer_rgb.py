@@ -85,3 +85,45 @@ class SDFRenderer_color(SDFRenderer):
         shading = self.compute_shading_maps(R, T, lighting_locations, zdepth.detach(), normal.reshape(-1, 3), valid)
         shading = (shading * lighting_energies[:, None]).sum(0).reshape(h, w)
         return depth, normal, color * shading[:, :, None], mask_img, min_sdf
+
+    def render_batch(self, latent_color, latent, Rs, Ts, clamp_dist=0.1, no_grad=False, lighting_locations=None, lighting_energies=None):
+        """render (renderer_rgb.py:73) of B views in ONE launch sequence (no counterpart in the reference, whose demos call render once per
+        frame): Rs (B,3,3) / Ts (B,3) or sequences of per-view tensors; latent (1,256) shared by the views or (B,256), latent_color
+        (1,cs) or (B,cs); lighting_locations (M,3) shared or (B,M,3), lighting_energies (M,) or (B,M) (default ones). Returns (depth
+        (B,H,W), normal (B,H,W,3), color (B,H,W,3), mask (B,H,W), min_sdf (B,H,W)).
+
+        Geometry is one batched render with `render`'s configuration: depth, normal, mask and min_sdf of view v are bit-identical to
+        render(latent_color, latent, Rs[v], Ts[v], ...). The colours are one node over the colour stage (distr_color_stage_*: the valid
+        pixels compacted on the device, their points rebuilt from the rays, one segmented colour evaluation, one shading epilogue): every
+        view's bytes and gradients are those of its own B = 1 call; against `render` the colours agree to rounding (the points are formed
+        in another f32 order). Gradients reach both codes, the cameras and, with lights, the normal image -- and through it the render;
+        lights and energies are observations (ValueError if one requires grad). no_grad detaches what render(no_grad=True) detaches."""
+        h, w = self.img_hw
+        dev = self.calib_map.device
+        to_dev = lambda t: t.to(device=dev, dtype=torch.float32)      # (per view, like render_depth_batch)
+        Rs = torch.stack([to_dev(r) for r in Rs]) if not torch.is_tensor(Rs) else Rs
+        Ts = torch.stack([to_dev(t) for t in Ts]) if not torch.is_tensor(Ts) else Ts
+        if Rs.dim() != 3 or Ts.dim() != 2 or Rs.shape[0] != Ts.shape[0]:
+            raise ValueError('expected Rs (B,3,3) and Ts (B,3) of the same B; got %s and %s' % (tuple(Rs.shape), tuple(Ts.shape)))
+        B = Rs.shape[0]
+        ceng = self._color_engine
+        functions.color_code_rows(ceng, latent_color, latent, B)       # ValueError naming the expected shapes, before anything is rendered
+        functions.color_lights(dev, B, lighting_locations, lighting_energies)
+        cfg = self._cfg(clamp_dist, 'recursive', True, want_normal=True, no_grad_depth=no_grad, no_grad_mask=no_grad,
+                        no_grad_camera=no_grad)
+        cfg.use_depth2normal = 0
+        zdepth, mask, min_sdf, depth, normal = functions.render_batch_call(self._engine, cfg, latent, Rs, Ts)
+        if no_grad:
+            depth, min_sdf = depth.detach(), min_sdf.detach()
+        color = functions.color_stage_call(ceng, cfg, latent_color, latent, Rs, Ts, zdepth.detach(), mask, normal, lighting_locations,
+                                           lighting_energies, detach_color=no_grad)
+        return depth, normal, color, mask.reshape(B, h, w), min_sdf.reshape(B, h, w)
+
+    def relight(self, color, normal, Zdepth, mask, R, T, lighting_locations, lighting_energies=None):
+        """F relit frames of ONE rendered view without marching it again (the relighting demo's loop): color (H,W,3) = the UNLIT colour
+        image of render / render_batch, normal (H,W,3), mask (H,W) of the same render, Zdepth (H*W) the ray-length depth of
+        render_depth for that view (not the `depth` image, which is Zdepth * calib_map); lighting_locations (F,M,3), lighting_energies
+        (M,) or (F,M), default ones. Returns (F,H,W,3): frame f is byte for byte the colour image of the lit render_batch of this view
+        with lighting_locations[f]. Forward only: nothing is on the tape."""
+        cfg = self._cfg(0.1, 'recursive', True, want_normal=True)
+        return functions.color_relight(self._color_engine, cfg, color, normal, Zdepth, mask, R, T, lighting_locations, lighting_energies)

@@ -137,3 +137,48 @@ def decode_color(decoder, color_code, shape_code, points, MAX_POINTS=100000, no_
     if needs:
         return functions.color_eval_autograd(eng, color_code, shape_code, points)
     return functions.color_eval(eng, color_code, shape_code, points)
+
+
+def _color_batch_layout(color_codes, shape_codes, points, counts):
+    """(flat points (sum N, 3), counts as a list, output shape without the last axis) of a decode_color_batch call; ValueError for
+    shapes that do not fit. The number of segments S comes from the points ((S, N, 3)) or from `counts`; each of the two codes is
+    (1, .) shared or (S, .) -- their lengths are checked against the decoder by functions.color_code_rows. Pure shape logic: runs
+    without a GPU."""
+    if counts is None:
+        if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] < 1:
+            raise ValueError('points has shape %s; without counts it is (S, N, 3)' % (tuple(points.shape),))
+        S = points.shape[0]
+        flat, counts, shape = points.reshape(-1, 3), [points.shape[1]] * S, (S, points.shape[1])
+    else:
+        counts = [int(c) for c in (counts.tolist() if torch.is_tensor(counts) else counts)]
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points has shape %s; with counts it is the flat list (sum N, 3)' % (tuple(points.shape),))
+        if not counts or min(counts) < 0:
+            raise ValueError('counts %r: at least one segment, segment sizes >= 0' % (counts,))
+        if sum(counts) != points.shape[0]:
+            raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), points.shape[0]))
+        S = len(counts)
+        flat, shape = points, (points.shape[0],)
+    for name, t in (('color_codes', color_codes), ('shape_codes', shape_codes)):
+        if t.dim() != 2 or t.shape[0] not in (1, S):
+            raise ValueError('%s has shape %s; %d segments take (1, C) (shared) or (%d, C)' % (name, tuple(t.shape), S, S))
+    return flat, counts, shape
+
+
+def decode_color_batch(decoder, color_codes, shape_codes, points, counts=None, no_grad=False):
+    """decode_color for S [shape | colour] code pairs in one launch sequence (not in the reference, which decodes one view at a time):
+    points either (S, N, 3) -> (S, N, 3), or the flat list (sum N, 3) with `counts` (a sequence or a CPU int tensor of S segment sizes
+    >= 0) -> (sum N, 3); color_codes (S, cs) and shape_codes (S, 256), or (1, .) for a code all segments share. Every segment's slice is
+    byte for byte decode_color of that segment alone; so are, unless `no_grad`, its gradients w.r.t. the points and its rows of the
+    code gradients (distr_color_eval_multi / distr_color_backward_multi; more than 64 segments run in chunks of 64)."""
+    flat, counts, shape = _color_batch_layout(color_codes, shape_codes, points, counts)
+    dev = points.device
+    if dev.type != 'cuda':
+        raise RuntimeError('decode_color_batch: tensors must be on the GPU (no CPU path in this build)')
+    eng = functions.get_color_engine(decoder, dev.index if dev.index is not None else torch.cuda.current_device())
+    needs = (not no_grad) and torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in (color_codes, shape_codes, points))
+    if needs:
+        out = functions.color_eval_multi_autograd(eng, color_codes, shape_codes, flat, counts)
+    else:
+        out = functions.color_eval_multi(eng, color_codes, shape_codes, flat, counts)
+    return out.reshape(shape + (3,))

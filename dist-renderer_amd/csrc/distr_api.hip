@@ -19,6 +19,7 @@
 #include "distr_mlp_b6.hpp"
 #include "distr_samples.hpp"
 #include "distr_normal_grad.hpp"
+#include "distr_color_batch.hpp"
 
 using namespace distr;
 
@@ -843,37 +844,103 @@ int distr_set_color_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, cons
   return DISTR_OK;
 }
 
-int distr_color_eval(distr_ctx* ctx, const float* latent_cat, const float* xyz, int64_t n, float* rgb, void* ws, size_t ws_bytes,
-                     void* stream) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
+}  // extern "C"
+
+// ---- the colour decoder on a point list, plain or segmented: distr_color_eval / _backward, their *_multi forms, the colour stage of a batch
+namespace {
+
+// the two ways to a list of the colour decoder; the caller holds the EntryGuard
+int color_plain_list(distr_ctx* ctx, int64_t n, bool backward, PointList& pl) {
   if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
-  hipStream_t s = (hipStream_t)stream;
-  PointList pl = plain_list(n);
-  pl.bad_args = "null device pointer"; pl.small_ws = "colour workspace too small";
-  const int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, 0, xyz && rgb, ws, ws_bytes, false, s);
-  if (rc || n == 0) return rc;
-  hipLaunchKernelGGL(k_color, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, rgb, ctx->DC);
+  pl = plain_list(n);
+  pl.bad_args = "null device pointer"; pl.small_ws = backward ? "colour backward workspace too small" : "colour workspace too small";
+  return DISTR_OK;
+}
+
+int color_seg_list(distr_ctx* ctx, int32_t nseg, const int64_t* counts, int64_t latent_stride, PointList& pl) {
+  if (int rc = seg_list(ctx, nseg, counts, pl)) return rc;
+  if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->DC.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->DC.nlat);
+  return DISTR_OK;
+}
+
+// the two launches on a list whose workspace is carved and whose constants and tile table are written
+int color_eval_launch(distr_ctx* ctx, const PointList& pl, const float* xyz, float* rgb, hipStream_t s) {
+  hipLaunchKernelGGL(k_color, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, pl.nseg ? (int64_t)0 : pl.n, (const float*)pl.c0c4, rgb, ctx->DC, (const SegTable*)pl.tab);
   LAUNCH_CHECK("k_color");
   return DISTR_OK;
 }
 
+int color_bwd_launch(distr_ctx* ctx, const PointList& pl, const float* xyz, const float* g_rgb, float* g_xyz, hipStream_t s) {
+  hipLaunchKernelGGL(k_color_bwd, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, pl.nseg ? (int64_t)0 : pl.n, (const float*)pl.c0c4, g_rgb, g_xyz, pl.partial, ctx->DC,
+                     (const SegTable*)pl.tab);
+  LAUNCH_CHECK("k_color_bwd");
+  return DISTR_OK;
+}
+
+int color_eval_list(distr_ctx* ctx, PointList& pl, const float* latent_cat, int64_t latent_stride, const float* xyz, float* rgb, void* ws, size_t ws_bytes,
+                    hipStream_t s) {
+  const int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, latent_stride, xyz && rgb, ws, ws_bytes, false, s);
+  if (rc || pl.n == 0) return rc;
+  return color_eval_launch(ctx, pl, xyz, rgb, s);
+}
+
+int color_backward_list(distr_ctx* ctx, PointList& pl, const float* latent_cat, int64_t latent_stride, const float* xyz, const float* g_rgb, float* g_xyz,
+                        float* g_latent_cat, void* ws, size_t ws_bytes, hipStream_t s) {
+  int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, latent_stride, xyz && g_rgb, ws, ws_bytes, true, s);
+  if (rc) return rc;
+  if (pl.n > 0 && (rc = color_bwd_launch(ctx, pl, xyz, g_rgb, g_xyz, s))) return rc;
+  return list_latent_grad(ctx, ctx->DC, pl, g_latent_cat, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int distr_color_eval(distr_ctx* ctx, const float* latent_cat, const float* xyz, int64_t n, float* rgb, void* ws, size_t ws_bytes,
+                     void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  PointList pl;
+  if (int rc = color_plain_list(ctx, n, false, pl)) return rc;
+  return color_eval_list(ctx, pl, latent_cat, 0, xyz, rgb, ws, ws_bytes, (hipStream_t)stream);
+}
 
 int distr_color_backward(distr_ctx* ctx, const float* latent_cat, const float* xyz, int64_t n, const float* g_rgb, float* g_xyz,
                          float* g_latent_cat, void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
-  if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
-  hipStream_t s = (hipStream_t)stream;
-  PointList pl = plain_list(n);
-  pl.bad_args = "null device pointer"; pl.small_ws = "colour backward workspace too small";
-  const int rc = point_list_prologue(ctx, ctx->DC, pl, latent_cat, 0, xyz && g_rgb, ws, ws_bytes, true, s);
-  if (rc) return rc;
-  if (n > 0) {
-    hipLaunchKernelGGL(k_color_bwd, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, g_rgb, g_xyz, pl.partial, ctx->DC);
-    LAUNCH_CHECK("k_color_bwd");
-  }
-  return list_latent_grad(ctx, ctx->DC, pl, g_latent_cat, s);
+  PointList pl;
+  if (int rc = color_plain_list(ctx, n, true, pl)) return rc;
+  return color_backward_list(ctx, pl, latent_cat, 0, xyz, g_rgb, g_xyz, g_latent_cat, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t distr_color_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  PointList pl;
+  return seg_list(nullptr, nseg, counts_host, pl) == DISTR_OK ? carve_list(nullptr, pl, false) : 0;
+}
+
+size_t distr_color_backward_multi_workspace_bytes(int32_t nseg, const int64_t* counts_host) {
+  PointList pl;
+  return seg_list(nullptr, nseg, counts_host, pl) == DISTR_OK ? carve_list(nullptr, pl, true) : 0;
+}
+
+int distr_color_eval_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent_cat, int64_t latent_stride, const float* xyz,
+                           float* rgb, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  PointList pl;
+  if (int rc = color_seg_list(ctx, nseg, counts_host, latent_stride, pl)) return rc;
+  return color_eval_list(ctx, pl, latent_cat, latent_stride, xyz, rgb, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int distr_color_backward_multi(distr_ctx* ctx, int32_t nseg, const int64_t* counts_host, const float* latent_cat, int64_t latent_stride,
+                               const float* xyz, const float* g_rgb, float* g_xyz, float* g_latent_cat, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  PointList pl;
+  if (int rc = color_seg_list(ctx, nseg, counts_host, latent_stride, pl)) return rc;
+  return color_backward_list(ctx, pl, latent_cat, latent_stride, xyz, g_rgb, g_xyz, g_latent_cat, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int distr_workspace_bytes(distr_ctx* ctx, const distr_render_cfg* cfg, size_t* fwd, size_t* bwd) {
@@ -2177,6 +2244,225 @@ int distr_render_normal_grad_backward_batch(distr_ctx* ctx, const distr_render_c
     hipLaunchKernelGGL(ngrad::k_ng_cam_fin, dim3(NV), blk, 0, s, V, (const int*)w.totals, (const float*)w.part, p.nblk, g_R, g_T);
     LAUNCH_CHECK("k_ng_cam_fin");
   }
+  return DISTR_OK;
+}
+
+}  // extern "C"
+
+// ---- the colour stage of a batch of rendered views (include/distr_color_batch.h, kernels: distr_color_batch.hpp)
+namespace {
+
+struct CbPlan {
+  int nviews, P, nblk;       // nblk: blocks of MTILE pixels per view (count / compact / camera sums)
+  cbatch::Geo G;
+  PointList pl;              // the segmented list at its capacity: a segment of P points per view (the table holds the real counts)
+};
+
+struct CbFwdWs {             // what the forward leaves for the backward
+  int *btot, *boff, *totals;
+  int32_t *index, *pos;      // [nviews][P] compacted valid pixels; list position of every pixel (-1 off the mask)
+  float *xyz, *col;          // [nviews * P][3] surface points and their unshaded colours, view v from v * P on
+  void* mlp;
+  size_t mlp_bytes, bytes;
+};
+
+struct CbBwdWs {
+  float *g_col, *g_xyz, *part;
+  void* mlp;
+  size_t mlp_bytes, bytes;
+};
+
+int cb_plan(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, CbPlan& p) {
+  if (int rc = check_cfg(ctx, cfg)) return rc;
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
+  if (cfg->rows != 0) return fail(ctx, DISTR_ERR_UNSUPPORTED, "colour stage: row bands (rows != 0) are not implemented");
+  memset(&p, 0, sizeof(p));
+  p.nviews = nviews;
+  p.P = cfg->H * cfg->W;
+  p.nblk = (p.P + cbatch::MTILE - 1) / cbatch::MTILE;
+  p.G.H = cfg->H; p.G.W = cfg->W; p.G.P = p.P;
+  memcpy(p.G.Ki, cfg->K_inv, sizeof(p.G.Ki));
+  memcpy(p.G.M, cfg->M, sizeof(p.G.M));
+  int64_t cap[DISTR_MAX_VIEWS];
+  for (int v = 0; v < nviews; ++v) cap[v] = p.P;
+  return seg_list(ctx, nviews, cap, p.pl);         // (refuses more than 2^30 pixels in all)
+}
+
+CbFwdWs cb_fwd_ws(void* base, CbPlan& p) {
+  WsCarve c(base);
+  CbFwdWs w;
+  const size_t NP = (size_t)p.nviews * p.P;
+  w.btot = c.take<int>((size_t)p.nviews * p.nblk);
+  w.boff = c.take<int>((size_t)p.nviews * p.nblk);
+  w.totals = c.take<int>(DISTR_MAX_VIEWS);
+  w.index = c.take<int32_t>(NP);
+  w.pos = c.take<int32_t>(NP);
+  w.xyz = c.take<float>(3 * NP);
+  w.col = c.take<float>(3 * NP);
+  w.mlp_bytes = carve_list(nullptr, p.pl, false);
+  w.mlp = c.take<char>(w.mlp_bytes);
+  w.bytes = c.bytes();
+  return w;
+}
+
+CbBwdWs cb_bwd_ws(void* base, CbPlan& p) {
+  WsCarve c(base);
+  CbBwdWs w;
+  const size_t NP = (size_t)p.nviews * p.P;
+  w.g_col = c.take<float>(3 * NP);
+  w.g_xyz = c.take<float>(3 * NP);
+  w.part = c.take<float>((size_t)p.nviews * p.nblk * 12);
+  w.mlp_bytes = carve_list(nullptr, p.pl, true);
+  w.mlp = c.take<char>(w.mlp_bytes);
+  w.bytes = c.bytes();
+  return w;
+}
+
+// the lights of a call as the kernels take them, or why they are refused; `sets`: views (or frames) that index the strides
+int cb_lights(distr_ctx* ctx, const distr_color_lights* in, bool have_normal, cbatch::Lights& L) {
+  memset(&L, 0, sizeof(L));
+  if (!in) return DISTR_OK;
+  if (in->struct_size != sizeof(distr_color_lights)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_color_lights.struct_size is %u, expected %zu", in->struct_size, sizeof(distr_color_lights));
+  if (in->nlights < 0 || in->nlights > 4096) return fail(ctx, DISTR_ERR_INVALID_ARG, "nlights %d: 0..4096", in->nlights);
+  if (in->nlights == 0) return DISTR_OK;
+  if (!in->locations_dev || !in->energies_dev || !have_normal) return fail(ctx, DISTR_ERR_INVALID_ARG, "lights need locations, energies and the normal image");
+  if ((in->location_stride != 0 && in->location_stride < 3 * (int64_t)in->nlights) || (in->energy_stride != 0 && in->energy_stride < in->nlights))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "light strides: 0 (shared) or >= 3 M / M floats");
+  L.loc = in->locations_dev; L.en = in->energies_dev; L.lstride = in->location_stride; L.estride = in->energy_stride; L.M = in->nlights;
+  return DISTR_OK;
+}
+
+// the latent constants of every view's [shape | colour] code and the tile table from the counts on the device
+int cb_list_setup(distr_ctx* ctx, CbPlan& p, const float* latent_cat, int64_t latent_stride, const int* totals, hipStream_t s) {
+  hipLaunchKernelGGL(k_latent_consts, dim3(4, (unsigned)p.nviews), dim3(256), 0, s, p.pl.c0c4, ctx->DC, latent_cat, latent_stride, (SegTable*)nullptr, p.pl.cnt);
+  LAUNCH_CHECK("k_latent_consts");
+  hipLaunchKernelGGL(ngrad::k_ng_seg_table, dim3(1), dim3(64), 0, s, totals, p.nviews, p.P, p.pl.tab);
+  LAUNCH_CHECK("k_ng_seg_table");
+  return DISTR_OK;
+}
+
+int cb_common(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, int64_t latent_stride, CbPlan& p) {
+  if (int rc = cb_plan(ctx, cfg, nviews, p)) return rc;
+  if (!ctx->has_color) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_color_decoder has not been called");
+  if (latent_stride != 0 && latent_stride < ctx->DC.nlat) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, ctx->DC.nlat);
+  return DISTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int distr_color_stage_workspace_bytes(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, size_t* forward_bytes, size_t* backward_bytes) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  CbPlan p;
+  if (int rc = cb_plan(ctx, cfg, nviews, p)) return rc;
+  if (forward_bytes) *forward_bytes = cb_fwd_ws(nullptr, p).bytes;
+  if (backward_bytes) *backward_bytes = cb_bwd_ws(nullptr, p).bytes;
+  return DISTR_OK;
+}
+
+int distr_color_stage_forward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const float* R, const float* T, const float* zdepth,
+                                    const uint8_t* mask, const float* normal, const float* latent_cat, int64_t latent_stride,
+                                    const distr_color_lights* lights, float* rgb, void* ws, size_t ws_bytes, int32_t* index_out, float* xyz_out,
+                                    int32_t* totals_out, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  CbPlan p;
+  if (int rc = cb_common(ctx, cfg, nviews, latent_stride, p)) return rc;
+  if (!R || !T || !zdepth || !mask || !latent_cat || !rgb || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  cbatch::Lights L;
+  if (int rc = cb_lights(ctx, lights, normal != nullptr, L)) return rc;
+  if (ws_bytes < cb_fwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "colour stage: forward workspace too small: %zu < %zu", ws_bytes, cb_fwd_ws(nullptr, p).bytes);
+  hipStream_t s = (hipStream_t)stream;
+  const CbFwdWs w = cb_fwd_ws(ws, p);
+  carve_list(w.mlp, p.pl, false);
+  const unsigned NV = (unsigned)nviews;
+  const dim3 gblk((unsigned)p.nblk, NV), gpx((unsigned)((p.P + cbatch::MB - 1) / cbatch::MB), NV), blk(cbatch::MB);
+  const cbatch::Cams C{R, T, zdepth, normal, (int64_t)p.P};
+  hipLaunchKernelGGL(cbatch::k_cb_count, gblk, blk, 0, s, mask, p.P, p.nblk, w.btot);
+  LAUNCH_CHECK("k_cb_count");
+  hipLaunchKernelGGL(samples::k_samp_top_scan, dim3(NV), blk, 0, s, (const int*)w.btot, p.nblk, w.boff, w.totals);
+  LAUNCH_CHECK("k_samp_top_scan");
+  hipLaunchKernelGGL(cbatch::k_cb_compact, gblk, blk, 0, s, mask, p.P, p.nblk, (const int*)w.boff, w.index, w.pos);
+  LAUNCH_CHECK("k_cb_compact");
+  hipLaunchKernelGGL(cbatch::k_cb_points, gpx, blk, 0, s, p.G, C, (const int32_t*)w.index, (const int*)w.totals, w.xyz);
+  LAUNCH_CHECK("k_cb_points");
+  if (int rc = cb_list_setup(ctx, p, latent_cat, latent_stride, w.totals, s)) return rc;
+  if (int rc = color_eval_launch(ctx, p.pl, w.xyz, w.col, s)) return rc;
+  hipLaunchKernelGGL(cbatch::k_cb_epilogue<true>, gpx, blk, 0, s, p.G, C, L, mask, (const int32_t*)w.pos, (const float*)w.col, rgb);
+  LAUNCH_CHECK("k_cb_epilogue");
+  const size_t NP = (size_t)nviews * p.P;
+  if (index_out) HIP_TRY(hipMemcpyAsync(index_out, w.index, NP * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (xyz_out) HIP_TRY(hipMemcpyAsync(xyz_out, w.xyz, 3 * NP * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (totals_out) HIP_TRY(hipMemcpyAsync(totals_out, w.totals, (size_t)nviews * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return DISTR_OK;
+}
+
+int distr_color_stage_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const float* R, const float* T, const float* zdepth,
+                                     const float* normal, const float* latent_cat, int64_t latent_stride, const distr_color_lights* lights,
+                                     const void* ws_fwd, size_t ws_fwd_bytes, const float* g_rgb, float* g_latent_cat, float* g_R, float* g_T,
+                                     float* g_normal, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  CbPlan p;
+  if (int rc = cb_common(ctx, cfg, nviews, latent_stride, p)) return rc;
+  if (!R || !T || !zdepth || !latent_cat || !ws_fwd || !g_rgb || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  cbatch::Lights L;
+  if (int rc = cb_lights(ctx, lights, normal != nullptr, L)) return rc;
+  if (ws_fwd_bytes < cb_fwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "colour stage: forward workspace too small: %zu < %zu", ws_fwd_bytes, cb_fwd_ws(nullptr, p).bytes);
+  if (ws_bytes < cb_bwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "colour stage: backward workspace too small: %zu < %zu", ws_bytes, cb_bwd_ws(nullptr, p).bytes);
+  hipStream_t s = (hipStream_t)stream;
+  const CbFwdWs f = cb_fwd_ws(const_cast<void*>(ws_fwd), p);
+  const CbBwdWs w = cb_bwd_ws(ws, p);
+  carve_list(w.mlp, p.pl, true);
+  const unsigned NV = (unsigned)nviews;
+  const dim3 gblk((unsigned)p.nblk, NV), gpx((unsigned)((p.P + cbatch::MB - 1) / cbatch::MB), NV), blk(cbatch::MB);
+  const cbatch::Cams C{R, T, zdepth, normal, (int64_t)p.P};
+  const bool decoder = g_latent_cat != nullptr;      // null: the colours are constants, only the shading terms are left
+  const bool camera = g_R || g_T;
+  if (!L.M) g_normal = nullptr;                      // written with lights only
+  if (decoder || g_normal) {
+    hipLaunchKernelGGL(cbatch::k_cb_bwd_pre, gpx, blk, 0, s, p.G, C, L, (const int32_t*)f.pos, (const float*)f.col, g_rgb, decoder ? w.g_col : (float*)nullptr,
+                       g_normal);
+    LAUNCH_CHECK("k_cb_bwd_pre");
+  }
+  if (decoder) {
+    if (int rc = cb_list_setup(ctx, p, latent_cat, latent_stride, f.totals, s)) return rc;
+    if (int rc = color_bwd_launch(ctx, p.pl, f.xyz, w.g_col, camera ? w.g_xyz : (float*)nullptr, s)) return rc;
+    if (int rc = list_latent_grad(ctx, ctx->DC, p.pl, g_latent_cat, s)) return rc;
+  }
+  if (camera) {
+    if (!decoder && !L.M) {      // nothing reaches the camera
+      if (g_R) HIP_TRY(hipMemsetAsync(g_R, 0, (size_t)nviews * 9 * sizeof(float), s));
+      if (g_T) HIP_TRY(hipMemsetAsync(g_T, 0, (size_t)nviews * 3 * sizeof(float), s));
+      return DISTR_OK;
+    }
+    hipLaunchKernelGGL(cbatch::k_cb_cam_bwd, gblk, blk, 0, s, p.G, C, L, (const int32_t*)f.index, (const int*)f.totals, (const float*)f.col, g_rgb,
+                       decoder ? (const float*)w.g_xyz : (const float*)nullptr, p.nblk, w.part);
+    LAUNCH_CHECK("k_cb_cam_bwd");
+    hipLaunchKernelGGL(cbatch::k_cb_cam_fin, dim3(NV), blk, 0, s, p.G, C, (const int*)f.totals, (const float*)w.part, p.nblk, g_R, g_T);
+    LAUNCH_CHECK("k_cb_cam_fin");
+  }
+  return DISTR_OK;
+}
+
+int distr_color_relight(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nframes, const float* R, const float* T, const float* zdepth,
+                        const uint8_t* mask, const float* normal, const float* color, const distr_color_lights* lights, float* out, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  CbPlan p;
+  if (int rc = cb_plan(ctx, cfg, 1, p)) return rc;
+  if (nframes < 1 || (int64_t)nframes * p.P > ((int64_t)1 << 30)) return fail(ctx, DISTR_ERR_INVALID_ARG, "nframes %d: at least 1, at most 2^30 pixels in all", nframes);
+  if (nframes > 65535) return fail(ctx, DISTR_ERR_INVALID_ARG, "nframes %d: at most 65535 per call", nframes);
+  if (!R || !T || !zdepth || !mask || !normal || !color || !out) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  cbatch::Lights L;
+  if (int rc = cb_lights(ctx, lights, true, L)) return rc;
+  if (!L.M) return fail(ctx, DISTR_ERR_INVALID_ARG, "relight needs at least one light");
+  const cbatch::Cams C{R, T, zdepth, normal, (int64_t)0};
+  const dim3 gpx((unsigned)((p.P + cbatch::MB - 1) / cbatch::MB), (unsigned)nframes), blk(cbatch::MB);
+  hipLaunchKernelGGL(cbatch::k_cb_epilogue<false>, gpx, blk, 0, (hipStream_t)stream, p.G, C, L, mask, (const int32_t*)nullptr, color, out);
+  LAUNCH_CHECK("k_cb_epilogue<relight>");
   return DISTR_OK;
 }
 

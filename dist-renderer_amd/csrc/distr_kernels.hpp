@@ -1726,12 +1726,22 @@ __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, Deco
 // decode_color (core/utils/decoder_utils.py:94-112) for the surface points of SDFRenderer_color.render_color
 // (core/sdfrenderer/renderer_rgb.py:20-38): the same fused tile on the colour decoder's weights (latent = shape code |
 // colour code, folded into c0 / c4), lin8 with three rows, tanh on each. Forward only.
+// seg (null: one code, n points): segmented list -- c0c4 = [segments][1024], n unused; the tile's segment, first point and count come from
+// the tile table (seg_find), and a tile behind the last segment leaves. A segment's tiles are those of its stand-alone call.
 DISTR_GLOBAL void __launch_bounds__(256, 1) k_color(const float* __restrict__ xyz, int64_t n, const float* __restrict__ c0c4,
-                                                  float* __restrict__ rgb, DecoderDev D) {
+                                                  float* __restrict__ rgb, DecoderDev D, const SegTable* __restrict__ seg) {
   constexpr int RB = 2, TILE = 64;
   __shared__ Smem<RB> S;
   const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * TILE;
+  int64_t base = (int64_t)blockIdx.x * TILE;
+  if (seg) {
+    int sg;
+    int64_t poff;
+    if (!seg_find(seg, (int)blockIdx.x, sg, base, poff, n)) return;
+    c0c4 += (size_t)sg * (2 * HID);
+    xyz += poff * 3;
+    rgb += poff * 3;
+  }
   if (base >= n) return;
   if (tid < TILE) {
     const int64_t r = base + tid;
@@ -1758,11 +1768,20 @@ DISTR_GLOBAL void __launch_bounds__(256, 1) k_color(const float* __restrict__ xy
 // delta sums for the [shape | colour] code gradient, d rgb / d xyz per point.
 DISTR_GLOBAL void __launch_bounds__(256, 1) k_color_bwd(const float* __restrict__ xyz, int64_t n, const float* __restrict__ c0c4,
                                                       const float* __restrict__ g_rgb, float* __restrict__ g_xyz, float* __restrict__ partial,
-                                                      DecoderDev D) {
+                                                      DecoderDev D, const SegTable* __restrict__ seg) {
   constexpr int RB = 2, TILE = 64;
   __shared__ Smem<RB> S;
   const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * TILE;
+  int64_t base = (int64_t)blockIdx.x * TILE;
+  if (seg) {                 // segmented list, as in k_color; the partial row stays the GLOBAL tile's (k_points_latent_grad walks the table)
+    int sg;
+    int64_t poff;
+    if (!seg_find(seg, (int)blockIdx.x, sg, base, poff, n)) return;
+    c0c4 += (size_t)sg * (2 * HID);
+    xyz += poff * 3;
+    g_rgb += poff * 3;
+    if (g_xyz) g_xyz += poff * 3;
+  }
   if (base >= n) return;
   const bool valid = tid < TILE && base + tid < n;
   if (tid < TILE) {

@@ -36,6 +36,10 @@ MULTI_EXPORTS = ['distr_mlp_multi_workspace_bytes', 'distr_mlp_backward_multi_wo
                  'distr_mlp_grad_multi', 'distr_mlp_backward_multi']
 # normal-map losses through the decoder's second path (include/distr_normal_grad.h, included by distr.h)
 NORMAL_GRAD_EXPORTS = ['distr_render_normal_grad_workspace_bytes', 'distr_render_normal_grad_backward_batch']
+# the colour decoder on a segmented point list and the colour stage of a batch of rendered views (include/distr_color_batch.h)
+COLOR_BATCH_EXPORTS = ['distr_color_multi_workspace_bytes', 'distr_color_backward_multi_workspace_bytes', 'distr_color_eval_multi',
+                       'distr_color_backward_multi', 'distr_color_stage_workspace_bytes', 'distr_color_stage_forward_batch',
+                       'distr_color_stage_backward_batch', 'distr_color_relight']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -100,6 +104,12 @@ class WarpCfg(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K', C.c_float * 9), ('K_inv', C.c_float * 9), ('thres_depth', C.c_float)]
 
 
+class ColorLights(_Sized):
+    """distr_color_lights (include/distr_color_batch.h): M point lights per view (or frame); a stride of 0 shares one set."""
+    _fields_ = [('struct_size', C.c_uint32), ('nlights', C.c_int32), ('locations_dev', C.c_void_p), ('location_stride', C.c_int64),
+                ('energies_dev', C.c_void_p), ('energy_stride', C.c_int64)]
+
+
 class SamplesCfg(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K_inv', C.c_float * 9), ('M', C.c_float * 9),
                 ('clamp_dist', C.c_float), ('mode', C.c_int32), ('number', C.c_int32)]
@@ -133,8 +143,8 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h')                    # include/: the C ABI
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp')
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h')                    # include/: the C ABI
 INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -361,6 +371,18 @@ def lib():
             L.distr_render_normal_grad_workspace_bytes.argtypes = [vp, C.POINTER(RenderCfg), i32, szp]
             L.distr_render_normal_grad_backward_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, C.POINTER(C.c_int32), vp, C.c_size_t, fp, fp, fp, fp,
                                                                   vp, C.c_size_t, vp]
+            for f in (L.distr_color_multi_workspace_bytes, L.distr_color_backward_multi_workspace_bytes):
+                f.argtypes = [i32, i64p]
+                f.restype = C.c_size_t
+            L.distr_color_eval_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, vp, C.c_size_t, vp]
+            L.distr_color_backward_multi.argtypes = [vp, i32, i64p, fp, i64, fp, fp, fp, fp, vp, C.c_size_t, vp]
+            lights = C.POINTER(ColorLights)
+            L.distr_color_stage_workspace_bytes.argtypes = [vp, C.POINTER(RenderCfg), i32, szp, szp]
+            L.distr_color_stage_forward_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, u8p, fp, fp, i64, lights, fp, vp, C.c_size_t,
+                                                          vp, fp, vp, vp]
+            L.distr_color_stage_backward_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, fp, fp, i64, lights, vp, C.c_size_t,
+                                                           fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
+            L.distr_color_relight.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, u8p, fp, fp, lights, fp, vp]
             _lib = L
     return _lib
 

@@ -819,3 +819,219 @@ class WarpLossFunction(torch.autograd.Function):
 
 def warp_loss(engine, wcfg, z1, m1, z2, img1, img2, R1, T1, R2, T2):
     return WarpLossFunction.apply(z1, R1, T1, R2, T2, engine, wcfg, m1, z2, img1, img2)
+
+
+# ------------------------------------------------------------------------------------------ colour on a segmented list; the colour stage
+SHAPE_CODE = 256        # code length of the shape decoder the colour path is built for (SDFRenderer_color refuses any other)
+
+
+def color_code_rows(engine, color_codes, shape_codes, S):
+    """[shape code | colour code] rows of S segments (or views) as one f32 device tensor: (S, 256 + cs), or (1, 256 + cs) when both
+    codes are shared. Each of the two is (1, .) shared or (S, .); ValueError naming the expected shapes otherwise. Runs without a GPU
+    on CPU tensors (engine: anything with latent_size and device)."""
+    cs = engine.latent_size - SHAPE_CODE
+    sc, cc = _f32c(shape_codes, engine.device), _f32c(color_codes, engine.device)
+    ok = sc.dim() == 2 and cc.dim() == 2 and sc.shape[1] == SHAPE_CODE and cc.shape[1] == cs and sc.shape[0] in (1, S) and cc.shape[0] in (1, S)
+    if not ok:
+        raise ValueError('shape codes have shape %s and colour codes %s; %d segments take shape codes (1, %d) or (%d, %d) and colour codes '
+                         '(1, %d) or (%d, %d)' % (tuple(shape_codes.shape), tuple(color_codes.shape), S, SHAPE_CODE, S, SHAPE_CODE, cs, S, cs))
+    rows = max(sc.shape[0], cc.shape[0])
+    return torch.cat([sc.expand(rows, -1), cc.expand(rows, -1)], 1).contiguous()
+
+
+def _split_code_grad(g_rows, color_codes, shape_codes):
+    """Rows [shape | colour] of a code gradient (one per segment) -> (g_color_codes, g_shape_codes) in the inputs' shapes; a shared
+    code gets the sum of the rows (fixed order)."""
+    def part(g, like):
+        g = g.sum(0, keepdim=True) if like.shape[0] == 1 and g.shape[0] > 1 else g
+        return g.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+    return part(g_rows[:, SHAPE_CODE:], color_codes), part(g_rows[:, :SHAPE_CODE], shape_codes)
+
+
+def color_eval_multi(engine, color_codes, shape_codes, points, counts):
+    """decode_color of a segmented point list: segment s = counts[s] consecutive rows of points (sum counts, 3), decoded with
+    [shape_codes[s] | color_codes[s]] (each (S, .) or (1, .) shared) -> (sum counts, 3). One launch sequence per 64 segments
+    (distr_color_eval_multi); every segment's slice is byte for byte color_eval of that segment alone."""
+    L, p, dev = engine.ctx.L, binding.ptr, engine.device
+    lat = color_code_rows(engine, color_codes, shape_codes, len(segment_plan(counts)['tiles']))
+    return _multi_run(engine, lat, points, counts, L.distr_color_multi_workspace_bytes,
+                      lambda n, S: torch.empty(n, 3, dtype=torch.float32, device=dev),
+                      lambda head, tail, p0, s0, out: L.distr_color_eval_multi(*head, p(out[p0:]), *tail))
+
+
+def color_backward_multi(engine, color_codes, shape_codes, points, counts, g_rgb, need_codes=True, need_points=True):
+    """Backward of color_eval_multi for the upstream gradient g_rgb (sum counts, 3): (g_rows (S, 256 + cs): one [shape | colour] row per
+    segment, also for shared codes (the caller sums), g_points (sum counts, 3)); either is None when not needed."""
+    L, p, dev = engine.ctx.L, binding.ptr, engine.device
+    lat = color_code_rows(engine, color_codes, shape_codes, len(segment_plan(counts)['tiles']))
+    gs = _f32c(g_rgb, dev).reshape(-1, 3)
+
+    def outputs(n, S):
+        if gs.shape[0] != n:
+            raise ValueError('g_rgb has %d rows for %d points' % (gs.shape[0], n))
+        return (torch.empty(S, engine.latent_size, dtype=torch.float32, device=dev) if need_codes else None,
+                torch.empty(n, 3, dtype=torch.float32, device=dev) if need_points else None)
+
+    def call(head, tail, p0, s0, out):
+        g_l, g_x = out
+        return L.distr_color_backward_multi(*head, p(gs[p0:]), p(None if g_x is None else g_x[p0:]), p(None if g_l is None else g_l[s0:]), *tail)
+    return _multi_run(engine, lat, points, counts, L.distr_color_backward_multi_workspace_bytes, outputs, call)
+
+
+class ColorDecodeMultiFunction(torch.autograd.Function):
+    """color_eval_multi with autograd: (color_codes, shape_codes, points (sum counts, 3)) -> (sum counts, 3); backward =
+    distr_color_backward_multi. Row s of the code gradients is the stand-alone call's, bit for bit; a shared code gets the sum of the rows."""
+
+    @staticmethod
+    def forward(ctx, color_codes, shape_codes, points, engine, counts):
+        out = color_eval_multi(engine, color_codes, shape_codes, points, counts)
+        ctx.engine, ctx.counts = engine, [int(c) for c in counts]
+        ctx.save_for_backward(color_codes.detach(), shape_codes.detach(), points.detach())
+        ctx.need = (color_codes.requires_grad, shape_codes.requires_grad, points.requires_grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        color_codes, shape_codes, points = ctx.saved_tensors
+        g_rows, g_x = color_backward_multi(ctx.engine, color_codes, shape_codes, points, ctx.counts, g, need_codes=ctx.need[0] or ctx.need[1],
+                                           need_points=ctx.need[2])
+        g_c, g_s = _split_code_grad(g_rows, color_codes, shape_codes) if g_rows is not None else (None, None)
+        return (g_c if ctx.need[0] else None), (g_s if ctx.need[1] else None), (None if g_x is None else g_x.reshape(points.shape)), None, None
+
+
+def color_eval_multi_autograd(engine, color_codes, shape_codes, points, counts):
+    return ColorDecodeMultiFunction.apply(color_codes, shape_codes, points, engine, counts)
+
+
+def color_lights(dev, sets, locations, energies):
+    """Point lights of `sets` views (or frames) as the colour stage reads them: locations (M, 3) shared or (sets, M, 3), energies (M,) or
+    (sets, M), default ones. Returns (locations, energies as f32 device tensors, binding.ColorLights), or (None, None, None) without
+    lights. Lights and energies are observations: ValueError when one requires grad."""
+    if locations is None:
+        return None, None, None
+    for name, t in (('lighting_locations', locations), ('lighting_energies', energies)):
+        if t is not None and getattr(t, 'requires_grad', False):
+            raise ValueError('%s requires grad: lights and energies are observations here, no gradient reaches them (detach them)' % name)
+    loc = _f32c(locations, dev)
+    if loc.dim() not in (2, 3) or loc.shape[-1] != 3 or loc.shape[-2] < 1 or (loc.dim() == 3 and loc.shape[0] != sets):
+        raise ValueError('lighting_locations has shape %s; expected (M, 3) or (%d, M, 3)' % (tuple(locations.shape), sets))
+    M = loc.shape[-2]
+    en = torch.ones(M, dtype=torch.float32, device=dev) if energies is None else _f32c(energies, dev)
+    if en.shape not in ((M,), (sets, M)):
+        raise ValueError('lighting_energies has shape %s; expected (%d,) or (%d, %d)' % (tuple(en.shape), M, sets, M))
+    st = binding.ColorLights()
+    st.nlights = M
+    st.locations_dev, st.location_stride = loc.data_ptr(), (3 * M if loc.dim() == 3 else 0)
+    st.energies_dev, st.energy_stride = en.data_ptr(), (M if en.dim() == 2 else 0)
+    return loc, en, st
+
+
+def _stage_views(engine, cfg, R, T, zdepth, mask, normal, lit):
+    dev = engine.device
+    P = cfg.H * cfg.W
+    Rc, Tc = _f32c(R, dev).reshape(-1, 9), _f32c(T, dev).reshape(-1, 3)
+    B = Rc.shape[0]
+    if Tc.shape[0] != B or not (1 <= B <= binding.MAX_VIEWS):
+        raise ValueError('expected R (B,3,3), T (B,3) with 1 <= B <= %d' % binding.MAX_VIEWS)
+    z, m = _f32c(zdepth, dev).reshape(-1), _u8c(mask, dev).reshape(-1)
+    n = _f32c(normal, dev).reshape(-1) if lit else None
+    if z.numel() != B * P or m.numel() != B * P or (lit and n.numel() != 3 * B * P):
+        raise ValueError('expected zdepth / mask (%d, %d) and, with lights, normal (%d, %d, %d, 3)' % (B, P, B, cfg.H, cfg.W))
+    return Rc, Tc, z, m, n, B, P
+
+
+def color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal=None, lights=None, energies=None, want_lists=False):
+    """distr_color_stage_forward_batch: the colours of B rendered views in one launch sequence -> rgb (B, H, W, 3), zero off the mask,
+    times the shading term when lights are given (then `normal` (B, H, W, 3) is read). Returns (rgb, saved): `saved` is what the
+    backward needs; with want_lists it also holds 'index' (B, P) int32, 'xyz' (B, P, 3) and 'totals' (B,) int32 -- the compacted valid
+    pixels of every view (its first totals[v] entries) and their surface points."""
+    dev, L, p = engine.device, engine.ctx.L, binding.ptr
+    lit = lights is not None
+    Rc, Tc, z, m, n, B, P = _stage_views(engine, cfg, R, T, zdepth, mask, normal, lit)
+    lat = color_code_rows(engine, color_codes, shape_codes, B)
+    loc, en, st = color_lights(dev, B, lights, energies)
+    fb, bb = C.c_size_t(), C.c_size_t()
+    engine.ctx.check(L.distr_color_stage_workspace_bytes(engine.ctx.h, C.byref(cfg), B, C.byref(fb), C.byref(bb)))
+    ws = torch.empty(fb.value, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(B, cfg.H, cfg.W, 3, dtype=torch.float32, device=dev)
+    lists = {}
+    if want_lists:
+        lists = dict(index=torch.empty(B, P, dtype=torch.int32, device=dev), xyz=torch.empty(B, P, 3, dtype=torch.float32, device=dev),
+                     totals=torch.empty(B, dtype=torch.int32, device=dev))
+    stride = 0 if lat.shape[0] == 1 else engine.latent_size
+    engine.ctx.check(L.distr_color_stage_forward_batch(
+        engine.ctx.h, C.byref(cfg), B, p(Rc), p(Tc), p(z), p(m), p(n), p(lat), stride, None if st is None else C.byref(st), p(rgb), p(ws), ws.numel(),
+        p(lists.get('index')), p(lists.get('xyz')), p(lists.get('totals')), engine.ctx.stream()))
+    saved = dict(lists, ws=ws, bwd_bytes=bb.value, views=(Rc, Tc, z, n), lat=lat, stride=stride, lights=(loc, en, st), B=B, P=P)
+    return rgb, saved
+
+
+class ColorStageFunction(torch.autograd.Function):
+    """The colour stage of B rendered views as ONE node: (color_codes (1, cs) / (B, cs), shape_codes (1, 256) / (B, 256), R (B,3,3),
+    T (B,3), normal (B,H,W,3) or None) + observations (zdepth, mask, lights, energies) -> rgb (B,H,W,3). backward =
+    distr_color_stage_backward_batch: gradients to both codes (summed over the views of a shared code), the cameras and -- with lights --
+    the normal image. detach_color: the colours are constants (render(no_grad=True)); only the shading terms carry gradient."""
+
+    @staticmethod
+    def forward(ctx, color_codes, shape_codes, R, T, normal, engine, cfg, zdepth, mask, lights, energies, detach_color):
+        rgb, saved = color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal, lights, energies)
+        ctx.engine, ctx.cfg, ctx.saved, ctx.detach_color = engine, cfg, saved, bool(detach_color)
+        ctx.generation = engine.generation
+        ctx.codes = (color_codes.detach(), shape_codes.detach())
+        ctx.shapes = (R.shape, T.shape, None if normal is None else normal.shape)
+        ctx.in_meta = tuple((t.device, t.dtype) for t in (R, T)) + (None if normal is None else (normal.device, normal.dtype),)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g):
+        engine, cfg, sv = ctx.engine, ctx.cfg, ctx.saved
+        _check_generation(ctx)
+        dev, L, p = engine.device, engine.ctx.L, binding.ptr
+        B, P = sv['B'], sv['P']
+        Rc, Tc, z, n = sv['views']
+        loc, en, st = sv['lights']
+        need_c, need_s, need_R, need_T, need_n = ctx.needs_input_grad[:5]
+        gs = _f32c(g, dev).reshape(-1)
+        g_lat = torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev) if (need_c or need_s) and not ctx.detach_color else None
+        g_R = torch.empty(B, 9, dtype=torch.float32, device=dev) if need_R else None
+        g_T = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_T else None
+        g_n = torch.empty(B, cfg.H, cfg.W, 3, dtype=torch.float32, device=dev) if need_n and st is not None else None
+        ws_b = torch.empty(sv['bwd_bytes'], dtype=torch.uint8, device=dev)
+        engine.ctx.check(L.distr_color_stage_backward_batch(
+            engine.ctx.h, C.byref(cfg), B, p(Rc), p(Tc), p(z), p(n), p(sv['lat']), sv['stride'], None if st is None else C.byref(st), p(sv['ws']),
+            sv['ws'].numel(), p(gs), p(g_lat), p(g_R), p(g_T), p(g_n), p(ws_b), ws_b.numel(), engine.ctx.stream()))
+        g_c, g_s = _split_code_grad(g_lat, *ctx.codes) if g_lat is not None else (None, None)
+        rs, ts, ns = ctx.shapes
+        cam = [None if t is None else t.reshape(sh).to(device=d, dtype=dt) for t, sh, (d, dt) in zip((g_R, g_T), (rs, ts), ctx.in_meta[:2])]
+        g_n = None if g_n is None else g_n.reshape(ns).to(device=ctx.in_meta[2][0], dtype=ctx.in_meta[2][1])
+        return ((g_c if need_c else None), (g_s if need_s else None), cam[0], cam[1], g_n) + (None,) * 7
+
+
+def color_stage_call(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal=None, lights=None, energies=None, detach_color=False):
+    """The colour images of B rendered views (color_stage_forward), on the tape unless nothing requires grad. detach_color: see
+    ColorStageFunction."""
+    ins = (R, T, normal) if detach_color else (color_codes, shape_codes, R, T, normal)
+    if lights is None and detach_color:
+        ins = ()
+    if torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in ins):
+        return ColorStageFunction.apply(color_codes, shape_codes, R, T, normal if lights is not None else None, engine, cfg, zdepth, mask, lights, energies,
+                                        detach_color)
+    return color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal, lights, energies)[0]
+
+
+def color_relight(engine, cfg, color, normal, zdepth, mask, R, T, lights, energies=None):
+    """distr_color_relight: F light sets (F, M, 3) on ONE rendered view -> (F, H, W, 3) = color * shading term of frame f; byte for byte
+    the lit colour stage of that view with frame f's lights. Forward only."""
+    dev, L, p = engine.device, engine.ctx.L, binding.ptr
+    loc = _f32c(lights, dev)
+    if loc.dim() != 3 or loc.shape[2] != 3 or loc.shape[0] < 1 or loc.shape[1] < 1:
+        raise ValueError('lighting_locations has shape %s; relight takes (F, M, 3)' % (tuple(lights.shape),))
+    F = loc.shape[0]
+    loc, en, st = color_lights(dev, F, loc, energies)
+    Rc, Tc, z, m, n, B, P = _stage_views(engine, cfg, R, T, zdepth, mask, normal, True)
+    col = _f32c(color, dev).reshape(-1)
+    if B != 1 or col.numel() != 3 * P:
+        raise ValueError('relight takes ONE view: R (3,3), T (3), color / normal (%d, %d, 3), Zdepth / mask (%d, %d)' % (cfg.H, cfg.W, cfg.H, cfg.W))
+    out = torch.empty(F, cfg.H, cfg.W, 3, dtype=torch.float32, device=dev)
+    engine.ctx.check(L.distr_color_relight(engine.ctx.h, C.byref(cfg), F, p(Rc), p(Tc), p(z), p(m), p(n), p(col), C.byref(st), p(out), engine.ctx.stream()))
+    return out

@@ -373,5 +373,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_multi.h"
 /* normal-map losses through the decoder's second path: the term distr_render_backward omits, opt-in */
 #include "distr_normal_grad.h"
+/* the colour decoder on a segmented point list; the colour stage of a batch of rendered views */
+#include "distr_color_batch.h"
 
 #endif /* DISTR_H_ */
