@@ -41,6 +41,7 @@ struct distr_ctx {
   bool profiling = false;
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
   int tail16_threshold = 4096;  // t16: ... and on 16-ray tiles (16x16x4 MFMA)
+  bool dense_compact = true;    // DISTR_DENSE_COMPACT=0: the exact-f32 64-ray tile multiplies every hidden unit, live for the tile or not (a time knob)
   bool save_masks = true;       // save ReLU masks in the forward so that the backward skips the decoder recompute
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
@@ -128,6 +129,17 @@ void pack_fragments(const float* W, int K, int O, float* dst) {
           float* d = dst + ((((size_t)g * 4 + w) * NOB + ob) * 64 + lane) * 4;
           for (int s = 0; s < 4; ++s) d[s] = W[(size_t)o * K + 8 * g + 2 * s + h];
         }
+}
+
+// k-major pack for the compacted 64-ray tile (distr_mlp.hpp, "compacted 64-ray tile"): one row of O floats per input feature k, a wave's
+// rows interleaved so that the 4 (NOB) floats at [RW * w + NOB * j + ob] are lane j's A operands of all its row blocks:
+//   dst[k * O + RW * w + NOB * j + ob] = W[RW * w + 32 * ob + j][k],  RW = 32 * NOB rows per wave, NOB = O / 128
+void pack_kmajor(const float* W, int K, int O, float* dst) {
+  const int NOB = O / 128, RW = 32 * NOB;
+  for (int k = 0; k < K; ++k)
+    for (int w = 0; w < 4; ++w)
+      for (int j = 0; j < 32; ++j)
+        for (int ob = 0; ob < NOB; ++ob) dst[(size_t)k * O + RW * w + NOB * j + ob] = W[(size_t)(RW * w + 32 * ob + j) * K + k];
 }
 
 // A-fragments of v_mfma_f32_16x16x4_f32 (distr_mlp.hpp::dense16):
@@ -620,6 +632,14 @@ int distr_create_abi(distr_ctx** out, int hip_device, uint32_t abi_version) {
   if (const char* e = getenv("DISTR_XCHG_TS")) ctx->xchg_ts = atoi(e) != 0;
   if (const char* e = getenv("DISTR_CLUSTER_TEST_ABORT")) ctx->cluster_test_abort = atoi(e);     // 1: abort at assembly; 2: member 0 drops out behind its last slice
   if (const char* e = getenv("DISTR_SAVE_MASKS")) ctx->save_masks = atoi(e) != 0;
+  if (const char* e = getenv("DISTR_DENSE_COMPACT")) {
+    if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
+      ctx->err = std::string("DISTR_DENSE_COMPACT must be 0 or 1 (got '") + e + "')";
+      *out = ctx;
+      return DISTR_ERR_INVALID_ARG;
+    }
+    ctx->dense_compact = e[0] == '1';
+  }
   if (const char* e = getenv("DISTR_STICKY")) ctx->sticky = atoi(e) != 0;
   if (const char* e = getenv("DISTR_XCHG_SC1")) ctx->xchg_sc1 = atoi(e) != 0;
   if (const char* e = getenv("DISTR_CLUSTER_SPREAD")) ctx->cluster_spread = atoi(e) != 0;
@@ -673,7 +693,7 @@ const char* distr_last_error(const distr_ctx* ctx) { return ctx ? ctx->err.c_str
 // 509..511) and lin4 K = 512. The split-bf16 / split-f16 planes are packed for C = 256 only (the only decoders they may run).
 static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const float* w, size_t n_floats, float** dev_buf, DecoderDev& D,
                          DecoderDev16* D16, DecoderB6* B6 = nullptr, uint32_t** dev_buf_b6 = nullptr, DecoderH3* H3 = nullptr,
-                         bool* h3_ok = nullptr) {
+                         bool* h3_ok = nullptr, bool compact = false) {
   if (rows3 < 1 || rows3 > 509) return fail(ctx, DISTR_ERR_UNSUPPORTED, "lin3 with %d rows does not fit the 509-row tile", rows3);
   const bool wide = rows3 > 253;
   const int R3 = wide ? 509 : 253;         // row of lin3's output (and column of lin4) where xyz is carried
@@ -717,6 +737,12 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
     offWb[l] = reserve(Wt.size());
     pack_fragments(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], host.data() + offWb[l]);
   }
+  size_t offWk = 0;
+  compact = compact && !wide;     // the compacted tile exists in the narrow layout only
+  if (compact) {
+    offWk = reserve(WK_FLOATS);
+    for (int l = 1; l < 8; ++l) pack_kmajor(Wp[l].data(), Kp[l], Op[l], host.data() + offWk + wk_offset(l));
+  }
   size_t offW16[8];
   for (int l = 0; l < 8; ++l) {
     const int K16 = (l == 0) ? 16 : Kp[l];
@@ -752,6 +778,7 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
   D.b8 = b[8][0];
   D.b8x[0] = nout > 1 ? b[8][1] : 0.f; D.b8x[1] = nout > 2 ? b[8][2] : 0.f;
   D.nlat = nlat;
+  D.Wk = compact ? d + offWk : nullptr;
   if (D16) for (int l = 0; l < 8; ++l) D16->Wf[l] = d + offW16[l];
 #ifdef DISTR_DIAG
   // DIAGNOSTICS BUILDS ONLY (-DDISTR_DIAG; values are wrong): every 512 x 512 layer of the 16-ray / cluster tiles reads lin1's fragments, so
@@ -821,9 +848,9 @@ int distr_set_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, const floa
   const int nlat = desc->latent_size;
   int rc;
   if (nlat == LAT) {
-    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok);
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok, ctx->dense_compact);
   } else {   // no split-arithmetic planes: bf16x6 / f16x3 refuse other code lengths (check_cfg, distr_mlp_eval_*)
-    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16);
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, nullptr, nullptr, nullptr, nullptr, ctx->dense_compact);
     if (!rc && ctx->dec_buf_b6) { HIP_TRY(hipFree(ctx->dec_buf_b6)); ctx->dec_buf_b6 = nullptr; ctx->B6 = DecoderB6{}; ctx->H3 = DecoderH3{}; ctx->h3_ok = false; }
   }
   if (rc) return rc;
@@ -988,16 +1015,21 @@ inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
 #define DISTR_LAUNCH_IF(cond, kernel, ...) \
   if (cond) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTHREADS), 0, s, __VA_ARGS__); LAUNCH_CHECK(what); return DISTR_OK; }
 // per family: which run-time values select a line of the list, and the kernel's arguments
-#define DISTR_TRY_STEP(K, AR) DISTR_LAUNCH_IF(keep == K && arith == AR, (k_step<K, AR>), A, ctx->D, ctx->D16, G)
+#define DISTR_TRY_STEP(K, AR, C) DISTR_LAUNCH_IF(keep == K && arith == AR && compact == C, (k_step<K, AR, C>), A, ctx->D, ctx->D16, G)
 #define DISTR_TRY_TAIL(K) DISTR_LAUNCH_IF(keep == K, (k_tail<K>), A, ctx->D, ctx->D16)
-#define DISTR_TRY_MARCH(M, RB, K, AR, W) \
-  DISTR_LAUNCH_IF(mode == M && rb == RB && keep == K && arith == AR && wide == W, (k_march<M, RB, K, AR, W>), A, ctx->D)
+#define DISTR_TRY_MARCH(M, RB, K, AR, W, C) \
+  DISTR_LAUNCH_IF(mode == M && rb == RB && keep == K && arith == AR && wide == W && compact == C, (k_march<M, RB, K, AR, W, C>), A, ctx->D)
 #define DISTR_TRY_MARCH16(M, K) DISTR_LAUNCH_IF(mode == M && keep == K, (k_march16<M, K>), A, ctx->D, ctx->D16)
 #define DISTR_TRY_BWD(M, RB, AR, W) DISTR_LAUNCH_IF(mode == M && rb == RB && arith == AR && wide == W, (k_bwd<M, RB, AR, W>), B, ctx->D)
 
+// The compacted 64-ray tile (DISTR_DENSE_COMPACT) is a column of the lists: taken wherever the exact-f32 64-ray tile of the narrow layout
+// runs and the context packed the k-major weights for it (D.Wk); every other tile keeps the dense loop.
+inline bool compact_tile(const distr_ctx* ctx, int rb, int arith) { return ctx->D.Wk != nullptr && rb == 2 && arith == 0; }
+
 int launch_step(distr_ctx* ctx, const char* what, bool keep, int arith, unsigned grid, hipStream_t s, const MarchArgs& A, const StepGrid& G) {
+  const bool compact = compact_tile(ctx, 2, arith);
   DISTR_ALL_GROUPS(DISTR_TRY_STEP, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
-  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_step<%d, %d> (distr_inst.hpp)", (int)keep, arith);
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_step<%d, %d, %d> (distr_inst.hpp)", (int)keep, arith, (int)compact);
 }
 
 int launch_tail(distr_ctx* ctx, const char* what, bool keep, unsigned grid, hipStream_t s, const MarchArgs& A) {
@@ -1006,8 +1038,9 @@ int launch_tail(distr_ctx* ctx, const char* what, bool keep, unsigned grid, hipS
 }
 
 int launch_march(distr_ctx* ctx, const char* what, int mode, int rb, bool keep, int arith, bool wide, unsigned grid, hipStream_t s, const MarchArgs& A) {
+  const bool compact = compact_tile(ctx, rb, arith);      // (D.Wk is not packed for the wide layout)
   DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_TRY_MARCH, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
-  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_march<%d, %d, %d, %d, %d> (distr_inst.hpp)", mode, rb, (int)keep, arith, (int)wide);
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_march<%d, %d, %d, %d, %d, %d> (distr_inst.hpp)", mode, rb, (int)keep, arith, (int)wide, (int)compact);
 }
 
 int launch_march16(distr_ctx* ctx, const char* what, int mode, bool keep, unsigned grid, hipStream_t s, const MarchArgs& A) {
@@ -1528,7 +1561,8 @@ int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz,
   PointList pl = plain_list(n);
   const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, n > 0 && xyz && out && layer >= 0 && layer <= 7, ws, ws_bytes, false, s);
   if (rc) return rc;
-  hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, layer, out, ctx->D, (long long*)nullptr);
+  if (ctx->D.Wk) hipLaunchKernelGGL((k_debug_layer<2, true>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, layer, out, ctx->D, (long long*)nullptr);
+  else hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, layer, out, ctx->D, (long long*)nullptr);
   LAUNCH_CHECK("k_debug_layer");
   return DISTR_OK;
 }
@@ -1544,7 +1578,8 @@ int distr_debug_tile_timing(distr_ctx* ctx, const float* latent, const float* xy
   PointList pl = plain_list(n);
   const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, n > 0 && xyz && sdf_out && ts_out, ws, ws_bytes, false, s);
   if (rc) return rc;
-  hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, 8, sdf_out, ctx->D, ts_out);
+  if (ctx->D.Wk) hipLaunchKernelGGL((k_debug_layer<2, true>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, 8, sdf_out, ctx->D, ts_out);
+  else hipLaunchKernelGGL((k_debug_layer<2>), dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, 8, sdf_out, ctx->D, ts_out);
   LAUNCH_CHECK("k_debug_layer<timing>");
   return DISTR_OK;
 }

@@ -13,31 +13,31 @@
 namespace distr {
 
 // Every list takes one macro per kernel family and calls it once per variant, in the order the unit emits them:
-//   STEP(KEEP, ARITH)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE)
+//   STEP(KEEP, ARITH, COMPACT)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE, COMPACT)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE)
 // KEEP = save the ReLU masks, RB = 32-ray blocks of a tile, ARITH = DISTR_ARITH_* (0 f32, 1 bf16x6, 2 f16x3), WIDE = the layout for
-// code lengths below 256.
+// code lengths below 256, COMPACT = the 64-ray tile walks the live hidden units of a tile only (exact f32, narrow layout; distr_mlp.hpp).
 
 // the full-resolution step of the exact-f32 march (the headline kernel)
 #define DISTR_GROUP_1(STEP, TAIL, MARCH, MARCH16, BWD) \
-  STEP(true, 0) STEP(false, 0)
+  STEP(true, 0, false) STEP(false, 0, false)
 // the persistent tail launch
 #define DISTR_GROUP_2(STEP, TAIL, MARCH, MARCH16, BWD) \
   TAIL(true) TAIL(false)
 // exact-f32 march tiles: coarse levels, 'trivial', point lists; 16-ray / cluster tiles
 #define DISTR_GROUP_3(STEP, TAIL, MARCH, MARCH16, BWD) \
-  MARCH(MODE_EVAL, 2, false, 0, false) \
-  MARCH(MODE_COARSE, 1, true, 0, false) MARCH(MODE_COARSE, 1, false, 0, false) MARCH(MODE_COARSE, 2, true, 0, false) MARCH(MODE_COARSE, 2, false, 0, false) \
-  MARCH(MODE_FINE, 2, true, 0, false) MARCH(MODE_FINE, 2, false, 0, false) \
+  MARCH(MODE_EVAL, 2, false, 0, false, false) \
+  MARCH(MODE_COARSE, 1, true, 0, false, false) MARCH(MODE_COARSE, 1, false, 0, false, false) MARCH(MODE_COARSE, 2, true, 0, false, false) MARCH(MODE_COARSE, 2, false, 0, false, false) \
+  MARCH(MODE_FINE, 2, true, 0, false, false) MARCH(MODE_FINE, 2, false, 0, false, false) \
   MARCH16(MODE_EVAL, false) MARCH16(MODE_COARSE, true) MARCH16(MODE_COARSE, false)
 // the step kernel in the two opt-in arithmetics
 #define DISTR_GROUP_4(STEP, TAIL, MARCH, MARCH16, BWD) \
-  STEP(true, 1) STEP(false, 1) STEP(true, 2) STEP(false, 2)
+  STEP(true, 1, false) STEP(false, 1, false) STEP(true, 2, false) STEP(false, 2, false)
 // march tiles in the two opt-in arithmetics
 #define DISTR_GROUP_5(STEP, TAIL, MARCH, MARCH16, BWD) \
-  MARCH(MODE_COARSE, 1, true, 1, false) MARCH(MODE_COARSE, 1, false, 1, false) MARCH(MODE_COARSE, 2, true, 1, false) MARCH(MODE_COARSE, 2, false, 1, false) \
-  MARCH(MODE_FINE, 2, true, 1, false) MARCH(MODE_FINE, 2, false, 1, false) \
-  MARCH(MODE_COARSE, 1, true, 2, false) MARCH(MODE_COARSE, 1, false, 2, false) MARCH(MODE_COARSE, 2, true, 2, false) MARCH(MODE_COARSE, 2, false, 2, false) \
-  MARCH(MODE_FINE, 2, true, 2, false) MARCH(MODE_FINE, 2, false, 2, false)
+  MARCH(MODE_COARSE, 1, true, 1, false, false) MARCH(MODE_COARSE, 1, false, 1, false, false) MARCH(MODE_COARSE, 2, true, 1, false, false) MARCH(MODE_COARSE, 2, false, 1, false, false) \
+  MARCH(MODE_FINE, 2, true, 1, false, false) MARCH(MODE_FINE, 2, false, 1, false, false) \
+  MARCH(MODE_COARSE, 1, true, 2, false, false) MARCH(MODE_COARSE, 1, false, 2, false, false) MARCH(MODE_COARSE, 2, true, 2, false, false) MARCH(MODE_COARSE, 2, false, 2, false, false) \
+  MARCH(MODE_FINE, 2, true, 2, false, false) MARCH(MODE_FINE, 2, false, 2, false, false)
 // backward kernels
 #define DISTR_GROUP_6(STEP, TAIL, MARCH, MARCH16, BWD) \
   BWD(BWD_FULL, 2, 0, false) BWD(BWD_POINTGRAD, 2, 0, false) \
@@ -45,15 +45,23 @@ namespace distr {
   BWD(BWD_SAVED, 2, 0, false) BWD(BWD_SAVED, 2, 1, false) BWD(BWD_SAVED, 2, 2, false)
 // the wide layout (code length < 256): 64-ray march tiles; 64- and 32-sample backward tiles
 #define DISTR_GROUP_7(STEP, TAIL, MARCH, MARCH16, BWD) \
-  MARCH(MODE_EVAL, 2, false, 0, true) MARCH(MODE_COARSE, 2, true, 0, true) MARCH(MODE_COARSE, 2, false, 0, true) \
-  MARCH(MODE_FINE, 2, true, 0, true) MARCH(MODE_FINE, 2, false, 0, true) \
+  MARCH(MODE_EVAL, 2, false, 0, true, false) MARCH(MODE_COARSE, 2, true, 0, true, false) MARCH(MODE_COARSE, 2, false, 0, true, false) \
+  MARCH(MODE_FINE, 2, true, 0, true, false) MARCH(MODE_FINE, 2, false, 0, true, false) \
   BWD(BWD_FULL, 2, 0, true) BWD(BWD_POINTGRAD, 2, 0, true) BWD(BWD_SAVED, 2, 0, true) BWD(BWD_SAVED, 1, 0, true)
 
-constexpr int DISTR_NUM_INST_GROUPS = 7;
+// the compacted 64-ray tile (DISTR_DENSE_COMPACT, the default): the step kernel ...
+#define DISTR_GROUP_8(STEP, TAIL, MARCH, MARCH16, BWD) \
+  STEP(true, 0, true) STEP(false, 0, true)
+// ... and the 64-ray march tiles
+#define DISTR_GROUP_9(STEP, TAIL, MARCH, MARCH16, BWD) \
+  MARCH(MODE_EVAL, 2, false, 0, false, true) MARCH(MODE_COARSE, 2, true, 0, false, true) MARCH(MODE_COARSE, 2, false, 0, false, true) \
+  MARCH(MODE_FINE, 2, true, 0, false, true) MARCH(MODE_FINE, 2, false, 0, false, true)
+
+constexpr int DISTR_NUM_INST_GROUPS = 9;
 
 #define DISTR_ALL_GROUPS(...) \
   DISTR_GROUP_1(__VA_ARGS__) DISTR_GROUP_2(__VA_ARGS__) DISTR_GROUP_3(__VA_ARGS__) DISTR_GROUP_4(__VA_ARGS__) DISTR_GROUP_5(__VA_ARGS__) \
-  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__)
+  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__) DISTR_GROUP_8(__VA_ARGS__) DISTR_GROUP_9(__VA_ARGS__)
 #define DISTR_NO_VARIANT(...)      // for the families a use of the lists does not ask for
 
 // in a group's translation unit only that group is instantiated; the launching unit declares all of them extern
@@ -67,9 +75,9 @@ constexpr int DISTR_NUM_INST_GROUPS = 7;
 #define DISTR_INST_LIST DISTR_ALL_GROUPS
 #endif
 
-#define DISTR_K_STEP(K, AR) DISTR_INST_DEF __global__ void k_step<K, AR>(MarchArgs, DecoderDev, DecoderDev16, StepGrid);
+#define DISTR_K_STEP(K, AR, C) DISTR_INST_DEF __global__ void k_step<K, AR, C>(MarchArgs, DecoderDev, DecoderDev16, StepGrid);
 #define DISTR_K_TAIL(K) DISTR_INST_DEF __global__ void k_tail<K>(MarchArgs, DecoderDev, DecoderDev16);
-#define DISTR_K_MARCH(M, RB, K, AR, W) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR, W>(MarchArgs, DecoderDev);
+#define DISTR_K_MARCH(M, RB, K, AR, W, C) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR, W, C>(MarchArgs, DecoderDev);
 #define DISTR_K_MARCH16(M, K) DISTR_INST_DEF __global__ void k_march16<M, K>(MarchArgs, DecoderDev, DecoderDev16);
 #define DISTR_K_BWD(M, RB, AR, W) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR, W>(BwdArgs, DecoderDev);
 

@@ -766,7 +766,7 @@ template <int RB, int ARITH> struct TileSmem { using type = Smem<RB>; };
 template <int RB> struct TileSmem<RB, 1> { using type = SmemB6<RB>; };
 template <int RB> struct TileSmem<RB, 2> { using type = SmemH3<RB>; };
 
-template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false>
+template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
 __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev& D, typename TileSmem<RB, ARITH>::type& S, int tile, int ntile_grid,
                                            int which, int origin_tile) {
   constexpr int TILE = 32 * RB;
@@ -854,7 +854,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
 
   uint32_t masks[8][4];
   float pre;
-  if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true, WIDE>(D, c0, c4, S, masks);
+  if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true, WIDE, COMPACT>(D, c0, c4, S, masks);
   else if constexpr (ARITH == 1) pre = mlp_forward_b6<RB, KEEP>(D, A.B6, c0, c4, S, masks);
   else pre = mlp_forward_h3<RB, KEEP>(D, A.H3, c0, c4, S, masks);
 
@@ -921,11 +921,11 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
 }
 
 // WIDE: decoders with a code length below 256 (distr_mlp.hpp, stage_bias); 64-ray tiles, exact f32 only
-template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false>
+template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
 __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_march(MarchArgs A, DecoderDev D) {
   static_assert(!WIDE || (RB == 2 && ARITH == 0), "the wide layout: 64-ray tiles, exact f32");
   __shared__ typename TileSmem<RB, ARITH>::type S;
-  (void)march_tile<MODE, RB, KEEP, ARITH, WIDE>(A, D, S, (int)blockIdx.x, (int)gridDim.x, A.which, A.origin_tile);
+  (void)march_tile<MODE, RB, KEEP, ARITH, WIDE, COMPACT>(A, D, S, (int)blockIdx.x, (int)gridDim.x, A.which, A.origin_tile);
 }
 
 // KEEP, cluster tile of CL members: this member's share of the rays' mask blocks. Every member recorded the ReLU bits of the rows IT
@@ -1702,7 +1702,7 @@ __global__ void __launch_bounds__(256, 1) k_tail(MarchArgs A, DecoderDev D, Deco
 // Against three launches per step this saves two empty launches (4-5 us each) on almost every step.
 struct StepGrid { int32_t n64, n32, n16; };
 
-template <bool KEEP, int ARITH = 0>
+template <bool KEEP, int ARITH = 0, bool COMPACT = false>
 __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, DecoderDev16 D16, StepGrid G) {
   __shared__ __attribute__((aligned(16))) unsigned char raw[(sizeof(Smem<2>) > sizeof(SmemB6<2>)) ? sizeof(Smem<2>) : sizeof(SmemB6<2>)];
   static_assert(sizeof(Smem<2>) >= sizeof(Smem<1>) && sizeof(Smem<2>) >= sizeof(Smem16CLX) && sizeof(SmemB6<2>) >= sizeof(SmemB6<1>), "role shared memory");
@@ -1717,7 +1717,7 @@ __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, Deco
     if constexpr (ARITH == 0) march_tile16<MODE_FINE, KEEP>(A, D, D16, *reinterpret_cast<Smem16CLX*>(raw), b - G.n32, A.origin_tile);
   } else {
     for (int t = b - G.n32 - G.n16;; t += G.n64) {
-      if (!march_tile<MODE_FINE, 2, KEEP, ARITH>(A, D, *reinterpret_cast<typename TileSmem<2, ARITH>::type*>(raw), t, 0x7fffffff, 64, 0)) break;
+      if (!march_tile<MODE_FINE, 2, KEEP, ARITH, false, COMPACT>(A, D, *reinterpret_cast<typename TileSmem<2, ARITH>::type*>(raw), t, 0x7fffffff, 64, 0)) break;
       __syncthreads();       // the tile's last LDS reads (mask store) are done before the next tile's points are written
     }
   }
@@ -1815,7 +1815,7 @@ DISTR_GLOBAL void __launch_bounds__(256, 1) k_color_bwd(const float* __restrict_
 }
 
 // test/debug only: post-activation of layer `layer` for n points -> out[n][512] (see tests/test_gpu_parity.py)
-template <int RB>
+template <int RB, bool COMPACT = false>
 __global__ void __launch_bounds__(256, (RB == 1) ? 2 : 1) k_debug_layer(const float* xyz, int64_t n, const float* c0c4, int layer,
                                                                         float* out, DecoderDev D, long long* ts_out) {
   constexpr int TILE = 32 * RB;
@@ -1830,7 +1830,7 @@ __global__ void __launch_bounds__(256, (RB == 1) ? 2 : 1) k_debug_layer(const fl
   __syncthreads();
   uint32_t masks[8][4];
   long long* ts = ts_out ? ts_out + (size_t)blockIdx.x * 40 : nullptr;
-  const float pre = mlp_forward<RB, false, true>(D, c0c4, c0c4 + HID, S, masks, layer, ts);
+  const float pre = mlp_forward<RB, false, true, false, false, COMPACT>(D, c0c4, c0c4 + HID, S, masks, layer, ts);
   if (ts_out) {   // timing mode: whole forward, no activation dump
     if (tid == 0) { ts[36] = (long long)__builtin_readcyclecounter(); ts[37] = (long long)wall_clock64(); }
     if (tid < TILE && base + tid < n) out[base + tid] = tanh_spec(pre);

@@ -82,7 +82,13 @@ struct DecoderDev {
   float b8;             // lin8 bias of row 0
   float b8x[2];         // lin8 biases of rows 1, 2 (colour decoder)
   int32_t nlat;         // latent length folded into c0 / c4 (the code length C of the SDF decoder; 256 + color_size for the colour decoder)
+  const float* Wk;      // k-major forward packs of lin1..lin7 (pack_kmajor; layer l at wk_offset(l)) for the compacted 64-ray tile; nullptr =
+                        // DISTR_DENSE_COMPACT=0 (or the wide layout): the tile multiplies every hidden unit, live for the tile or not
 };
+
+// float offset of layer l's k-major pack in DecoderDev::Wk (narrow layout: lin3 has 256 rows, lin4 256 input features)
+__host__ __device__ constexpr int wk_offset(int l) { return (l - 1) * (HID * HID) - (l > 3 ? HID * HID / 2 : 0) - (l > 4 ? HID * HID / 2 : 0); }
+constexpr int WK_FLOATS = 6 * HID * HID;
 
 // A tile = RB blocks of 32 rays. RB=2: 64 rays, 133 KiB LDS, one workgroup per CU. RB=1: 32 rays, 67 KiB LDS, two
 // workgroups per CU (each hides the other's prologue / epilogue / barrier stalls; half the tile latency).
@@ -356,6 +362,169 @@ __device__ __forceinline__ void writeback(float* X, const f32x16 (&acc)[NOB][RB]
   __builtin_amdgcn_sched_barrier(0);
 }
 
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f);     // (defined with the cluster tile below)
+
+// ---------------------------------------------------------------------------------------- compacted 64-ray tile
+// A hidden unit that is <= 0 for all 64 rays of a tile stores +0 for every ray; its products in the next layer are no-op links of the
+// k-ordered fma chains (fma(w, +0, acc) = acc up to the sign of a zero, which the next integer ReLU erases; weights are finite:
+// decoder_pack.validate). The compacting write-back therefore stores only the LIVE rows, at consecutive positions of X in ascending
+// feature order, zero rows up to the next multiple of 16 (at least 32), and the feature index of every position in `klist`; the next
+// layer (dense_asm_compact_*) walks positions instead of features and gathers its weights from the k-major pack by klist.
+// The bookkeeping lives in S.part .. S.aux (4 KiB, idle during the layers; the dense loop's tuple scratch in the other mode).
+struct CompactLds {
+  uint32_t postab[HID];   // byte offset from X of the row a unit is stored to: position * 256, or the trash row for a dead unit
+  uint16_t klist[HID];    // feature index of position p
+  uint32_t bits[16];      // live bits of the layer being written back: word 4 * wave + ob, bit = row within the block (feature order)
+  uint32_t pad_[4];
+  float trash[64];        // where the (+0) rows of dead units go
+};
+
+__device__ __forceinline__ uint32_t spread4(uint32_t x) {   // bit 4q + i -> bit 8q + i
+  return (x & 0xfu) | ((x & 0xf0u) << 4) | ((x & 0xf00u) << 8) | ((x & 0xf000u) << 12);
+}
+
+// Before the layer's first barrier: the ReLU bits of this wave's rows (KEEP: into mask[], exactly as writeback() forms them), OR-ed
+// over the tile's 64 rays, published as the wave's words of C.bits.
+template <int NOB, bool KEEP>
+__device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&acc)[NOB][2], int wave, int lane, uint32_t (&mask)[4]) {
+  uint32_t lw[4] = {0u, 0u, 0u, 0u};
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) {
+    uint32_t m = 0u;
+    if (KEEP) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m |= min((uint32_t)max(__float_as_int(acc[ob][rb][r]), 0), 1u) << (rb * 16 + r);
+      }
+      asm volatile("" : "+v"(m));
+      mask[ob] = m;
+      lw[ob] = (m | (m >> 16)) & 0xffffu;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) m |= min((uint32_t)max(max(__float_as_int(acc[ob][0][r]), __float_as_int(acc[ob][1][r])), 0), 1u) << r;
+      asm volatile("" : "+v"(m));
+      lw[ob] = m;
+    }
+  }
+  uint32_t a = lw[0] | (lw[1] << 16), b = lw[2] | (lw[3] << 16);
+  // OR over the 32 lanes of each half-wave (ds_swizzle, xor butterfly)
+#define DISTR_OR_SWZ(x) do { a |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)a, ((x) << 10) | 0x1f); if (NOB == 4) b |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)b, ((x) << 10) | 0x1f); } while (0)
+  DISTR_OR_SWZ(1); DISTR_OR_SWZ(2); DISTR_OR_SWZ(4); DISTR_OR_SWZ(8); DISTR_OR_SWZ(16);
+#undef DISTR_OR_SWZ
+  const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, 32);
+  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32);
+  // lane (j, h) holds rows (r & 3) + 8 * (r >> 2) + 4 * h of a block: interleave the two halves' nibbles into feature order
+  const uint32_t w0 = spread4(a0 & 0xffffu) | (spread4(a1 & 0xffffu) << 4), w1 = spread4(a0 >> 16) | (spread4(a1 >> 16) << 4);
+  const uint32_t w2 = spread4(b0 & 0xffffu) | (spread4(b1 & 0xffffu) << 4), w3 = spread4(b0 >> 16) | (spread4(b1 >> 16) << 4);
+  if (lane == 0) *reinterpret_cast<uint4*>(&C.bits[4 * wave]) = make_uint4(w0, w1, w2, w3);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Between the layer's two barriers: positions from the published bits, the live rows to X[pos], klist, the zero rows of the padding.
+// XYZ (lin3): the three xyz rows follow the live rows as features 253..255 (lin4's xyz columns). Returns the padded row count.
+template <int NOB, bool XYZ>
+__device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const float* xyz, const f32x16 (&acc)[NOB][2], int wave, int lane) {
+  constexpr int RW = 32 * NOB;             // rows of a wave
+  const int tid = threadIdx.x;
+  const int h = lane >> 5, j = lane & 31;
+  uint32_t cnt[4], own[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[4 * w]);
+    cnt[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)));
+  }
+  {
+    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[4 * wave]);
+    own[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x); own[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
+    own[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z); own[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w);
+  }
+  const uint32_t base = (wave > 0 ? cnt[0] : 0u) + (wave > 1 ? cnt[1] : 0u) + (wave > 2 ? cnt[2] : 0u);
+  const uint32_t nlive = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  const uint32_t trash_off = lds_off(C.trash) - lds_off(X);
+  // lane <-> unit: where each of the wave's rows goes, and the list entry of the live ones
+#pragma unroll
+  for (int t = 0; t < NOB / 2; ++t) {
+    const uint32_t word = h ? own[2 * t + 1] : own[2 * t];
+    uint32_t below = (uint32_t)__popc(word & ((1u << j) - 1u)) + (h ? (uint32_t)__popc(own[2 * t]) : 0u);
+    if (t) below += (uint32_t)__popc(own[0]) + (uint32_t)__popc(own[1]);
+    const uint32_t pos = base + below;
+    const bool live = (word >> j) & 1u;
+    const uint32_t f = (uint32_t)wave * RW + 64 * t + lane;
+    C.postab[f] = live ? pos * 256u : trash_off;
+    if (live) C.klist[pos] = (uint16_t)f;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  char* xl = reinterpret_cast<char*>(X) + 4 * j;
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint4 pt = *reinterpret_cast<const uint4*>(&C.postab[wave * RW + 32 * ob + 8 * q + 4 * h]);
+      const uint32_t po[4] = {pt.x, pt.y, pt.z, pt.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float* dst = reinterpret_cast<float*>(xl + po[i]);
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+          int bits = __float_as_int(acc[ob][rb][4 * q + i]);
+          asm volatile("" : "+v"(bits));      // opaque: the ReLU values formed for the live bits must not stay in VGPRs across the barrier
+          dst[32 * rb] = __int_as_float(max(bits, 0));
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  uint32_t nl = nlive;
+  if (XYZ) {
+    if (tid < 3 * 64) {
+      const int k = tid >> 6;
+      X[(nlive + k) * 64 + (tid & 63)] = xyz[tid];
+      if ((tid & 63) == 0) C.klist[nlive + k] = (uint16_t)(253 + k);
+    }
+    nl += 3;
+  }
+  uint32_t npad = (nl + 15u) & ~15u;
+  if (npad < 32u) npad = 32u;
+  for (uint32_t p = nl + (uint32_t)wave; p < npad; p += 4) {      // zero rows: exact no-op links; their list entries name any valid unit
+    X[p * 64 + lane] = 0.f;
+    if (lane == 0) C.klist[p] = 0;
+  }
+  return npad;
+}
+
+// the compacting counterpart of "barrier, writeback(), barrier"
+template <int NOB, bool KEEP, bool XYZ, class SM>
+__device__ __forceinline__ uint32_t writeback_compact(SM& S, const f32x16 (&acc)[NOB][2], int wave, int lane, uint32_t (&mask)[4]) {
+  static_assert(sizeof(CompactLds) <= sizeof(S.part) + sizeof(S.aux), "CompactLds lives in S.part .. S.aux");
+  CompactLds& C = *reinterpret_cast<CompactLds*>(S.part);
+  compact_publish<NOB, KEEP>(C, acc, wave, lane, mask);
+  __syncthreads();
+  const uint32_t npad = compact_store<NOB, XYZ>(C, S.X, S.xyz, acc, wave, lane);
+  __syncthreads();
+  return npad;
+}
+
+// buffer descriptor over exactly the bytes of one layer's k-major pack: `row_bytes` per input feature (the stride the gather's index
+// is multiplied by), K features -- an index outside the layer reads zeros instead of faulting
+__device__ __forceinline__ rsrc_t kmajor_rsrc(const float* p, int row_bytes, int K) {
+  // opaque to the optimiser: the descriptor is formed HERE, per layer -- otherwise all seven are hoisted to the kernel's entry (the pointer is
+  // a kernel argument) and kept alive, in SGPRs spilled to VGPR lanes, across every tile of the kernel
+  asm volatile("" : "+s"(p));
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)row_bytes, K * row_bytes, 0x00020000);
+}
+
+// trip count of dense_asm_compact_*: two 8-position groups per iteration, first and last group peeled; clamped so that no value can
+// make the loop run past the layer
+__device__ __forceinline__ uint32_t compact_trips(uint32_t npad, uint32_t K) {
+  uint32_t n = npad / 16u;
+  n = n < 2u ? 2u : n;
+  n = n > K / 16u ? K / 16u : n;
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)(n - 1u));
+}
+
 // ---------------------------------------------------------------------------------------- saved ReLU masks
 // A ray's 512-byte mask block = 8 chunks of 64 bytes, chunk (wave, h) = the 32 16-bit words masks[l][ob] (l = 0..7,
 // ob = 0..3) that lane (j, h) of wave `wave` holds for that ray. The layout is per ray, so a block written by a
@@ -415,7 +584,8 @@ __device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float
 // Returns (every thread, for ray = tid & (TILE-1)) the pre-tanh output. masks[l] = ReLU bitmasks of layer l
 // (bit rb*16+r of masks[l][ob]). DEBUG_STOP: (test builds only) return right after layer `stop` is in X.
 // STAGED: the caller already ran stage_bias (early, so that its loads overlap the tile's prologue).
-template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false>
+// COMPACT (64-ray narrow tile only; needs D.Wk): layers 1..7 walk the live hidden units of the tile (same values, fewer MFMAs).
+template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false, bool COMPACT = false>
 __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* __restrict__ c0,
                                              const float* __restrict__ c4, Smem<RB>& S, uint32_t (&masks)[8][4],
                                              int stop = 8, long long* ts = nullptr) {
@@ -429,6 +599,9 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
   const int h = lane >> 5;
   const int ray = tid & (TILE - 1);
   float* X = S.X;
+  static_assert(!COMPACT || (RB == 2 && !WIDE), "the compacted tile is the 64-ray tile of the narrow layout");
+  constexpr bool compact = COMPACT;
+  uint32_t npad = HID;   // compacted tile: rows of X the next layer walks
   // first weight group of every layer travels while the previous layer finishes (dense_pf)
   f32x4 wpre[4];
   {
@@ -444,15 +617,80 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
   {
     f32x16 acc[4][RB];
     acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 0), wave * 128, h);
-    dense_pf<8, 4, RB, 4, 4, 4>(D.Wf[0], X, acc, wave, lane, wpre, D.Wf[1]);
+    dense_pf<8, 4, RB, 4, 4, 4>(D.Wf[0], X, acc, wave, lane, wpre, COMPACT ? nullptr : D.Wf[1]);
     DISTR_TS(1);
-    __syncthreads();
-    writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[0]);
-    __syncthreads();
+    if constexpr (COMPACT) {
+      if (compact && !(DEBUG_STOP && stop == 0)) {
+        npad = writeback_compact<4, KEEP, false>(S, acc, wave, lane, masks[0]);
+      } else {
+        __syncthreads();
+        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[0]);
+        __syncthreads();
+      }
+    } else {
+      __syncthreads();
+      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[0]);
+      __syncthreads();
+    }
     DISTR_TS(2);
   }
   if (DEBUG_STOP && stop == 0) return 0.f;
-  if constexpr (RB == 2) {
+  if constexpr (COMPACT) {
+    if (compact) {
+      // layers 1..7 over the live units of the tile (dense_asm_compact_*): every layer but the last -- and, in a DEBUG_STOP build, the one
+      // whose activations are dumped by feature -- leaves its output compacted for the next one; lin8_row reads the dense h7
+      CompactLds& C = *reinterpret_cast<CompactLds*>(S.part);
+      const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)(lane & 31) * 4;
+      const uint32_t kaddr = lds_off(C.klist) + (uint32_t)h * 2;
+      const uint32_t bias4 = lds_off(S.bias) + (uint32_t)wave * 512 + (uint32_t)h * 16;
+      const uint32_t bias2 = lds_off(S.bias) + 3 * 2048 + (uint32_t)wave * 256 + (uint32_t)h * 16;
+      // (static_for, not a loop with an unroll pragma: every layer must be straight-line code with its own masks[l] registers)
+      bool stopped = false;
+      static_for<7>([&](auto LI) {
+        constexpr int l = decltype(LI)::value + 1;
+        if (DEBUG_STOP && stopped) return;
+        if constexpr (l == 3) {  // lin3: 512 -> 253; the xyz rows join the list as units 253..255
+          f32x16 acc[2][2];
+          dense_asm_compact_n2_bias(acc, xaddr, kaddr, (uint32_t)(lane & 31) * 8, kmajor_rsrc(D.Wk + wk_offset(3), 1024, 512), (uint32_t)wave * 256,
+                                    compact_trips(npad, 512), bias2);
+          DISTR_TS(7);
+          masks[3][2] = 0; masks[3][3] = 0;
+          if (DEBUG_STOP && stop == 3) {
+            __syncthreads();
+            writeback<2, RB, true, false, KEEP>(X, acc, wave * 64, lane, masks[3]);
+            __syncthreads();
+            if (tid < 3 * TILE) X[253 * TILE + tid] = S.xyz[tid];
+            __syncthreads();
+            stopped = true;
+            return;
+          }
+          npad = writeback_compact<2, KEEP, true>(S, acc, wave, lane, masks[3]);
+          DISTR_TS(8);
+        } else {
+          f32x16 acc[4][2];
+          constexpr int K = (l == 4) ? 256 : 512;
+          dense_asm_compact_n4_bias(acc, xaddr, kaddr, (uint32_t)(lane & 31) * 16, kmajor_rsrc(D.Wk + wk_offset(l), 2048, K), (uint32_t)wave * 512,
+                                    compact_trips(npad, K), bias4 + l * 2048);
+          DISTR_TS(2 * l + 1);
+          if (l == 7 || (DEBUG_STOP && stop == l)) {
+            __syncthreads();
+            writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
+            __syncthreads();
+            DISTR_TS(2 * l + 2);
+            if (DEBUG_STOP && stop == l) stopped = true;
+          } else {
+            npad = writeback_compact<4, KEEP, false>(S, acc, wave, lane, masks[l]);
+            DISTR_TS(2 * l + 2);
+          }
+        }
+      });
+      if (DEBUG_STOP && stopped) return 0.f;
+      const float pre_c = lin8_row<RB>(D.w8, D.b8, S);
+      DISTR_TS(17);
+      return pre_c;
+    }
+  }
+  if constexpr (RB == 2 && !COMPACT) {
     // 64-ray tile: layers 1..7 on the hand-scheduled loop (distr_dense_asm.hpp). Every layer's accumulators start from the
     // LDS copy of its bias (srcC of the first MFMAs); the next layer's first weight group travels in `wpre` across the
     // write-back; S.part..S.aux (4 KiB, idle during the layers) is the scratch of the tuple -> register move.

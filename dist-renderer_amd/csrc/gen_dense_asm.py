@@ -303,6 +303,164 @@ __device__ __forceinline__ void %s(f32x4 (&acc)[%d], f32x4 (&t)[8], uint32_t xad
 }
 ''' % (K, NB, NOUT, name, NB, body, outs, ins, ', '.join(clob))
 
+# =====================================================================================================================
+# Compacted 64-ray tile: the same stream over the LIVE input features only. The write-back of the previous layer stored the rows of
+# the units that are > 0 for at least one ray of the tile at consecutive positions of X (ascending feature order, zero rows up to a
+# multiple of 16) and their feature indices in `klist` (uint16 per position). B operands: the dense walk over positions, i.e. gen()'s
+# reads unchanged. A operands: one buffer_load per k-step from the k-major pack Wk[k][rows of the wave, 4*j + ob] (row stride in the
+# resource, idxen + offen): lanes 0-31 take feature klist[2m], lanes 32-63 klist[2m + 1]; the index register of every load is filled
+# by a ds_read_u16 one group earlier and sits in a VGPR pair with the constant lane offset -- no VALU per load. The trip count is an
+# SGPR operand (npad / 16 - 1, clamped by the caller). No cross-layer prefetch: the first features of the next layer are not known
+# before its write-back, so the 16 registers of gen()'s `t` tuples hold the index pairs instead.
+#   v[160:167] four (index, lane offset) pairs   v168 running klist address   (A0/A1/B0/B1/VX/bias tuples as in gen())
+# A registers: A[buf] + NOB*s + ob (one load = all row blocks of k-step s).
+IDX = 160
+VK = 168
+
+
+def gen_compact(NOB):
+    L = []
+    emit = L.append
+    width = {4: 'dwordx4', 2: 'dwordx2'}[NOB]
+
+    def acc(ob, rb):
+        return '%%[c%d%d]' % (ob, rb)
+
+    def mfma(buf, s, ob, rb, srcc=None):
+        a = vr(A[buf] + NOB * s + ob)
+        b = vr(B[buf] + 2 * s + rb)
+        emit('v_mfma_f32_32x32x2_f32 %s, %s, %s, %s' % (acc(ob, rb), a, b, srcc if srcc is not None else acc(ob, rb)))
+
+    def load_a(buf, s):
+        emit('buffer_load_%s %s, %s, %%[rs], %%[soff] idxen offen' % (width, vr(A[buf] + NOB * s, NOB), vr(IDX + 2 * s, 2)))
+
+    def load_b(buf, s, rb, base, goff):
+        emit('ds_read_b32 %s, %s offset:%d' % (vr(B[buf] + 2 * s + rb), base, goff * 8 * TILE * 4 + s * 2 * TILE * 4 + rb * 128))
+
+    def load_i(s, base, pos):      # index of k-step s of the group that starts at position `pos` past `base`
+        emit('ds_read_u16 %s, %s offset:%d' % (vr(IDX + 2 * s), base, 2 * pos + 4 * s))
+
+    def group(cur, nxt, goff, loads=True):
+        """8*NOB MFMAs on buffers `cur`; interleaved: the loads of the next group (into `nxt`), then the indices of the one after."""
+        emit('s_waitcnt vmcnt(0) lgkmcnt(0)')
+        pend = []
+        if loads:
+            pend += [('a', s) for s in range(4)]
+            pend += [('b', s, rb) for s in range(4) for rb in range(2)]
+            pend += [('i', s) for s in range(4)]
+        for s in range(4):
+            for ob in range(NOB):
+                for rb in range(2):
+                    mfma(cur, s, ob, rb)
+                    if pend:
+                        p = pend.pop(0)
+                        if p[0] == 'a':
+                            load_a(nxt, p[1])
+                        elif p[0] == 'b':
+                            load_b(nxt, p[1], p[2], vr(VX), goff)
+                        else:
+                            load_i(p[1], vr(VK), 8 * (goff + 2))
+        assert not pend
+
+    lgkm = []
+
+    def lds(text, tag):
+        emit(text)
+        lgkm.append(tag)
+        assert len(lgkm) <= 15, 'too many LDS operations outstanding'
+
+    def wait_for(*tags):
+        idxs = [i for i, t in enumerate(lgkm) if t in tags]
+        if not idxs:
+            return
+        idx = max(idxs)
+        emit('s_waitcnt lgkmcnt(%d)' % (len(lgkm) - 1 - idx))
+        del lgkm[:idx + 1]
+
+    slot_of = {0: 0, 1: 1, 2: 2, 3: 0}
+
+    def bias_tuple(ob):
+        for q in range(4):
+            lds('ds_read_b128 %s, %%[bias] offset:%d' % (ar(BIAS[slot_of[ob]] + 4 * q, 4), ob * 128 + q * 32), 'bias%d' % ob)
+
+    def b0(s):
+        for rb in range(2):
+            lds('ds_read_b32 %s, %%[xaddr] offset:%d' % (vr(B[0] + 2 * s + rb), s * 2 * TILE * 4 + rb * 128), 'b0s%d' % s)
+
+    def first_mfmas(ob):
+        wait_for('b0s0', 'bias%d' % ob)
+        for rb in range(2):
+            mfma(0, 0, ob, rb, ar(BIAS[slot_of[ob]], 16))
+
+    # ---------------------------------------------------------------- prologue: groups 0 and 1 requested, indices of group 2 read
+    emit('s_nop 4')
+    for s in range(4):
+        emit('v_mov_b32 %s, %%[voff]' % vr(IDX + 2 * s + 1))
+    emit('v_mov_b32 %s, %%[kaddr]' % vr(VK))
+    emit('s_mov_b32 %s, %%[nit]' % S_CNT)
+    for g in range(2):
+        for s in range(4):
+            emit('ds_read_u16 %s, %%[kaddr] offset:%d' % (vr(IDX + 2 * s), 16 * g + 4 * s))
+        emit('s_waitcnt lgkmcnt(0)')
+        for s in range(4):
+            load_a(g, s)
+    for s in range(4):
+        lds('ds_read_u16 %s, %%[kaddr] offset:%d' % (vr(IDX + 2 * s), 32 + 4 * s), 'i2')
+    b0(0); bias_tuple(0)
+    bias_tuple(1)
+    emit('v_add_u32 %s, %d, %%[xaddr]' % (vr(VX), 8 * TILE * 4))
+    emit('s_waitcnt vmcnt(4)')     # group 0 has arrived (group 1 stays in flight)
+    first_mfmas(0)
+    if NOB == 4:
+        bias_tuple(2)
+        first_mfmas(1)
+        bias_tuple(3)
+        first_mfmas(2)
+        b0(1); b0(2); b0(3)
+        first_mfmas(3)
+    else:
+        b0(1); b0(2); b0(3)
+        first_mfmas(1)
+    pend = [(ps, prb) for ps in range(4) for prb in range(2)]
+    for s in range(1, 4):
+        wait_for('b0s%d' % s)
+        for ob in range(NOB):
+            for rb in range(2):
+                mfma(0, s, ob, rb)
+                if pend and s >= 2:
+                    ps, prb = pend.pop(0)
+                    lds('ds_read_b32 %s, %%[xaddr] offset:%d' % (vr(B[1] + 2 * ps + prb), 8 * TILE * 4 + ps * 2 * TILE * 4 + prb * 128), 'b1')
+    assert not pend
+    # ---------------------------------------------------------------- main loop: groups 1 .. NG-2, two per iteration
+    emit('.Ldense_compact_loop_%=:')
+    group(1, 0, 1)
+    group(0, 1, 2)
+    emit('v_add_u32 %s, %d, %s' % (vr(VX), 2 * 8 * TILE * 4, vr(VX)))
+    emit('v_add_u32 %s, 32, %s' % (vr(VK), vr(VK)))
+    emit('s_sub_u32 %s, %s, 1' % (S_CNT, S_CNT))
+    emit('s_cmp_lg_u32 %s, 0' % S_CNT)
+    emit('s_cbranch_scc1 .Ldense_compact_loop_%=')
+    # ---------------------------------------------------------------- peeled last group (its first wait also drains the index reads)
+    group(1, 0, 0, loads=False)
+    emit('s_nop 15')
+    emit('s_nop 3')
+    body = '\n'.join('      "%s\\n"' % x for x in L)
+
+    name = 'dense_asm_compact_n%d_bias' % NOB
+    outs = ', '.join('[c%d%d] "=&a"(acc[%d][%d])' % (ob, rb, ob, rb) for ob in range(NOB) for rb in range(2))
+    ins = '[xaddr] "v"(xaddr), [kaddr] "v"(kaddr), [voff] "v"(voff), [rs] "s"(rs), [soff] "s"(soff), [nit] "s"(nit), [bias] "v"(biasaddr)'
+    clob = ['"v%d"' % i for i in range(IDX, VK + 1)] + ['"v%d"' % i for i in range(A[0], VX + 1)] + ['"a%d"' % i for i in range(BIAS[0], BIAS[2] + 16)] + ['"%s"' % S_CNT, '"scc"', '"memory"']
+    return name, '''// compacted tile: %d row blocks of 32 per wave; nit = positions / 16 - 1 (>= 1); klist / Wk: see gen_dense_asm.py
+__device__ __forceinline__ void %s(f32x16 (&acc)[%d][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff,
+    uint32_t nit, uint32_t biasaddr) {
+  asm volatile(
+%s
+      : %s
+      : %s
+      : %s);
+}
+''' % (NOB, name, NOB, body, outs, ins, ', '.join(clob))
+
 
 def main():
     out = ['// GENERATED by gen_dense_asm.py -- do not edit; see that file for the design notes.',
@@ -314,6 +472,8 @@ def main():
             out.append(gen(K, NOB, NOUT, init)[1])
     for (K, NB, NOUT) in ((512, 8, 8), (512, 8, 4), (512, 4, 8), (256, 8, 8), (512, 8, 0)):
         out.append(gen16(K, NB, NOUT)[1])
+    for NOB in (4, 2):
+        out.append(gen_compact(NOB)[1])
     out.append('}  // namespace distr')
     sys.stdout.write('\n'.join(out) + '\n')
 

@@ -145,7 +145,7 @@ class RenderStats(_Sized):
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
            'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp')
 HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h')                    # include/: the C ABI
-INST_GROUPS = 7            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
+INST_GROUPS = 9            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
 
@@ -181,7 +181,7 @@ def build_commands(obj_dir=None):
 
 # kernels that contain the cluster tile (hand-counted vmcnt waits, live data in fixed registers between asm statements): unit, symbol part
 CLUSTER_KERNELS = (('inst1', 'k_stepILb1ELi0'), ('inst1', 'k_stepILb0ELi0'), ('inst2', 'k_tailILb1'), ('inst2', 'k_tailILb0'),
-                   ('inst3', 'k_march16ILi1ELb1'), ('inst3', 'k_march16ILi1ELb0'))
+                   ('inst3', 'k_march16ILi1ELb1'), ('inst3', 'k_march16ILi1ELb0'), ('inst8', 'k_stepILb1ELi0ELb1'), ('inst8', 'k_stepILb0ELi0ELb1'))
 NO_SCRATCH = ('k_step', 'k_march', 'k_bwd', 'k_tail')          # kernels that must not carry scratch (private segment 0): name parts
 
 

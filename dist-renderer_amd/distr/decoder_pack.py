@@ -74,6 +74,10 @@ def validate(Ws, bs):
         if tuple(np.shape(W)) != shapes[l] or tuple(np.shape(b)) != (shapes[l][0],):
             raise UnsupportedDecoder('lin%d has shape %s, kernels are specialised for %s (DeepSDF 8x512, '
                                      'latent %d, latent_in=[4], last_dim=1)' % (l, np.shape(W), shapes[l], C))
+        # the compacted 64-ray tile skips the products of hidden units that are +0 for a whole tile: the same value only for finite
+        # weights (0 * inf is the one product a skipped link would have changed)
+        if not (np.isfinite(W).all() and np.isfinite(b).all()):
+            raise UnsupportedDecoder('lin%d has non-finite weights or biases' % l)
     return C
 
 
