@@ -49,7 +49,8 @@ def load_decoder(experiment_directory, checkpoint_num=None, color_size=None, exp
 
 def decode_sdf(decoder, latent_vector, points, clamp_dist=0.1, MAX_POINTS=100000, no_grad=False, arith='f32'):
     """(n,3) points -> (n,1) SDF, optionally clamped (decoder_utils.py:53-74). Differentiable w.r.t. the latent code and
-    the points unless `no_grad` (fused backward: distr_mlp_backward); the decoder weights are frozen. `arith` (not in the
+    the points unless `no_grad` (fused backward: distr_mlp_backward); the decoder weights are constants here (decode_sdf_train returns
+    gradients to them). `arith` (not in the
     reference): 'f32' = exact f32 MFMA (default); 'bf16x6' / 'f16x3' = split-bf16 / split-f16 arithmetic, forward only, f32-equivalent
     but not bit-identical (distr_mlp_eval_bf16x6 / distr_mlp_eval_f16x3; the latter needs activations below 1023 and returns NaN otherwise)."""
     if latent_vector is None:
@@ -111,6 +112,35 @@ def decode_sdf_batch(decoder, latent_vectors, points, counts=None, clamp_dist=0.
         out = functions.mlp_eval_multi_autograd(eng, latent_vectors, x, counts, clamp_dist)
     else:
         out = functions.mlp_eval_multi(eng, latent_vectors, x, counts, clamp_dist)
+    return out.reshape(shape + (1,))
+
+
+def _train_layout(Cn, latent_vectors, points, counts):
+    """Shape logic of decode_sdf_train: decode_sdf_batch's (_batch_layout), and points that ask for a gradient are refused. Runs
+    without a GPU."""
+    if latent_vectors is None:
+        raise NotImplementedError('latent_vectors=None (a code in every input row, decoder_utils.py:58-59) is not supported')
+    if points.requires_grad:
+        raise ValueError('decode_sdf_train: points.requires_grad is set, but points are data on the layer-wise path (no point gradients); '
+                         'pass points.detach(), or use decode_sdf_batch for gradients to the points')
+    return _batch_layout(Cn, latent_vectors, points, counts)
+
+
+def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.1):
+    """decode_sdf_batch that is differentiable w.r.t. `decoder.parameters()` AND the codes (not in the reference, which trains through
+    the torch Decoder): the layer-wise path of DESIGN.md section 8f -- one f32-MFMA GEMM per layer over the whole point list, the layer
+    inputs kept for the backward (24 KB of workspace per point; above DISTR_TRAIN_MAX_BYTES, default 32 GiB, the call is refused
+    rather than chunked, since chunking would change the sum order of the gradients). Arguments, shapes and ValueErrors as
+    decode_sdf_batch; points with requires_grad are refused. The decoder must be in eval mode (dropout in training mode raises, as
+    everywhere); weight norm is folded on the autograd graph, so the gradients arrive at weight_g / weight_v. The fused engine is not
+    involved: after an optimiser step the renderers and decode_sdf re-pack the weights by themselves."""
+    from distr import decoder_pack
+    functions._check_eval(decoder.module if hasattr(decoder, 'module') else decoder)
+    Ws, bs = decoder_pack.effective_weights_torch(decoder)
+    x, counts, shape = _train_layout(Ws[0].shape[1] - 3, latent_vectors, points, counts)
+    if x.device.type != 'cuda':
+        raise RuntimeError('decode_sdf_train: tensors must be on the GPU (no CPU path in this build)')
+    out = functions.decode_sdf_train_call(Ws + bs, latent_vectors, x, counts, clamp_dist)
     return out.reshape(shape + (1,))
 
 

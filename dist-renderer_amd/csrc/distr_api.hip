@@ -20,6 +20,7 @@
 #include "distr_samples.hpp"
 #include "distr_normal_grad.hpp"
 #include "distr_color_batch.hpp"
+#include "distr_train.hpp"
 
 using namespace distr;
 
@@ -2498,6 +2499,233 @@ int distr_color_relight(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nfr
   const dim3 gpx((unsigned)((p.P + cbatch::MB - 1) / cbatch::MB), (unsigned)nframes), blk(cbatch::MB);
   hipLaunchKernelGGL(cbatch::k_cb_epilogue<false>, gpx, blk, 0, (hipStream_t)stream, p.G, C, L, mask, (const int32_t*)nullptr, color, out);
   LAUNCH_CHECK("k_cb_epilogue<relight>");
+  return DISTR_OK;
+}
+
+}  // extern "C"
+
+// ---- the layer-wise decoder path: weight gradients for decode_sdf (include/distr_train.h, distr_train.hpp)
+namespace {
+
+struct TrainPlan {
+  int C, nseg;
+  int64_t n;                 // points
+  int rows, blocks;          // padded rows, 64-row blocks
+  int64_t slab_len; int nslab;
+  train::Segs sg;
+  int32_t seg_row[DISTR_MAX_VIEWS + 1];
+  // workspace
+  int32_t *rowpt, *blkseg;
+  float *c0c4, *xyz4, *X[9] /* 1..8 */, *z, *th, *dz, *D[2], *colpart, *colseg[3] /* lin0, lin4, the others */, *slabs;
+  int out_w[9], in_w[9];     // GEMM widths: rows of W_l, and the columns of W_l that multiply the saved activation (lin4: 509 - C)
+};
+
+void train_slab_plan(int64_t rows, int64_t* len, int* count) {
+  // slab length: a multiple of 64 rows, at least SLAB_MIN, and long enough for MAX_SLABS slabs to cover the list
+  const int64_t per = (rows + train::MAX_SLABS - 1) / train::MAX_SLABS;
+  const int64_t L = std::max<int64_t>(train::SLAB_MIN, (per + train::TROW - 1) / train::TROW * train::TROW);
+  *len = L;
+  *count = (int)((rows + L - 1) / L);
+}
+
+int train_plan(distr_ctx* ctx, int32_t C, int32_t nseg, const int64_t* counts, TrainPlan& p) {
+  memset(&p, 0, sizeof(p));
+  PointList pl;
+  if (int rc = seg_list(ctx, nseg, counts, pl)) return rc;
+  if (C < 1 || C > HID - 4) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_size %d: 1..%d", C, HID - 4);
+  p.C = C; p.nseg = nseg; p.n = pl.n;
+  int64_t rows = 0;
+  for (int s = 0; s < nseg; ++s) {
+    p.sg.n[s] = (int32_t)counts[s];
+    p.seg_row[s] = (int32_t)rows;
+    rows += (counts[s] + train::TROW - 1) / train::TROW * train::TROW;
+  }
+  p.seg_row[nseg] = (int32_t)rows;
+  p.rows = (int)rows; p.blocks = (int)(rows / train::TROW);
+  train_slab_plan(rows, &p.slab_len, &p.nslab);
+  for (int l = 0; l < 9; ++l) { p.out_w[l] = HID; p.in_w[l] = HID; }
+  p.out_w[3] = HID - 3 - C; p.in_w[4] = HID - 3 - C; p.out_w[8] = 1; p.in_w[0] = 3;
+  return DISTR_OK;
+}
+
+size_t train_carve(void* base, TrainPlan& p) {
+  WsCarve c(base);
+  const size_t R = (size_t)p.rows;
+  p.rowpt = c.take<int32_t>(R); p.blkseg = c.take<int32_t>((size_t)p.blocks);
+  p.c0c4 = c.take<float>((size_t)p.nseg * 2 * HID);
+  p.xyz4 = c.take<float>(R * 4);
+  for (int l = 1; l <= 8; ++l) p.X[l] = c.take<float>(R * HID);
+  p.z = c.take<float>(R); p.th = c.take<float>(R); p.dz = c.take<float>(R);
+  p.D[0] = c.take<float>(R * HID); p.D[1] = c.take<float>(R * HID);
+  p.colpart = c.take<float>((size_t)p.blocks * 4 * HID);
+  for (int i = 0; i < 3; ++i) p.colseg[i] = c.take<float>((size_t)p.nseg * 4 * HID);
+  p.slabs = c.take<float>((size_t)p.nslab * HID * HID);
+  return c.bytes();
+}
+
+inline int vec_ok(const void* p, int ld) { return ((uintptr_t)p % 16 == 0 && ld % 4 == 0) ? 1 : 0; }
+
+template <bool A_K, bool B_K, int EPI>
+int train_gemm(distr_ctx* ctx, const char* name, train::GemmArgs& g, int nz, hipStream_t s) {
+  g.vecA = vec_ok(g.A, g.lda); g.vecB = vec_ok(g.B, g.ldb);
+  const dim3 grid((unsigned)((g.M + train::TBM - 1) / train::TBM), (unsigned)((g.N + train::TBN - 1) / train::TBN), (unsigned)nz);
+  hipLaunchKernelGGL((train::k_train_gemm<A_K, B_K, EPI>), grid, dim3(256), 0, s, g);
+  LAUNCH_CHECK(name);
+  return DISTR_OK;
+}
+
+int train_weights_ok(distr_ctx* ctx, const distr_train_weights* w) {
+  if (!w || w->struct_size != sizeof(distr_train_weights)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_weights: struct_size (use DISTR_INIT)");
+  for (int l = 0; l < 9; ++l)
+    if (!w->W[l] || !w->b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_weights: null pointer for lin%d", l);
+  return DISTR_OK;
+}
+
+// g_W of one layer's activation columns: Delta^T X over the K slabs, then the slabs in order
+int train_weight_grad(distr_ctx* ctx, const TrainPlan& p, const float* delta, int ldd, int M, const float* X, int N, float* g_W, hipStream_t s) {
+  train::GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = delta; g.lda = ldd; g.B = X; g.ldb = HID; g.Cout = p.slabs; g.ldc = N; g.M = M; g.N = N; g.K = p.rows;
+  g.slab_len = (int)p.slab_len; g.slab_stride = (size_t)M * N;
+  if (int rc = train_gemm<false, false, train::EPI_PART>(ctx, "k_train_gemm<weights>", g, p.nslab, s)) return rc;
+  hipLaunchKernelGGL(train::k_train_slab_sum, grid1((int64_t)M * N), dim3(256), 0, s, (const float*)p.slabs, p.nslab, M, N, g_W, HID);
+  LAUNCH_CHECK("k_train_slab_sum");
+  return DISTR_OK;
+}
+
+// column sums of a delta per segment (slot of p.colseg), then g_b and (lin0 / lin4: g_W non-null) the xyz and latent columns of g_W
+int train_bias_grad(distr_ctx* ctx, const TrainPlan& p, const float* delta, int ldd, int ncols, bool moments, float* seg, float* g_b, float* g_W, int ldw,
+                    int lat_col, int xyz_col, const float* latent, int64_t latent_stride, hipStream_t s) {
+  hipLaunchKernelGGL(train::k_train_colsum, dim3((unsigned)p.blocks), dim3(256), 0, s, delta, ldd, ncols, moments ? (const float*)p.xyz4 : (const float*)nullptr, p.colpart);
+  LAUNCH_CHECK("k_train_colsum");
+  hipLaunchKernelGGL(train::k_train_colsum_seg, dim3((unsigned)p.nseg, HID / 32, moments ? 4 : 1), dim3(256), 0, s, (const float*)p.colpart, p.sg, ncols, seg);
+  LAUNCH_CHECK("k_train_colsum_seg");
+  hipLaunchKernelGGL(train::k_train_bias, dim3((unsigned)ncols), dim3(256), 0, s, (const float*)seg, p.nseg, g_b, g_W, ldw, lat_col, xyz_col, g_W ? p.C : 0, latent,
+                     latent_stride);
+  LAUNCH_CHECK("k_train_bias");
+  return DISTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t distr_train_workspace_bytes(int32_t latent_size, int32_t nseg, const int64_t* counts_host) {
+  TrainPlan p;
+  return train_plan(nullptr, latent_size, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
+}
+
+size_t distr_train_activation_offset(int32_t latent_size, int32_t nseg, const int64_t* counts_host, int32_t layer) {
+  TrainPlan p;
+  if (layer < 1 || layer > 8 || train_plan(nullptr, latent_size, nseg, counts_host, p) != DISTR_OK) return 0;
+  train_carve(nullptr, p);
+  return (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt);
+}
+
+int64_t distr_train_segment_row(int32_t nseg, const int64_t* counts_host, int32_t seg) {
+  TrainPlan p;
+  if (seg < 0 || seg > nseg || train_plan(nullptr, 1, nseg, counts_host, p) != DISTR_OK) return -1;
+  return p.seg_row[seg];
+}
+
+void distr_train_slab_plan(int64_t rows, int64_t* slab_len, int32_t* num_slabs) {
+  int64_t L = 0; int n = 0;
+  train_slab_plan(rows < 0 ? 0 : rows, &L, &n);
+  if (slab_len) *slab_len = L;
+  if (num_slabs) *num_slabs = n;
+}
+
+int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                        const float* xyz, float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = train_weights_ok(ctx, w)) return rc;
+  TrainPlan p;
+  if (int rc = train_plan(ctx, w->latent_size, nseg, counts_host, p)) return rc;
+  const int C = p.C;
+  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
+  if (!latent || !ws || (p.n > 0 && (!xyz || !sdf))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < train_carve(nullptr, p)) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
+  train_carve(ws, p);
+  if (p.rows == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg);
+  LAUNCH_CHECK("k_train_rows");
+  hipLaunchKernelGGL(train::k_train_consts, dim3(4, (unsigned)p.nseg), dim3(256), 0, s, p.c0c4, w->W[0], w->b[0], w->W[4], w->b[4], C, latent, latent_stride);
+  LAUNCH_CHECK("k_train_consts");
+  hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
+                     p.X[1], p.xyz4);
+  LAUNCH_CHECK("k_train_lin0");
+  for (int l = 1; l <= 8; ++l) {
+    train::GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = p.X[l]; g.lda = HID; g.B = w->W[l]; g.ldb = HID; g.M = p.rows; g.N = p.out_w[l]; g.K = p.in_w[l];
+    g.Cout = l < 8 ? p.X[l + 1] : p.z; g.ldc = l < 8 ? HID : 1; g.relu = l < 8;
+    if (l == 4) {      // the accumulator starts from c4[segment]; xyz follows the lin3 outputs in k order
+      g.ctab = p.c0c4 + HID; g.ctab_stride = 2 * HID; g.blkseg = p.blkseg;
+      g.tailW = w->W[4] + (HID - 3); g.tail_ld = HID; g.xyz4 = p.xyz4;
+    } else g.bias = w->b[l];
+    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s)) return rc;
+  }
+  hipLaunchKernelGGL(train::k_train_out, grid1(p.rows), dim3(256), 0, s, (const float*)p.z, (const int32_t*)p.rowpt, p.rows, clamp, p.th, sdf);
+  LAUNCH_CHECK("k_train_out");
+  return DISTR_OK;
+}
+
+int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                         const float* g_sdf, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = train_weights_ok(ctx, w)) return rc;
+  if (!gr || gr->struct_size != sizeof(distr_train_grads)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: struct_size (use DISTR_INIT)");
+  for (int l = 0; l < 9; ++l)
+    if (!gr->g_W[l] || !gr->g_b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: null pointer for lin%d", l);
+  TrainPlan p;
+  if (int rc = train_plan(ctx, w->latent_size, nseg, counts_host, p)) return rc;
+  const int C = p.C;
+  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
+  if (!latent || !ws || (p.n > 0 && !g_sdf)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  train_carve(ws, p);
+  hipStream_t s = (hipStream_t)stream;
+  if (p.rows == 0) {       // an empty list: every gradient is zero
+    for (int l = 0; l < 9; ++l) {
+      const size_t in = l == 0 ? (size_t)C + 3 : HID;
+      HIP_TRY(hipMemsetAsync(gr->g_W[l], 0, (size_t)p.out_w[l] * in * sizeof(float), s));
+      HIP_TRY(hipMemsetAsync(gr->g_b[l], 0, (size_t)p.out_w[l] * sizeof(float), s));
+    }
+    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * C * sizeof(float), s));
+    return DISTR_OK;
+  }
+  hipLaunchKernelGGL(train::k_train_dz, grid1(p.rows), dim3(256), 0, s, g_sdf, (const float*)p.th, (const int32_t*)p.rowpt, p.rows, clamp, p.dz);
+  LAUNCH_CHECK("k_train_dz");
+  // lin8: its delta is the column dz
+  if (int rc = train_weight_grad(ctx, p, p.dz, 1, 1, p.X[8], HID, gr->g_W[8], s)) return rc;
+  if (int rc = train_bias_grad(ctx, p, p.dz, 1, 1, false, p.colseg[2], gr->g_b[8], nullptr, 0, 0, 0, latent, latent_stride, s)) return rc;
+  const float* delta = p.dz;
+  int ldd = 1, cur = 0;
+  for (int l = 8; l >= 1; --l) {
+    // delta of lin(l-1) = (delta of lin_l) W_l, gated by the saved relu output X_l; lin4: its lin3 columns only
+    train::GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
+    g.Cout = p.D[cur]; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
+    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s)) return rc;
+    delta = p.D[cur]; ldd = HID; cur ^= 1;
+    const int m = l - 1;       // delta now belongs to lin m
+    if (m >= 1) {
+      if (int rc = train_weight_grad(ctx, p, delta, HID, p.out_w[m], p.X[m], p.in_w[m], gr->g_W[m], s)) return rc;
+      if (int rc = train_bias_grad(ctx, p, delta, HID, p.out_w[m], m == 4, p.colseg[m == 4 ? 1 : 2], gr->g_b[m], m == 4 ? gr->g_W[4] : nullptr, HID, HID - 3 - C,
+                                   HID - 3, latent, latent_stride, s))
+        return rc;
+    } else {
+      if (int rc = train_bias_grad(ctx, p, delta, HID, HID, true, p.colseg[0], gr->g_b[0], gr->g_W[0], C + 3, 0, C, latent, latent_stride, s)) return rc;
+    }
+  }
+  if (g_latent) {
+    hipLaunchKernelGGL(train::k_train_glatent, dim3((unsigned)((C + 255) / 256), (unsigned)p.nseg), dim3(256), 0, s, (const float*)p.colseg[0], (const float*)p.colseg[1], w->W[0],
+                       w->W[4], C, g_latent);
+    LAUNCH_CHECK("k_train_glatent");
+  }
   return DISTR_OK;
 }
 

@@ -40,6 +40,9 @@ NORMAL_GRAD_EXPORTS = ['distr_render_normal_grad_workspace_bytes', 'distr_render
 COLOR_BATCH_EXPORTS = ['distr_color_multi_workspace_bytes', 'distr_color_backward_multi_workspace_bytes', 'distr_color_eval_multi',
                        'distr_color_backward_multi', 'distr_color_stage_workspace_bytes', 'distr_color_stage_forward_batch',
                        'distr_color_stage_backward_batch', 'distr_color_relight']
+# the layer-wise decoder path (include/distr_train.h, included by distr.h): decode_sdf with gradients to the decoder's weights
+TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset', 'distr_train_segment_row', 'distr_train_slab_plan',
+                 'distr_train_forward', 'distr_train_backward']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -136,6 +139,16 @@ def make_warp_cfg(img_hw, intrinsic, thres_depth):
     return cfg
 
 
+class TrainWeights(_Sized):
+    """distr_train_weights: the nine layers of the decoder as device pointers, row-major (out, in)."""
+    _fields_ = [('struct_size', C.c_uint32), ('latent_size', C.c_int32), ('W', C.c_void_p * 9), ('b', C.c_void_p * 9)]
+
+
+class TrainGrads(_Sized):
+    """distr_train_grads: where distr_train_backward writes g_W / g_b."""
+    _fields_ = [('struct_size', C.c_uint32), ('reserved', C.c_uint32), ('g_W', C.c_void_p * 9), ('g_b', C.c_void_p * 9)]
+
+
 class RenderStats(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('reserved', C.c_uint32), ('num_in_sphere', C.c_int64), ('num_march_launches', C.c_int64), ('num_point_evals', C.c_int64),
                 ('num_valid', C.c_int64), ('num_grad_samples', C.c_int64), ('cluster_fallbacks', C.c_int64), ('f16_overflows', C.c_int64),
@@ -143,8 +156,8 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h')                    # include/: the C ABI
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp')
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h')                    # include/: the C ABI
 INST_GROUPS = 9            # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -383,6 +396,17 @@ def lib():
             L.distr_color_stage_backward_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, fp, fp, i64, lights, vp, C.c_size_t,
                                                            fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
             L.distr_color_relight.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, u8p, fp, fp, lights, fp, vp]
+            tw, tg = C.POINTER(TrainWeights), C.POINTER(TrainGrads)
+            L.distr_train_workspace_bytes.argtypes = [i32, i32, i64p]
+            L.distr_train_workspace_bytes.restype = C.c_size_t
+            L.distr_train_activation_offset.argtypes = [i32, i32, i64p, i32]
+            L.distr_train_activation_offset.restype = C.c_size_t
+            L.distr_train_segment_row.argtypes = [i32, i64p, i32]
+            L.distr_train_segment_row.restype = C.c_int64
+            L.distr_train_slab_plan.argtypes = [i64, i64p, C.POINTER(i32)]
+            L.distr_train_slab_plan.restype = None
+            L.distr_train_forward.argtypes = [vp, tw, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp]
+            L.distr_train_backward.argtypes = [vp, tw, i32, i64p, fp, i64, fp, C.c_float, vp, tg, fp, vp]
             _lib = L
     return _lib
 

@@ -81,6 +81,98 @@ def validate(Ws, bs):
     return C
 
 
+def _row_sumsq_f32(v):
+    """sum(v ** 2, axis=1) of a 2-D f32 tensor in the order numpy's f32 sum takes along a contiguous row (pairwise: halves down to runs
+    of at most 128, eight strided partial sums per run, their fixed tree, then the run's remainder), out of differentiable elementwise
+    torch operations: the row norms -- and with them the folded weights -- of effective_weights_torch are those of effective_weights."""
+    n = v.shape[1]
+    sq = v * v
+    if n >= 256 and n % 128 == 0 and (n // 128) & (n // 128 - 1) == 0:     # equal runs of 128: all runs at once
+        r = sq.reshape(sq.shape[0], n // 128, 16, 8)
+        acc = r[:, :, 0]
+        for i in range(1, 16):
+            acc = acc + r[:, :, i]
+        t = ((acc[..., 0] + acc[..., 1]) + (acc[..., 2] + acc[..., 3])) + ((acc[..., 4] + acc[..., 5]) + (acc[..., 6] + acc[..., 7]))
+        while t.shape[1] > 1:
+            t = t[:, 0::2] + t[:, 1::2]
+        return t[:, 0]
+
+    def run(a):
+        m = a.shape[1]
+        if m < 8:
+            res = a[:, 0] * 0
+            for i in range(m):
+                res = res + a[:, i]
+            return res
+        if m <= 128:
+            full = m - m % 8
+            acc = a[:, :8]
+            for i in range(8, full, 8):
+                acc = acc + a[:, i:i + 8]
+            res = ((acc[:, 0] + acc[:, 1]) + (acc[:, 2] + acc[:, 3])) + ((acc[:, 4] + acc[:, 5]) + (acc[:, 6] + acc[:, 7]))
+            for i in range(full, m):
+                res = res + a[:, i]
+            return res
+        half = m // 2
+        half -= half % 8
+        return run(a[:, :half]) + run(a[:, half:])
+    return run(sq)
+
+
+def _fold_weight_norm(v, g):
+    """v * (g / ||v||_row), operation for operation what effective_weights computes in numpy (and torch._weight_norm up to the order of
+    the norm's sum)."""
+    import torch
+    # the square root and the quotient through float64: rounding a float64 sqrt / quotient of f32 values to f32 gives the correctly
+    # rounded f32 result (53 >= 2 * 24 + 2 bits), whatever the f32 sqrt and division of the device's torch build do
+    nrm = torch.sqrt(_row_sumsq_f32(v).double()).float()
+    return v * (g.reshape(-1, 1).double() / nrm.reshape(-1, 1).double()).float()
+
+
+def effective_weights_torch(decoder):
+    """nn.Module (optionally DataParallel-wrapped) -> ([W_l], [b_l]) as torch tensors ON THE AUTOGRAD GRAPH of the module's parameters:
+    the weights the layer-wise train path (decode_sdf_train) reads in place and returns gradients for. A plain layer
+    hands out its own parameters; weight norm, old style (`weight_g` / `weight_v`) or parametrized (`parametrizations.weight.original0 /
+    original1`), is folded as effective_weights folds it, W = v * (g / ||v||_row) with the same f32 operations in the same order, so the
+    train path and the packed engine see the same weights, and autograd carries g_W on to g and v. Checked as check_module_flags and validate check a decoder that is packed (flags, the nine shapes, finite values)."""
+    import torch
+    check_module_flags(decoder)
+    d = decoder.module if hasattr(decoder, 'module') else decoder
+    params = dict(d.named_parameters())
+    if any(k.startswith('bn') for k in params):
+        raise UnsupportedDecoder('LayerNorm decoders (weight_norm=False with norm_layers) are not supported')
+    Ws, bs = [], []
+    l = 0
+    while ('lin%d.bias' % l) in params:
+        for g_name, v_name in (('weight_g', 'weight_v'), ('parametrizations.weight.original0', 'parametrizations.weight.original1')):
+            if ('lin%d.%s' % (l, v_name)) in params:
+                v, g = params['lin%d.%s' % (l, v_name)], params['lin%d.%s' % (l, g_name)]
+                W = _fold_weight_norm(v, g)
+                break
+        else:
+            W = params['lin%d.weight' % l]
+        Ws.append(W)
+        bs.append(params['lin%d.bias' % l])
+        l += 1
+    if len(Ws) != fixture.NUM_LINEAR:
+        raise UnsupportedDecoder('expected %d linear layers, got %d' % (fixture.NUM_LINEAR, len(Ws)))
+    C = int(Ws[0].shape[1]) - 3 if Ws[0].dim() == 2 else -1
+    if C < 1 or C > MAX_LATENT:
+        raise UnsupportedDecoder('lin0 has shape %s: code length %d is outside 1..%d (lin3 of a latent_in=[4] decoder has 509 - C rows)'
+                                 % (tuple(Ws[0].shape), C, MAX_LATENT))
+    shapes = fixture.layer_shapes(C)
+    for l, (W, b) in enumerate(zip(Ws, bs)):
+        if tuple(W.shape) != shapes[l] or tuple(b.shape) != (shapes[l][0],):
+            raise UnsupportedDecoder('lin%d has shape %s, kernels are specialised for %s (DeepSDF 8x512, latent %d, latent_in=[4], '
+                                     'last_dim=1)' % (l, tuple(W.shape), shapes[l], C))
+    with torch.no_grad():       # one reduction and one host read for all eighteen tensors
+        finite = torch.stack([torch.isfinite(t).all() for t in Ws + bs])
+        if not bool(finite.all()):
+            bad = [i for i, ok in enumerate(finite.tolist()) if not ok][0]
+            raise UnsupportedDecoder('lin%d has non-finite weights or biases' % (bad % fixture.NUM_LINEAR))
+    return Ws, bs
+
+
 def validate_color(Ws, bs):
     """Colour decoder (load_decoder(color_size=cs), decoder_utils.py:16-24): returns its latent length 256 + cs."""
     if len(Ws) != 9:

@@ -593,6 +593,177 @@ def mlp_eval_multi_autograd(engine, latents, points, counts, clamp_dist=None):
     return DecodeSdfMultiFunction.apply(latents, points, engine, counts, clamp_dist)
 
 
+# ---- the layer-wise decoder path: decode_sdf with gradients to the decoder's weights (include/distr_train.h)
+TRAIN_ROW_TILE = 64                 # every segment is padded to a multiple of 64 workspace rows
+TRAIN_SLAB_MIN = 256                # smallest K slab of a weight-gradient GEMM (rows)
+TRAIN_MAX_SLABS = 64                # DISTR_TRAIN_MAX_SLABS
+TRAIN_MAX_BYTES_DEFAULT = 32 << 30  # DISTR_TRAIN_MAX_BYTES: largest workspace decode_sdf_train allocates for one call
+
+
+def train_slab_plan(rows):
+    """(slab length, number of slabs) of the weight-gradient GEMMs over `rows` workspace rows: g_W = Delta^T X sums over the rows in
+    slabs that are added up in slab order. A pure function of the row count (never of the GPU): the length is a multiple of 64 rows, at
+    least 256, and long enough for 64 slabs to cover the list. Mirror of distr_train_slab_plan."""
+    rows = max(0, int(rows))
+    per = -(-rows // TRAIN_MAX_SLABS)
+    length = max(TRAIN_SLAB_MIN, -(-per // TRAIN_ROW_TILE) * TRAIN_ROW_TILE)
+    return length, -(-rows // length)
+
+
+def train_segment_rows(counts):
+    """First workspace row of every segment, and behind them the number of rows in all (mirror of distr_train_segment_row)."""
+    rows, at = [], 0
+    for c in counts:
+        rows.append(at)
+        at += -(-int(c) // TRAIN_ROW_TILE) * TRAIN_ROW_TILE
+    return rows + [at]
+
+
+def train_max_bytes():
+    import os
+    return int(os.environ.get('DISTR_TRAIN_MAX_BYTES', TRAIN_MAX_BYTES_DEFAULT))
+
+
+_train_contexts = {}
+
+
+def _train_context(device_index):
+    """The context of the train calls on one device: it supplies the device and the stream, no decoder is set on it."""
+    if device_index not in _train_contexts:
+        _train_contexts[device_index] = binding.Context(device_index)
+    return _train_contexts[device_index]
+
+
+class TrainSaved(object):
+    """What train_forward keeps for train_backward: the workspace with the saved layer inputs, and the call it belongs to."""
+
+    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp):
+        self.ctx, self.ws, self.latent_size, self.counts = ctx, ws, C_len, list(counts)
+        self.weights, self.lat, self.stride, self.clamp = weights, lat, stride, clamp
+        self.seg_rows = train_segment_rows(counts)
+
+    def _cnt(self):
+        return (C.c_int64 * len(self.counts))(*self.counts)
+
+    def rows(self, s):
+        """(first row, last row + 1) of segment s's points in the workspace (its padded rows follow)."""
+        return self.seg_rows[s], self.seg_rows[s] + self.counts[s]
+
+    def activations(self, layer):
+        """(rows, width) f32 view of X_layer (1..8), the saved input of lin_layer = relu of lin_(layer-1); width 512, 509 - C for layer 4."""
+        off = self.ctx.L.distr_train_activation_offset(self.latent_size, len(self.counts), self._cnt(), int(layer))
+        if not off:
+            raise ValueError('layer %r: 1..8' % (layer,))
+        R = self.seg_rows[-1]
+        base = (-self.ws.data_ptr()) % 256
+        x = self.ws[base + off: base + off + R * 512 * 4].view(torch.float32).reshape(R, 512)
+        return x[:, :509 - self.latent_size] if layer == 4 else x
+
+
+def _train_weight_struct(weights, C_len):
+    tw = binding.TrainWeights(latent_size=int(C_len))
+    for l in range(9):
+        tw.W[l] = weights[l].data_ptr()
+        tw.b[l] = weights[9 + l].data_ptr()
+    return tw
+
+
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None):
+    """Layer-wise decode_sdf of one segmented list of at most 64 segments (distr_train_forward): weights = [W0..W8, b0..b8] f32 device
+    tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
+    A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed."""
+    counts = [int(c) for c in counts]
+    dev = points.device
+    if dev.type != 'cuda':
+        raise RuntimeError('train_forward: tensors must be on the GPU (no CPU path in this build)')
+    if not 1 <= len(counts) <= binding.MAX_SEGMENTS:
+        raise ValueError('%d segments: one train_forward call takes 1..%d' % (len(counts), binding.MAX_SEGMENTS))
+    ctx = _train_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    weights = [_f32c(t, dev) for t in weights]
+    C_len = weights[0].shape[1] - 3
+    lat = _f32c(latents, dev).reshape(-1, C_len)
+    if lat.shape[0] not in (1, len(counts)):
+        raise ValueError('latents have shape %s; %d segments take (%d, %d) or (1, %d)' % (tuple(latents.shape), len(counts), len(counts), C_len, C_len))
+    x = _f32c(points, dev).reshape(-1, 3)
+    if x.shape[0] != sum(counts):
+        raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), x.shape[0]))
+    cnt = (C.c_int64 * len(counts))(*counts)
+    need = ctx.L.distr_train_workspace_bytes(C_len, len(counts), cnt)
+    if need > train_max_bytes():
+        raise binding.DistrError('decode_sdf_train: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
+                                 'more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient follows the batch)'
+                                 % (x.shape[0], need, train_max_bytes()))
+    ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
+    stride = 0 if lat.shape[0] == 1 else C_len
+    out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+    p = binding.ptr
+    ctx.check(ctx.L.distr_train_forward(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
+                                        p(out), p(ws), ws.numel(), ctx.stream()))
+    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist)
+
+
+def train_backward(saved, g_sdf):
+    """Backward of train_forward (distr_train_backward): g_sdf (sum counts,) -> ([g_W0..g_W8, g_b0..g_b8], g_latent (S, C): one row per
+    segment, also for a shared code)."""
+    ctx, dev = saved.ctx, saved.ws.device
+    gs = _f32c(g_sdf, dev).reshape(-1)
+    if gs.numel() != sum(saved.counts):
+        raise ValueError('g_sdf has %d entries for %d points' % (gs.numel(), sum(saved.counts)))
+    grads = [torch.empty_like(w) for w in saved.weights]
+    g_lat = torch.empty(len(saved.counts), saved.latent_size, dtype=torch.float32, device=dev)
+    tg = binding.TrainGrads()
+    for l in range(9):
+        tg.g_W[l] = grads[l].data_ptr()
+        tg.g_b[l] = grads[9 + l].data_ptr()
+    p = binding.ptr
+    ctx.check(ctx.L.distr_train_backward(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(), p(saved.lat),
+                                         saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream()))
+    return grads, g_lat
+
+
+class DecodeSdfTrainFunction(torch.autograd.Function):
+    """decode_sdf on the layer-wise path with autograd to the codes AND the eighteen weight tensors: (codes (S, C) or (1, C), flat points
+    (sum counts, 3), counts, clamp, W0..W8, b0..b8) -> (sum counts, 1). The forward keeps the workspaces (the layer inputs) for the
+    backward. More than 64 segments run in chunks of 64; the weight gradients of the chunks are added in chunk order. Points are data."""
+
+    @staticmethod
+    def forward(ctx, codes, points, counts, clamp_dist, *weights):
+        if len(weights) != 18:
+            raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
+        counts = [int(c) for c in counts]
+        plan = segment_plan(counts)
+        lat = codes.detach().reshape(-1, weights[0].shape[1] - 3)
+        x = points.detach().reshape(-1, 3)
+        outs, ctx.saved_chunks = [], []
+        for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
+            n = sum(counts[s0:s0 + ns])
+            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist)
+            outs.append(out)
+            ctx.saved_chunks.append((saved, p0, n, s0, ns))
+        ctx.codes_shape, ctx.shared = codes.shape, lat.shape[0] == 1
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.reshape(-1)
+        total, rows = None, []
+        for saved, p0, n, s0, ns in ctx.saved_chunks:
+            grads, g_lat = train_backward(saved, g[p0:p0 + n])
+            rows.append(g_lat)
+            if total is None:
+                total = grads
+            else:
+                for a, b in zip(total, grads):
+                    a += b
+        g_rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+        g_codes = (g_rows.sum(0) if ctx.shared and g_rows.shape[0] > 1 else g_rows).reshape(ctx.codes_shape)
+        return (g_codes, None, None, None) + tuple(total)
+
+
+def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None):
+    return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, *weights)
+
+
 def depth_samples_count(engine, cfg, depth):
     """Valid pixels (0 < depth < 1e5) of V depth maps (V, H, W), compacted on the GPU in row-major order (distr_depth_samples_count: a
     fixed-order scan, one host read). Returns (depth as the f32 device tensor the kernels read, index (V, H*W) int32 whose first

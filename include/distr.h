@@ -375,5 +375,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_normal_grad.h"
 /* the colour decoder on a segmented point list; the colour stage of a batch of rendered views */
 #include "distr_color_batch.h"
+/* the layer-wise decoder path: decode_sdf with gradients to the decoder's weights */
+#include "distr_train.h"
 
 #endif /* DISTR_H_ */

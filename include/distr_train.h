@@ -1,0 +1,79 @@
+/*
+ * distr_train.h -- C ABI of libdistr.so, part 7: the LAYER-WISE decoder path -- decode_sdf with gradients to the decoder's WEIGHTS.
+ * Included by distr.h. Every other decoder entry point runs the fused tiles on the packed copy of distr_set_decoder and treats the
+ * weights as constants. The calls below evaluate the same DeepSDF 8x512 network (latent_in=[4], code length C in 1..508, eval mode)
+ * one layer at a time: every layer is one f32-MFMA GEMM over the whole point list, the layer inputs stay in the workspace (16 KB per
+ * row), and the backward returns g_W / g_b of all nine layers and the code gradient. The weights are the caller's own arrays, plain
+ * row-major (out, in) as torch keeps them: nothing is packed, the context's decoder (if any) is not involved.
+ *
+ * Point list. Segments as in distr_multi.h: nseg (1..DISTR_MAX_VIEWS), counts_host[s] >= 0 points (HOST array, at most 2^30 in all), the
+ * code of segment s at latent_dev + s * latent_stride (0: one shared code, else >= C). In the workspace every segment is padded to a
+ * multiple of 64 ROWS: segment s starts at row distr_train_segment_row(nseg, counts_host, s), point i of it is row + i. A padded row
+ * has xyz = 0 and an upstream gradient of 0; it adds exactly nothing to any sum.
+ *
+ * Saved activations. X_l (l = 1..8) is the input of lin_l = relu of lin_(l-1)'s output, point-major f32 rows of 512 floats each,
+ * at byte offset distr_train_activation_offset(latent_size, nseg, counts_host, l) from the workspace pointer rounded up to 256 bytes.
+ * X_4 holds the 509 - C outputs of lin3 in its first columns (the rest of the row is not written); lin4's remaining inputs are the code
+ * (folded into a per-segment constant) and xyz.
+ *
+ * What is identical to what. Sums run in fixed orders (k in natural order inside a GEMM; a weight gradient's row dimension in at most
+ * 64 slabs whose length depends on the row count only -- distr_train_slab_plan -- added in slab order; column sums per 64-row block,
+ * per segment, then over segments in order): no float atomics, the same bytes on every run and every machine. A segment's sdf slice
+ * and its g_latent row are byte for byte those of a call on that segment alone. f32 arithmetic only.
+ *
+ * Conventions of distr.h: struct_size first (DISTR_INIT), everything enqueued on the caller's stream, no allocation, no host
+ * synchronisation. Refused: what distr_multi.h refuses, a latent_size outside 1..508, a null weight / gradient pointer
+ * (DISTR_ERR_INVALID_ARG), a workspace that is too small (DISTR_ERR_WORKSPACE). distr_train_workspace_bytes,
+ * distr_train_activation_offset return 0 and distr_train_segment_row returns -1 for arguments the calls refuse.
+ */
+#ifndef DISTR_TRAIN_H_
+#define DISTR_TRAIN_H_
+
+#include "distr.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define DISTR_TRAIN_MAX_SLABS 64
+
+/* the nine layers, device pointers: W[l] row-major (out_l, in_l), b[l] (out_l); shapes of DeepSDF 8x512 with latent_in=[4]:
+ * lin0 (512, C + 3), lin3 (509 - C, 512), lin8 (1, 512), the others (512, 512) */
+typedef struct distr_train_weights {
+  uint32_t struct_size;
+  int32_t latent_size; /* C */
+  const float* W[9];
+  const float* b[9];
+} distr_train_weights;
+
+/* where the backward writes (overwrites, does not add): g_W[l] and g_b[l] in the shapes of W[l] and b[l], all eighteen required */
+typedef struct distr_train_grads {
+  uint32_t struct_size;
+  uint32_t reserved;
+  float* g_W[9];
+  float* g_b[9];
+} distr_train_grads;
+
+/* one workspace serves the forward and its backward */
+size_t distr_train_workspace_bytes(int32_t latent_size, int32_t nseg, const int64_t* counts_host);
+/* byte offset of X_layer (layer 1..8) behind the 256-byte aligned workspace base; rows of 512 floats */
+size_t distr_train_activation_offset(int32_t latent_size, int32_t nseg, const int64_t* counts_host, int32_t layer);
+/* first workspace row of segment seg (0..nseg; nseg: the number of rows in all) */
+int64_t distr_train_segment_row(int32_t nseg, const int64_t* counts_host, int32_t seg);
+/* K slabs of a weight-gradient GEMM over `rows` rows: a function of the row count alone; at most DISTR_TRAIN_MAX_SLABS slabs */
+void distr_train_slab_plan(int64_t rows, int64_t* slab_len, int32_t* num_slabs);
+
+/* sdf_dev[sum counts] in the caller's point order; clamp_dist < 0 = no clamp. Fills the workspace for distr_train_backward. */
+int distr_train_forward(distr_ctx* ctx, const distr_train_weights* weights, int32_t nseg, const int64_t* counts_host,
+                        const float* latent_dev, int64_t latent_stride, const float* xyz_dev, float clamp_dist, float* sdf_dev,
+                        void* ws_dev, size_t ws_bytes, void* stream);
+/* backward of distr_train_forward with the SAME weights, list, codes and clamp, on the workspace it filled: g_sdf[sum counts] ->
+ * grads, g_latent[nseg][C] (may be NULL; a row per segment, also for a shared code: the caller adds the rows up) */
+int distr_train_backward(distr_ctx* ctx, const distr_train_weights* weights, int32_t nseg, const int64_t* counts_host,
+                         const float* latent_dev, int64_t latent_stride, const float* g_sdf, float clamp, void* ws_dev,
+                         const distr_train_grads* grads, float* g_latent, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DISTR_TRAIN_H_ */
