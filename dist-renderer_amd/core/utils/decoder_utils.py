@@ -52,7 +52,7 @@ def decode_sdf(decoder, latent_vector, points, clamp_dist=0.1, MAX_POINTS=100000
     the points unless `no_grad` (fused backward: distr_mlp_backward); the decoder weights are constants here (decode_sdf_train returns
     gradients to them). `arith` (not in the
     reference): 'f32' = exact f32 MFMA (default); 'bf16x6' / 'f16x3' = split-bf16 / split-f16 arithmetic, forward only, f32-equivalent
-    but not bit-identical (distr_mlp_eval_bf16x6 / distr_mlp_eval_f16x3; the latter needs activations below 1023 and returns NaN otherwise)."""
+    but not bit-identical (distr_mlp_eval_bf16x6 / distr_mlp_eval_f16x3; the latter needs every layer's largest |weight| in [2^-8, 1023.5) -- refused otherwise -- and activations below 1023.75, and returns NaN otherwise)."""
     if latent_vector is None:
         raise NotImplementedError('latent_vector=None (decoder_utils.py:58-59) is not supported')
     eng = _engine(decoder, points)

@@ -36,8 +36,9 @@ struct distr_ctx {
   DecoderDev16 D16{};
   DecoderB6 B6{};                   // split-bf16 weight planes of the shape decoder (distr_mlp_eval_bf16x6), own allocation
   uint32_t* dec_buf_b6 = nullptr;
-  DecoderH3 H3{};                   // split-f16 weight planes (distr_mlp_h3.hpp), in the same allocation; h3_ok: the weights fit the f16 range
-  bool h3_ok = false;
+  DecoderH3 H3{};                   // split-f16 weight planes (distr_mlp_h3.hpp), in the same allocation; h3_ok: every layer's largest
+  bool h3_ok = false;               // |weight| lies in [H3_WMIN, H3_WMAX); otherwise h3_why names the first layer outside it
+  std::string h3_why;
   bool has_decoder = false;
   bool profiling = false;
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
@@ -291,7 +292,7 @@ int check_cfg(distr_ctx* ctx, const distr_render_cfg* c) {
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith %s: the split arithmetics are built for code length %d only (this decoder: %d); use f32",
                 c->arith == DISTR_ARITH_BF16X6 ? "bf16x6" : "f16x3", LAT, ctx->D.nlat);
   if (c->arith == DISTR_ARITH_F16X3 && ctx->has_decoder && !ctx->h3_ok)
-    return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
+    return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith f16x3: %s; use bf16x6 or f32 for this decoder", ctx->h3_why.c_str());
   if (c->rows != 0) {
     if (c->rows < 0 || c->row0 < 0 || c->row0 + c->rows > c->H) return fail(ctx, DISTR_ERR_INVALID_ARG, "row band [%d,+%d) outside the %d-row image", c->row0, c->rows, c->H);
     if ((c->row0 & 3) || ((c->rows & 3) && c->row0 + c->rows != c->H))
@@ -694,7 +695,7 @@ const char* distr_last_error(const distr_ctx* ctx) { return ctx ? ctx->err.c_str
 // 509..511) and lin4 K = 512. The split-bf16 / split-f16 planes are packed for C = 256 only (the only decoders they may run).
 static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const float* w, size_t n_floats, float** dev_buf, DecoderDev& D,
                          DecoderDev16* D16, DecoderB6* B6 = nullptr, uint32_t** dev_buf_b6 = nullptr, DecoderH3* H3 = nullptr,
-                         bool* h3_ok = nullptr, bool compact = false) {
+                         bool* h3_ok = nullptr, bool compact = false, std::string* h3_why = nullptr) {
   if (rows3 < 1 || rows3 > 509) return fail(ctx, DISTR_ERR_UNSUPPORTED, "lin3 with %d rows does not fit the 509-row tile", rows3);
   const bool wide = rows3 > 253;
   const int R3 = wide ? 509 : 253;         // row of lin3's output (and column of lin4) where xyz is carried
@@ -810,7 +811,20 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
       for (int l = 1; l < 8; ++l) {
         offh[l] = (hb.size() + 127) & ~(size_t)127;
         hb.resize(offh[l] + Wp[l].size() * 2, 0);
-        if (!pack_fragments_h3(Wp[l].data(), Kp[l], Op[l], hb.data() + offh[l])) *h3_ok = false;
+        const bool fits = pack_fragments_h3(Wp[l].data(), Kp[l], Op[l], hb.data() + offh[l]);
+        // the accepted range of the mode, per layer and on both sides (distr_mlp_h3.hpp: H3_WMAX, H3_WMIN)
+        float wmax = 0.f;
+        for (float v : Wp[l]) wmax = fmaxf(wmax, fabsf(v));
+        const bool high = !fits || !(wmax < H3_WMAX), low = wmax < H3_WMIN;
+        if ((high || low) && *h3_ok) {
+          *h3_ok = false;
+          if (h3_why) {
+            char msg[200];
+            if (high) snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g times %g leaves the f16 range (the bound is %g)", l, (double)wmax, (double)H3_SW, (double)H3_WMAX);
+            else snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g is below %g: its outputs' second f16 plane falls into the denormals and accuracy is lost silently", l, (double)wmax, (double)H3_WMIN);
+            *h3_why = msg;
+          }
+        }
       }
       for (int l = 1; l < 8; ++l) {
         const std::vector<float> Wt = transposed(l);
@@ -849,7 +863,7 @@ int distr_set_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, const floa
   const int nlat = desc->latent_size;
   int rc;
   if (nlat == LAT) {
-    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok, ctx->dense_compact);
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok, ctx->dense_compact, &ctx->h3_why);
   } else {   // no split-arithmetic planes: bf16x6 / f16x3 refuse other code lengths (check_cfg, distr_mlp_eval_*)
     rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, nullptr, nullptr, nullptr, nullptr, ctx->dense_compact);
     if (!rc && ctx->dec_buf_b6) { HIP_TRY(hipFree(ctx->dec_buf_b6)); ctx->dec_buf_b6 = nullptr; ctx->B6 = DecoderB6{}; ctx->H3 = DecoderH3{}; ctx->h3_ok = false; }
@@ -1490,7 +1504,7 @@ static int mlp_eval_split(distr_ctx* ctx, bool h3, const float* latent, const fl
   EntryGuard guard_(ctx);
   if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
   if (ctx->D.nlat != LAT) return fail(ctx, DISTR_ERR_UNSUPPORTED, "%s: built for code length %d only (this decoder: %d); use f32", h3 ? "f16x3" : "bf16x6", LAT, ctx->D.nlat);
-  if (h3 && !ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: a decoder weight times %g leaves the f16 range; use bf16x6 or f32 for this decoder", (double)H3_SW);
+  if (h3 && !ctx->h3_ok) return fail(ctx, DISTR_ERR_UNSUPPORTED, "f16x3: %s; use bf16x6 or f32 for this decoder", ctx->h3_why.c_str());
   hipStream_t s = (hipStream_t)stream;
   PointList pl = plain_list(n);      // (exact f32: the latent columns stay a per-call constant)
   const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, xyz && sdf, ws, ws_bytes, false, s);

@@ -13,12 +13,19 @@
 // two f16 planes = the bytes of f32 (the bf16 form streams 1.5 x). profiles/ubench/split_f16_layer.hip: 34.3 k cycles per
 // 512 x 512 layer on a 64-ray tile (bf16x6 66.4 k, exact f32 133.7 k).
 //
-// What f16 costs is RANGE (5 exponent bits): a scaled operand beyond 65504 becomes inf. SX = SW = 64 keeps the second planes of
-// this network's magnitudes (activations 1e-3 .. 1, weights ~ 0.05) above the f16 denormals and allows |x|, |W| < 1023;
-// weights outside that range make the mode unavailable for the decoder (distr_set_decoder notes it, the calls that ask for the
-// mode fail), and an activation that overflows turns the evaluation's result non-finite, which the tiles COUNT
+// What f16 costs is RANGE (5 exponent bits), on both sides. Above: a scaled operand beyond 65504 becomes inf. SX = SW = 64 allows
+// |x|, |W| < 1023.5 (H3_WMAX); an activation that overflows turns the evaluation's result non-finite, which the tiles COUNT
 // (Consts.f16_overflow -> distr_render_stats.f16_overflows; distr_mlp_eval_f16x3 writes NaN for the point) instead of hiding it
-// behind the clamps of the march.
+// behind the clamps of the march. Below: the second plane of a value x holds SX x's bits 12..22; once it falls under 2^-14 it is an
+// f16 denormal (the conversions and the MFMA keep them: measured, tests/test_gpu_split_arith.py) with a fixed spacing of 2^-24,
+// so a layer whose activations are small loses accuracy and NOTHING is counted. SX = 64 keeps the second planes of this network's
+// magnitudes (activations 1e-3 .. 1, weights ~ 0.05) above that. Measured on function-preserving rescales of fixture F1 (one
+// layer's weights times 2^-k, the next layer's times 2^k; or lin1 times 2^-k and lin7 times 2^k), max |sdf - sdf_f64| relative
+// to the exact f32 kernel's on the same 8 193 points: 1.3 at k = 6 (smallest layer maximum 4.5e-3), 2.5 at k = 7 (2.3e-3),
+// 3.2 at k = 8, 13.5 at k = 10. distr_set_decoder therefore accepts the mode only when every layer's
+// largest |weight| lies in [H3_WMIN, H3_WMAX); otherwise the calls that ask for the mode fail and name the layer. This is a rule on
+// WEIGHTS: it cannot prove that activations stay large enough (a decoder whose small activations come from its inputs or biases
+// passes it); it was checked on the two rescale families above and on both fixtures.
 // The backward of a render in this mode (mlp_backward_h3) is the dX chain on the ReLU masks this forward saved, in the same
 // arithmetic, on deltas NORMALISED per ray by the loss gradient (whose range has no bound), with transposed weight planes.
 #pragma once
@@ -32,6 +39,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr float H3_SX = 64.f, H3_SW = 64.f;      // powers of two: every rescale below is exact
+
+constexpr float H3_WMAX = 65504.f / H3_SW;      // a layer's largest |weight| must stay below this (1023 passes, 1024 does not) ...
+constexpr float H3_WMIN = 0.00390625f;           // ... and reach this (2^-8: between the measured 4.5e-3, inside 2 x the f32 error, and 2.3e-3, outside)
 
 constexpr float H3_SD = 1024.f;                  // scale of the backward's per-ray normalised deltas (|delta / d8| < 64)
 

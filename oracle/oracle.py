@@ -77,6 +77,8 @@ def lib():
         L.orc_state_init_z.argtypes = [C.c_void_p, fp]
         L.orc_render_backward.restype = C.c_int64
         L.orc_render_backward.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp, fp, fp, fp]
+        L.orc_render_samples.restype = C.c_int64
+        L.orc_render_samples.argtypes = [C.c_void_p, C.c_void_p, fp, fp, fp, fp, C.c_int64, C.POINTER(C.c_int32), fp, fp]
         _lib = L
     return _lib
 
@@ -189,6 +191,18 @@ class RenderState(object):
         g_T = np.zeros(3, np.float32)
         ns = lib().orc_render_backward(self.oracle.h, self.ptr, _fp(gz), _fp(gq), _fp(gd), _fp(gn), _fp(g_lat), _fp(g_R), _fp(g_T))
         return g_lat.reshape(1, 256), g_R.reshape(3, 3), g_T, ns
+
+    def samples(self, g_zdepth=None, g_min_sdf=None, g_depth=None, g_normal=None):
+        """The gradient-carrying samples backward() builds from the same upstream gradients, in its order: (pixel (n,) int32,
+        point (n, 3), coef (n,)). The combined pad sample, if any, comes last with pixel -1 and the origin as its point.
+        g_latent = sum over the list of coef (1 - y^2) d pre / d code at the sample's point."""
+        grads = [_f32(g) for g in (g_zdepth, g_min_sdf, g_depth, g_normal)]
+        args = [self.oracle.h, self.ptr] + [_fp(g) for g in grads]
+        n = lib().orc_render_samples(*(args + [0, None, None, None]))
+        pix, pts, coef = np.zeros(n, np.int32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        if n:
+            lib().orc_render_samples(*(args + [n, pix.ctypes.data_as(C.POINTER(C.c_int32)), _fp(pts), _fp(coef)]))
+        return pix, pts, coef
 
 
 class Oracle(object):
