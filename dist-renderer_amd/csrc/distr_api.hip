@@ -43,7 +43,7 @@ struct distr_ctx {
   bool profiling = false;
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
   int tail16_threshold = 4096;  // t16: ... and on 16-ray tiles (16x16x4 MFMA)
-  bool dense_compact = true;    // DISTR_DENSE_COMPACT=0: the exact-f32 64-ray tile multiplies every hidden unit, live for the tile or not (a time knob)
+  bool dense_compact = true;    // DISTR_DENSE_COMPACT=0: the exact-f32 64-ray tile (march and saved-mask backward) multiplies every hidden unit, live for the tile or not (a time knob)
   bool save_masks = true;       // save ReLU masks in the forward so that the backward skips the decoder recompute
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
@@ -739,11 +739,18 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
     offWb[l] = reserve(Wt.size());
     pack_fragments(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], host.data() + offWb[l]);
   }
-  size_t offWk = 0;
+  size_t offWk = 0, offWkb = 0;
   compact = compact && !wide;     // the compacted tile exists in the narrow layout only
   if (compact) {
     offWk = reserve(WK_FLOATS);
     for (int l = 1; l < 8; ++l) pack_kmajor(Wp[l].data(), Kp[l], Op[l], host.data() + offWk + wk_offset(l));
+    // the same pack of the transposed matrices (backward dX chain: K' = Op[l], O' = Kp[l]; lin3^T and lin4^T swap their sizes, so layer l
+    // keeps its offset)
+    offWkb = reserve(WK_FLOATS);
+    for (int l = 1; l < 8; ++l) {
+      const std::vector<float> Wt = transposed(l);
+      pack_kmajor(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], host.data() + offWkb + wk_offset(l));
+    }
   }
   size_t offW16[8];
   for (int l = 0; l < 8; ++l) {
@@ -781,6 +788,7 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
   D.b8x[0] = nout > 1 ? b[8][1] : 0.f; D.b8x[1] = nout > 2 ? b[8][2] : 0.f;
   D.nlat = nlat;
   D.Wk = compact ? d + offWk : nullptr;
+  D.Wkb = compact ? d + offWkb : nullptr;
   if (D16) for (int l = 0; l < 8; ++l) D16->Wf[l] = d + offW16[l];
 #ifdef DISTR_DIAG
   // DIAGNOSTICS BUILDS ONLY (-DDISTR_DIAG; values are wrong): every 512 x 512 layer of the 16-ray / cluster tiles reads lin1's fragments, so
@@ -1035,7 +1043,8 @@ inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
 #define DISTR_TRY_MARCH(M, RB, K, AR, W, C) \
   DISTR_LAUNCH_IF(mode == M && rb == RB && keep == K && arith == AR && wide == W && compact == C, (k_march<M, RB, K, AR, W, C>), A, ctx->D)
 #define DISTR_TRY_MARCH16(M, K) DISTR_LAUNCH_IF(mode == M && keep == K, (k_march16<M, K>), A, ctx->D, ctx->D16)
-#define DISTR_TRY_BWD(M, RB, AR, W) DISTR_LAUNCH_IF(mode == M && rb == RB && arith == AR && wide == W, (k_bwd<M, RB, AR, W>), B, ctx->D)
+#define DISTR_TRY_BWD(M, RB, AR, W, C) \
+  DISTR_LAUNCH_IF(mode == M && rb == RB && arith == AR && wide == W && compact == C, (k_bwd<M, RB, AR, W, C>), B, ctx->D)
 
 // The compacted 64-ray tile (DISTR_DENSE_COMPACT) is a column of the lists: taken wherever the exact-f32 64-ray tile of the narrow layout
 // runs and the context packed the k-major weights for it (D.Wk); every other tile keeps the dense loop.
@@ -1064,8 +1073,10 @@ int launch_march16(distr_ctx* ctx, const char* what, int mode, bool keep, unsign
 }
 
 int launch_bwd(distr_ctx* ctx, const char* what, int mode, int rb, int arith, bool wide, unsigned grid, hipStream_t s, const BwdArgs& B) {
+  // the compacted backward: the 64-sample tile over saved masks only (BWD_FULL / BWD_POINTGRAD recompute the forward and keep the dense loop)
+  const bool compact = mode == BWD_SAVED && !wide && compact_tile(ctx, rb, arith) && ctx->D.Wkb != nullptr;
   DISTR_ALL_GROUPS(DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_TRY_BWD)
-  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_bwd<%d, %d, %d, %d> (distr_inst.hpp)", mode, rb, arith, (int)wide);
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_bwd<%d, %d, %d, %d, %d> (distr_inst.hpp)", mode, rb, arith, (int)wide, (int)compact);
 }
 
 // What a forward render has decided before its first march launch.

@@ -13,9 +13,10 @@
 namespace distr {
 
 // Every list takes one macro per kernel family and calls it once per variant, in the order the unit emits them:
-//   STEP(KEEP, ARITH, COMPACT)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE, COMPACT)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE)
+//   STEP(KEEP, ARITH, COMPACT)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE, COMPACT)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE, COMPACT)
 // KEEP = save the ReLU masks, RB = 32-ray blocks of a tile, ARITH = DISTR_ARITH_* (0 f32, 1 bf16x6, 2 f16x3), WIDE = the layout for
-// code lengths below 256, COMPACT = the 64-ray tile walks the live hidden units of a tile only (exact f32, narrow layout; distr_mlp.hpp).
+// code lengths below 256, COMPACT = the 64-ray / 64-sample tile walks the live hidden units of a tile only (exact f32, narrow layout;
+// distr_mlp.hpp; the backward: the tile over saved masks, BWD_SAVED, whose live sets are known before its chain starts).
 
 // the full-resolution step of the exact-f32 march (the headline kernel)
 #define DISTR_GROUP_1(STEP, TAIL, MARCH, MARCH16, BWD) \
@@ -40,14 +41,14 @@ namespace distr {
   MARCH(MODE_FINE, 2, true, 2, false, false) MARCH(MODE_FINE, 2, false, 2, false, false)
 // backward kernels
 #define DISTR_GROUP_6(STEP, TAIL, MARCH, MARCH16, BWD) \
-  BWD(BWD_FULL, 2, 0, false) BWD(BWD_POINTGRAD, 2, 0, false) \
-  BWD(BWD_SAVED, 1, 0, false) BWD(BWD_SAVED, 1, 1, false) BWD(BWD_SAVED, 1, 2, false) \
-  BWD(BWD_SAVED, 2, 0, false) BWD(BWD_SAVED, 2, 1, false) BWD(BWD_SAVED, 2, 2, false)
+  BWD(BWD_FULL, 2, 0, false, false) BWD(BWD_POINTGRAD, 2, 0, false, false) \
+  BWD(BWD_SAVED, 1, 0, false, false) BWD(BWD_SAVED, 1, 1, false, false) BWD(BWD_SAVED, 1, 2, false, false) \
+  BWD(BWD_SAVED, 2, 0, false, false) BWD(BWD_SAVED, 2, 1, false, false) BWD(BWD_SAVED, 2, 2, false, false)
 // the wide layout (code length < 256): 64-ray march tiles; 64- and 32-sample backward tiles
 #define DISTR_GROUP_7(STEP, TAIL, MARCH, MARCH16, BWD) \
   MARCH(MODE_EVAL, 2, false, 0, true, false) MARCH(MODE_COARSE, 2, true, 0, true, false) MARCH(MODE_COARSE, 2, false, 0, true, false) \
   MARCH(MODE_FINE, 2, true, 0, true, false) MARCH(MODE_FINE, 2, false, 0, true, false) \
-  BWD(BWD_FULL, 2, 0, true) BWD(BWD_POINTGRAD, 2, 0, true) BWD(BWD_SAVED, 2, 0, true) BWD(BWD_SAVED, 1, 0, true)
+  BWD(BWD_FULL, 2, 0, true, false) BWD(BWD_POINTGRAD, 2, 0, true, false) BWD(BWD_SAVED, 2, 0, true, false) BWD(BWD_SAVED, 1, 0, true, false)
 
 // the compacted 64-ray tile (DISTR_DENSE_COMPACT, the default): the step kernel ...
 #define DISTR_GROUP_8(STEP, TAIL, MARCH, MARCH16, BWD) \
@@ -57,11 +58,15 @@ namespace distr {
   MARCH(MODE_EVAL, 2, false, 0, false, true) MARCH(MODE_COARSE, 2, true, 0, false, true) MARCH(MODE_COARSE, 2, false, 0, false, true) \
   MARCH(MODE_FINE, 2, true, 0, false, true) MARCH(MODE_FINE, 2, false, 0, false, true)
 
-constexpr int DISTR_NUM_INST_GROUPS = 9;
+// ... and the 64-sample backward tile over saved masks
+#define DISTR_GROUP_10(STEP, TAIL, MARCH, MARCH16, BWD) \
+  BWD(BWD_SAVED, 2, 0, false, true)
+
+constexpr int DISTR_NUM_INST_GROUPS = 10;
 
 #define DISTR_ALL_GROUPS(...) \
   DISTR_GROUP_1(__VA_ARGS__) DISTR_GROUP_2(__VA_ARGS__) DISTR_GROUP_3(__VA_ARGS__) DISTR_GROUP_4(__VA_ARGS__) DISTR_GROUP_5(__VA_ARGS__) \
-  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__) DISTR_GROUP_8(__VA_ARGS__) DISTR_GROUP_9(__VA_ARGS__)
+  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__) DISTR_GROUP_8(__VA_ARGS__) DISTR_GROUP_9(__VA_ARGS__) DISTR_GROUP_10(__VA_ARGS__)
 #define DISTR_NO_VARIANT(...)      // for the families a use of the lists does not ask for
 
 // in a group's translation unit only that group is instantiated; the launching unit declares all of them extern
@@ -79,7 +84,7 @@ constexpr int DISTR_NUM_INST_GROUPS = 9;
 #define DISTR_K_TAIL(K) DISTR_INST_DEF __global__ void k_tail<K>(MarchArgs, DecoderDev, DecoderDev16);
 #define DISTR_K_MARCH(M, RB, K, AR, W, C) DISTR_INST_DEF __global__ void k_march<M, RB, K, AR, W, C>(MarchArgs, DecoderDev);
 #define DISTR_K_MARCH16(M, K) DISTR_INST_DEF __global__ void k_march16<M, K>(MarchArgs, DecoderDev, DecoderDev16);
-#define DISTR_K_BWD(M, RB, AR, W) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR, W>(BwdArgs, DecoderDev);
+#define DISTR_K_BWD(M, RB, AR, W, C) DISTR_INST_DEF __global__ void k_bwd<M, RB, AR, W, C>(BwdArgs, DecoderDev);
 
 DISTR_INST_LIST(DISTR_K_STEP, DISTR_K_TAIL, DISTR_K_MARCH, DISTR_K_MARCH16, DISTR_K_BWD)
 

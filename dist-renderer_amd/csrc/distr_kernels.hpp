@@ -2016,10 +2016,13 @@ __device__ __forceinline__ void bwd_range(int64_t count, int split, int tile_siz
   else { lo = full; hi = count; first_tile = t64; }
 }
 
-template <int MODE, int RB, int ARITH = 0, bool WIDE = false>
+// COMPACT (BWD_SAVED, 64 samples, exact f32, narrow layout; needs D.Wkb): every transposed layer walks the hidden units that are live for
+// the tile only -- mlp_backward's compacted chain; same bytes.
+template <int MODE, int RB, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
 __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(BwdArgs A, DecoderDev D) {
   static_assert(ARITH == 0 || MODE == BWD_SAVED, "the split-bf16 backward exists for saved masks only");
   static_assert(!WIDE || ARITH == 0, "the wide layout: exact f32");
+  static_assert(!COMPACT || (MODE == BWD_SAVED && RB == 2 && ARITH == 0 && !WIDE), "the compacted backward: saved masks, 64 samples, exact f32, narrow layout");
   constexpr int TILE = 32 * RB;
   __shared__ typename TileSmem<RB, ARITH>::type S;
   const View& V0 = A.V;
@@ -2144,7 +2147,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
     __syncthreads();
   }
   float* part = (MODE != BWD_POINTGRAD || partial) ? partial + (size_t)tile * PSTRIDE : nullptr;
-  if constexpr (ARITH == 0) mlp_backward<RB, 1, WIDE>(D, S, masks, part, part ? part + HID : nullptr);
+  if constexpr (ARITH == 0) mlp_backward<RB, 1, WIDE, COMPACT>(D, S, masks, part, part ? part + HID : nullptr);
   else if constexpr (ARITH == 1) mlp_backward_b6<RB>(D, A.B6, S, masks, part, part ? part + HID : nullptr);
   else mlp_backward_h3<RB>(D, A.H3, S, masks, part, part ? part + HID : nullptr);
 

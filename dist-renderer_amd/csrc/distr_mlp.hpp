@@ -82,6 +82,8 @@ struct DecoderDev {
   float b8;             // lin8 bias of row 0
   float b8x[2];         // lin8 biases of rows 1, 2 (colour decoder)
   int32_t nlat;         // latent length folded into c0 / c4 (the code length C of the SDF decoder; 256 + color_size for the colour decoder)
+  const float* Wkb;     // k-major packs of the TRANSPOSED lin1..lin7 (pack_kmajor of W_l^T: one row per output unit of lin_l over its input units; layer l
+                        // at wk_offset(l) -- lin3^T and lin4^T swap their sizes) for the compacted 64-sample backward tile; nullptr with Wk
   const float* Wk;      // k-major forward packs of lin1..lin7 (pack_kmajor; layer l at wk_offset(l)) for the compacted 64-ray tile; nullptr =
                         // DISTR_DENSE_COMPACT=0 (or the wide layout): the tile multiplies every hidden unit, live for the tile or not
 };
@@ -890,9 +892,134 @@ __device__ __forceinline__ void row_sums(const float* X, float* __restrict__ dst
   }
 }
 
+
+// ---------------------------------------------------------------------------------------- compacted 64-sample backward tile
+// The backward's K operand of layer l is delta_l, gated by the ReLU bits of h_l: a unit that is dead for all 64 samples of the tile has a
+// zero delta row, and every link through it is fma(w, +0, acc) -- a no-op of an accumulator that started at +0 (finite weights). Unlike the
+// forward, all live sets are known from the saved masks BEFORE the chain starts: the tables of the seven layers are built once per tile
+// and every write-back stores its rows straight to their positions (ascending feature order, zero rows up to a multiple of 16, at least
+// 32 -- compact_store's rule); no publish step, no barrier beyond the dense chain's two per layer. delta_0 is written dense.
+// The tables live in Smem<2>::bias (the forward's start values: idle in a backward over saved masks); the trash row of dead units is the
+// first row behind X (S.xyz: idle here, the compact loop has no tuple scratch). S.part / S.aux keep their roles (d8, d/dxyz).
+struct CompactBwdLds {
+  uint16_t postab[7][HID];   // [l - 1][unit of layer l] -> row of X its delta is stored to, or HID (the trash row) for a dead unit
+  uint16_t klist[7][HID];    // [l - 1][position] -> unit
+  uint32_t bits[7][16];      // live bits of layer l: word 4 * wave + ob, bit = row within the block (feature order)
+  uint32_t nlive[8];         // [l - 1]: live units of layer l
+};
+static_assert(sizeof(CompactBwdLds) <= sizeof(SmemBias<2>), "CompactBwdLds lives in Smem<2>::bias");
+
+// live bits of this wave's rows of one layer from the saved masks (bit 16 * rb + r of mask[ob]: see writeback), OR-ed over the tile's
+// 64 samples -- compact_publish without the accumulators
+template <int NOB>
+__device__ __forceinline__ void bwd_publish_bits(uint32_t* bits, const uint32_t (&mask)[4], int wave, int lane) {
+  uint32_t lw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) lw[ob] = (mask[ob] | (mask[ob] >> 16)) & 0xffffu;
+  uint32_t a = lw[0] | (lw[1] << 16), b = lw[2] | (lw[3] << 16);
+#define DISTR_OR_SWZ(x) do { a |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)a, ((x) << 10) | 0x1f); if (NOB == 4) b |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)b, ((x) << 10) | 0x1f); } while (0)
+  DISTR_OR_SWZ(1); DISTR_OR_SWZ(2); DISTR_OR_SWZ(4); DISTR_OR_SWZ(8); DISTR_OR_SWZ(16);
+#undef DISTR_OR_SWZ
+  const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, 32);
+  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32);
+  const uint32_t w0 = spread4(a0 & 0xffffu) | (spread4(a1 & 0xffffu) << 4), w1 = spread4(a0 >> 16) | (spread4(a1 >> 16) << 4);
+  const uint32_t w2 = spread4(b0 & 0xffffu) | (spread4(b1 & 0xffffu) << 4), w3 = spread4(b0 >> 16) | (spread4(b1 >> 16) << 4);
+  if (lane == 0) *reinterpret_cast<uint4*>(&bits[4 * wave]) = make_uint4(w0, w1, w2, w3);
+}
+
+__device__ __forceinline__ uint32_t compact_npad(uint32_t nlive) {
+  const uint32_t npad = (nlive + 15u) & ~15u;
+  return npad < 32u ? 32u : npad;
+}
+
+// positions of one layer from its published bits (compact_store's assignment): postab, klist, the list entries of the zero rows, nlive
+template <int NOB>
+__device__ __forceinline__ void bwd_build_table(CompactBwdLds& C, int li, int wave, int lane) {
+  constexpr int RW = 32 * NOB;
+  const int h = lane >> 5, j = lane & 31;
+  uint32_t cnt[4], own[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[li][4 * w]);
+    cnt[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)));
+  }
+  {
+    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[li][4 * wave]);
+    own[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x); own[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
+    own[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z); own[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w);
+  }
+  const uint32_t base = (wave > 0 ? cnt[0] : 0u) + (wave > 1 ? cnt[1] : 0u) + (wave > 2 ? cnt[2] : 0u);
+  const uint32_t nlive = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+#pragma unroll
+  for (int t = 0; t < NOB / 2; ++t) {
+    const uint32_t word = h ? own[2 * t + 1] : own[2 * t];
+    uint32_t below = (uint32_t)__popc(word & ((1u << j) - 1u)) + (h ? (uint32_t)__popc(own[2 * t]) : 0u);
+    if (t) below += (uint32_t)__popc(own[0]) + (uint32_t)__popc(own[1]);
+    const uint32_t pos = base + below;
+    const bool live = (word >> j) & 1u;
+    const uint32_t f = (uint32_t)wave * RW + 64 * t + lane;
+    C.postab[li][f] = (uint16_t)(live ? pos : (uint32_t)HID);
+    if (live) C.klist[li][pos] = (uint16_t)f;
+  }
+  const uint32_t npad = compact_npad(nlive);
+  for (uint32_t p = nlive + (uint32_t)(wave * 64 + lane); p < npad; p += NTHREADS) C.klist[li][p] = 0;   // zero rows: any valid unit
+  if (wave == 0 && lane == 0) C.nlive[li] = nlive;
+}
+
+// the zero rows behind the live rows of a layer just stored (exact no-op links of the next chain)
+__device__ __forceinline__ void bwd_zero_rows(float* X, uint32_t nlive, int wave, int lane) {
+  const uint32_t npad = compact_npad(nlive);
+  for (uint32_t p = nlive + (uint32_t)wave; p < npad; p += 4) X[p * 64 + lane] = 0.f;
+}
+
+// writeback<NOB, 2, false, true> through the position table of the layer being written: live rows to their positions, dead rows (all
+// bits 0: +0 for every sample) to the trash row
+template <int NOB>
+__device__ __forceinline__ void writeback_gate_compact(float* X, const uint16_t* postab, const f32x16 (&acc)[NOB][2], int row0, int lane,
+                                                       const uint32_t (&mask)[4]) {
+  const int h = lane >> 5, j = lane & 31;
+  char* xl = reinterpret_cast<char*>(X) + 4 * j;
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) {
+    const uint32_t m = mask[ob];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint2 pw = *reinterpret_cast<const uint2*>(postab + row0 + 32 * ob + 8 * q + 4 * h);
+      const uint32_t po[4] = {(pw.x & 0xffffu) << 8, (pw.x >> 16) << 8, (pw.y & 0xffffu) << 8, (pw.y >> 16) << 8};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float* dst = reinterpret_cast<float*>(xl + po[i]);
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) dst[32 * rb] = gate(acc[ob][rb][4 * q + i], (m >> (rb * 16 + 4 * q + i)) & 1u);
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// row_sums<2> of a compacted layer, by unit: a live unit's row is summed with the UNIT's rotation (the order of a row's adds decides its
+// last bits), a dead unit's sum is the +0 its dense zero row gives
+__device__ __forceinline__ void row_sums_compact(const float* X, const uint16_t* postab, float* __restrict__ dst, int tid) {
+  const int lane = tid & 63;
+#pragma unroll 1
+  for (int rr = 0; rr < 2; ++rr) {
+    const int row = tid + rr * 256;
+    const uint32_t pos = postab[row];
+    float s = 0.f;
+    if (pos < (uint32_t)HID) {
+#pragma unroll 8
+      for (int i = 0; i < 64; ++i) s += X[pos * 64 + ((i + lane) & 63)];
+    }
+    dst[row] = s;
+  }
+}
+
 // NOUT: rows of lin8 (1: SDF decoder; 3: colour decoder -- then S.aux rows 0..2 hold the three d8 rows and
 // delta7 = relu'(h7) * sum_c w8[c][k] * d8_c, accumulated in channel order)
-template <int RB, int NOUT = 1, bool WIDE = false>
+// COMPACT (64-sample narrow tile, NOUT = 1; needs D.Wkb; S.bias must be idle: a backward over saved masks): the chain walks the live units
+// of every layer only (dense_asm_compact_*_zero) -- same bytes in S.aux, sd0, sd4.
+template <int RB, int NOUT = 1, bool WIDE = false, bool COMPACT = false>
 __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, uint32_t (&masks)[8][4],
                                              float* __restrict__ sd0, float* __restrict__ sd4) {
   constexpr int TILE = 32 * RB;
@@ -902,6 +1029,82 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
   const int h = lane >> 5, j = lane & 31;
   const int ray = tid & (TILE - 1);
   float* X = S.X;
+  static_assert(!COMPACT || (RB == 2 && NOUT == 1 && !WIDE), "the compacted backward tile: 64 samples, one lin8 row, narrow layout");
+  if constexpr (COMPACT) {
+    static_assert(sizeof(Smem<RB>) == sizeof(SmemBias<RB>) + sizeof(float) * (HID + 4 + 12 + 4) * TILE, "no padding: the trash row (position HID) is S.xyz");
+    CompactBwdLds& C = *reinterpret_cast<CompactBwdLds*>(S.bias);
+    // live sets of layers 1..7 (layer 3: 256 rows, two row blocks per wave) and their tables, once per tile
+    static_for<7>([&](auto LI) {
+      constexpr int l = decltype(LI)::value + 1;
+      bwd_publish_bits<(l == 3) ? 2 : 4>(C.bits[l - 1], masks[l], wave, lane);
+    });
+    __syncthreads();
+    static_for<7>([&](auto LI) {
+      constexpr int l = decltype(LI)::value + 1;
+      bwd_build_table<(l == 3) ? 2 : 4>(C, l - 1, wave, lane);
+    });
+    __syncthreads();
+    {  // delta7[k][ray] = relu'(h7) * w8[k] * d8[ray], live rows at their positions
+      float d8[2];
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) d8[rb] = S.aux[32 * rb + j];
+      char* xl = reinterpret_cast<char*>(X) + 4 * j;
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) {
+        const uint32_t m = masks[7][ob];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = wave * 128 + 32 * ob + 8 * q + 4 * h;
+          const uint2 pw = *reinterpret_cast<const uint2*>(&C.postab[6][row]);
+          const uint32_t po[4] = {(pw.x & 0xffffu) << 8, (pw.x >> 16) << 8, (pw.y & 0xffffu) << 8, (pw.y >> 16) << 8};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float* dst = reinterpret_cast<float*>(xl + po[i]);
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) dst[32 * rb] = gate(D.w8[row + i] * d8[rb], (m >> (16 * rb + 4 * q + i)) & 1u);
+          }
+        }
+      }
+      bwd_zero_rows(X, C.nlive[6], wave, lane);
+    }
+    __syncthreads();
+    const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)j * 4;
+    // (static_for: every layer straight-line code with its own masks[l] registers; K operand delta_l, weights lin_l^T, output delta_{l-1})
+    static_for<7>([&](auto LI) {
+      constexpr int l = 7 - decltype(LI)::value;
+      const uint32_t kaddr = lds_off(C.klist[l - 1]) + (uint32_t)h * 2;
+      const uint32_t npad = compact_npad(C.nlive[l - 1]);
+      if constexpr (l == 4) {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
+        f32x16 acc[2][2];
+        dense_asm_compact_n2_zero(acc, xaddr, kaddr, (uint32_t)j * 8, kmajor_rsrc(D.Wkb + wk_offset(4), 1024, 512), (uint32_t)wave * 256,
+                                  compact_trips(npad, 512));
+        __syncthreads();
+        writeback_gate_compact<2>(X, C.postab[2], acc, wave * 64, lane, masks[3]);  // rows 253..255 have mask 0: dead
+        bwd_zero_rows(X, C.nlive[2], wave, lane);
+        if (wave == 3 && h == 1) {
+#pragma unroll
+          for (int r = 13; r < 16; ++r)
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[1][rb][r];
+        }
+        __syncthreads();
+      } else {
+        constexpr int K = (l == 3) ? 256 : 512;   // lin3^T: delta3 (256 rows, 253 real)
+        f32x16 acc[4][2];
+        dense_asm_compact_n4_zero(acc, xaddr, kaddr, (uint32_t)j * 16, kmajor_rsrc(D.Wkb + wk_offset(l), 2048, K), (uint32_t)wave * 512,
+                                  compact_trips(npad, K));
+        __syncthreads();
+        if constexpr (l == 1) {
+          writeback<4, 2, false, true>(X, acc, wave * 128, lane, masks[0]);      // delta0: dense (row_sums, the W0x chains)
+        } else {
+          writeback_gate_compact<4>(X, C.postab[l - 2], acc, wave * 128, lane, masks[l - 1]);
+          bwd_zero_rows(X, C.nlive[l - 2], wave, lane);
+        }
+        __syncthreads();
+        if constexpr (l == 5) { if (sd4) row_sums_compact(X, C.postab[3], sd4, tid); }  // X = delta4
+      }
+    });
+  } else {
   // delta7[k][ray] = relu'(h7) * w8[k] * d8[ray]
   {
     float d8[NOUT][RB];
@@ -1072,6 +1275,7 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
     __syncthreads();
   }
   }
+  }  // !COMPACT
   if (sd0) row_sums<RB>(X, sd0, tid);  // X = delta0
   // d xyz through lin0's xyz columns: 3 x four 128-long chains per ray
   {

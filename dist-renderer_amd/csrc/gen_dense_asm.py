@@ -318,7 +318,9 @@ IDX = 160
 VK = 168
 
 
-def gen_compact(NOB):
+def gen_compact(NOB, INIT='bias'):
+    """INIT: 'bias' (accumulators start from LDS bias tuples: the forward) or 'zero' (the backward's dX chain: no bias reads, no bias operand)."""
+    bias = INIT == 'bias'
     L = []
     emit = L.append
     width = {4: 'dwordx4', 2: 'dwordx2'}[NOB]
@@ -380,8 +382,9 @@ def gen_compact(NOB):
     slot_of = {0: 0, 1: 1, 2: 2, 3: 0}
 
     def bias_tuple(ob):
-        for q in range(4):
-            lds('ds_read_b128 %s, %%[bias] offset:%d' % (ar(BIAS[slot_of[ob]] + 4 * q, 4), ob * 128 + q * 32), 'bias%d' % ob)
+        if bias:
+            for q in range(4):
+                lds('ds_read_b128 %s, %%[bias] offset:%d' % (ar(BIAS[slot_of[ob]] + 4 * q, 4), ob * 128 + q * 32), 'bias%d' % ob)
 
     def b0(s):
         for rb in range(2):
@@ -390,7 +393,7 @@ def gen_compact(NOB):
     def first_mfmas(ob):
         wait_for('b0s0', 'bias%d' % ob)
         for rb in range(2):
-            mfma(0, 0, ob, rb, ar(BIAS[slot_of[ob]], 16))
+            mfma(0, 0, ob, rb, ar(BIAS[slot_of[ob]], 16) if bias else '0')
 
     # ---------------------------------------------------------------- prologue: groups 0 and 1 requested, indices of group 2 read
     emit('s_nop 4')
@@ -446,20 +449,25 @@ def gen_compact(NOB):
     emit('s_nop 3')
     body = '\n'.join('      "%s\\n"' % x for x in L)
 
-    name = 'dense_asm_compact_n%d_bias' % NOB
+    name = 'dense_asm_compact_n%d_%s' % (NOB, INIT)
     outs = ', '.join('[c%d%d] "=&a"(acc[%d][%d])' % (ob, rb, ob, rb) for ob in range(NOB) for rb in range(2))
-    ins = '[xaddr] "v"(xaddr), [kaddr] "v"(kaddr), [voff] "v"(voff), [rs] "s"(rs), [soff] "s"(soff), [nit] "s"(nit), [bias] "v"(biasaddr)'
-    clob = ['"v%d"' % i for i in range(IDX, VK + 1)] + ['"v%d"' % i for i in range(A[0], VX + 1)] + ['"a%d"' % i for i in range(BIAS[0], BIAS[2] + 16)] + ['"%s"' % S_CNT, '"scc"', '"memory"']
-    return name, '''// compacted tile: %d row blocks of 32 per wave; nit = positions / 16 - 1 (>= 1); klist / Wk: see gen_dense_asm.py
-__device__ __forceinline__ void %s(f32x16 (&acc)[%d][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff,
-    uint32_t nit, uint32_t biasaddr) {
+    ins = '[xaddr] "v"(xaddr), [kaddr] "v"(kaddr), [voff] "v"(voff), [rs] "s"(rs), [soff] "s"(soff), [nit] "s"(nit)' + (', [bias] "v"(biasaddr)' if bias else '')
+    clob = ['"v%d"' % i for i in range(IDX, VK + 1)] + ['"v%d"' % i for i in range(A[0], VX + 1)] + (['"a%d"' % i for i in range(BIAS[0], BIAS[2] + 16)] if bias else []) + ['"%s"' % S_CNT, '"scc"', '"memory"']
+    if bias:
+        head = '// compacted tile: %d row blocks of 32 per wave; nit = positions / 16 - 1 (>= 1); klist / Wk: see gen_dense_asm.py' % NOB
+        tail = ',\n    uint32_t nit, uint32_t biasaddr) {'
+    else:
+        head = '// compacted tile, accumulators start from zero (the backward dX chain; weights: the transposed k-major pack Wkb): %d row blocks of 32 per wave' % NOB
+        tail = ',\n    uint32_t nit) {'
+    return name, '''%s
+__device__ __forceinline__ void %s(f32x16 (&acc)[%d][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff%s
   asm volatile(
 %s
       : %s
       : %s
       : %s);
 }
-''' % (NOB, name, NOB, body, outs, ins, ', '.join(clob))
+''' % (head, name, NOB, tail, body, outs, ins, ', '.join(clob))
 
 
 def main():
@@ -474,6 +482,8 @@ def main():
         out.append(gen16(K, NB, NOUT)[1])
     for NOB in (4, 2):
         out.append(gen_compact(NOB)[1])
+    for NOB in (4, 2):
+        out.append(gen_compact(NOB, 'zero')[1])
     out.append('}  // namespace distr')
     sys.stdout.write('\n'.join(out) + '\n')
 
