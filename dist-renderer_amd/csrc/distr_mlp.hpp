@@ -132,6 +132,13 @@ __device__ __forceinline__ const float* layer_init(const DecoderDev& D, const fl
   else return (l == 0) ? c0 : (l == 4) ? c4 : D.bias[l];
 }
 
+// Smem<2>::bias, or nullptr for the tile that has none
+template <int RB>
+__device__ __forceinline__ float* bias_base(Smem<RB>& S) {
+  if constexpr (RB == 2) return S.bias;
+  else return nullptr;
+}
+
 // ---------------------------------------------------------------------------------------- scalar math
 // tanh in explicit IEEE operations so that host (oracle) and device agree bit for bit.
 __device__ __forceinline__ float exp_spec(float x) {
@@ -228,7 +235,7 @@ __device__ __forceinline__ void dense(const float* __restrict__ Wp, const float*
     f32x4 an[NOB];
     float bn[4][RB];
     const int gn = (g + 1 < NG) ? g + 1 : g;
-    const f32x4* wn = wp + (size_t)gn * (4 * NOB * 64);
+    const f32x4* wn = wp + (uint32_t)gn * (uint32_t)(4 * NOB * 64);    // (a 32-bit index, at most 63 * 1024: a 64-bit product costs the loop an SGPR pair)
 #pragma unroll
     for (int ob = 0; ob < NOB; ++ob) an[ob] = wn[ob * 64];
     const float* xg = xb + (size_t)gn * 8 * TILE;
@@ -386,6 +393,68 @@ __device__ __forceinline__ uint32_t spread4(uint32_t x) {   // bit 4q + i -> bit
   return (x & 0xfu) | ((x & 0xf0u) << 4) | ((x & 0xf00u) << 8) | ((x & 0xf000u) << 12);
 }
 
+// OR of per-lane live words over the tile's 64 rays / samples, published as the wave's four words bits[4 * wave ..]. lw[ob], bit r = "row
+// (r & 3) + 8 * (r >> 2) + 4 * h of the wave's block ob is live on this lane" (the accumulator layout: see writeback).
+template <int NOB>
+__device__ __forceinline__ void publish_live_words(uint32_t* bits, const uint32_t (&lw)[4], int wave, int lane) {
+  uint32_t a = lw[0] | (lw[1] << 16), b = lw[2] | (lw[3] << 16);
+  // OR over the 32 lanes of each half-wave (ds_swizzle, xor butterfly)
+  static_for<5>([&](auto I) {
+    constexpr int x = 1 << decltype(I)::value;
+    a |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)a, (x << 10) | 0x1f);
+    if (NOB == 4) b |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)b, (x << 10) | 0x1f);
+  });
+  const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, 32);
+  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32);
+  // lane (j, h) holds rows (r & 3) + 8 * (r >> 2) + 4 * h of a block: interleave the two halves' nibbles into feature order
+  const uint32_t w0 = spread4(a0 & 0xffffu) | (spread4(a1 & 0xffffu) << 4), w1 = spread4(a0 >> 16) | (spread4(a1 >> 16) << 4);
+  const uint32_t w2 = spread4(b0 & 0xffffu) | (spread4(b1 & 0xffffu) << 4), w3 = spread4(b0 >> 16) | (spread4(b1 >> 16) << 4);
+  if (lane == 0) *reinterpret_cast<uint4*>(&bits[4 * wave]) = make_uint4(w0, w1, w2, w3);
+}
+
+// Positions from the published words of a layer (all four waves' words visible): live units take consecutive positions in ascending
+// feature order. live_counts: this wave's own words, the live units of the waves below it (base) and of the whole layer (nlive).
+struct LiveCounts {
+  uint32_t own[4], base, nlive;
+};
+
+__device__ __forceinline__ LiveCounts live_counts(const uint32_t* bits, int wave) {
+  LiveCounts L;
+  uint32_t cnt[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint4 q = *reinterpret_cast<const uint4*>(&bits[4 * w]);
+    cnt[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)));
+  }
+  {
+    const uint4 q = *reinterpret_cast<const uint4*>(&bits[4 * wave]);
+    L.own[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x); L.own[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
+    L.own[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z); L.own[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w);
+  }
+  L.base = (wave > 0 ? cnt[0] : 0u) + (wave > 1 ? cnt[1] : 0u) + (wave > 2 ? cnt[2] : 0u);
+  L.nlive = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  return L;
+}
+
+// the t-th of the NOB / 2 units this lane owns (unit = wave * 32 * NOB + 64 * t + lane): its position among the live units (meaningful
+// for a live unit only); returns whether it is live
+template <int NOB>
+__device__ __forceinline__ bool unit_position(const LiveCounts& L, int t, int wave, int lane, uint32_t& unit, uint32_t& pos) {
+  const int h = lane >> 5, j = lane & 31;
+  const uint32_t word = h ? L.own[2 * t + 1] : L.own[2 * t];
+  uint32_t below = (uint32_t)__popc(word & ((1u << j) - 1u)) + (h ? (uint32_t)__popc(L.own[2 * t]) : 0u);
+  if (t) below += (uint32_t)__popc(L.own[0]) + (uint32_t)__popc(L.own[1]);
+  pos = L.base + below;
+  unit = (uint32_t)wave * (32 * NOB) + 64 * t + lane;
+  return (word >> j) & 1u;
+}
+
+// rows of X a layer with nlive stored rows hands to the next k-loop: the next multiple of 16, at least 32 (compact_trips)
+__device__ __forceinline__ uint32_t compact_npad(uint32_t nlive) {
+  const uint32_t npad = (nlive + 15u) & ~15u;
+  return npad < 32u ? 32u : npad;
+}
+
 // Before the layer's first barrier: the ReLU bits of this wave's rows (KEEP: into mask[], exactly as writeback() forms them), OR-ed
 // over the tile's 64 rays, published as the wave's words of C.bits.
 template <int NOB, bool KEEP>
@@ -411,17 +480,7 @@ __device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&ac
       lw[ob] = m;
     }
   }
-  uint32_t a = lw[0] | (lw[1] << 16), b = lw[2] | (lw[3] << 16);
-  // OR over the 32 lanes of each half-wave (ds_swizzle, xor butterfly)
-#define DISTR_OR_SWZ(x) do { a |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)a, ((x) << 10) | 0x1f); if (NOB == 4) b |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)b, ((x) << 10) | 0x1f); } while (0)
-  DISTR_OR_SWZ(1); DISTR_OR_SWZ(2); DISTR_OR_SWZ(4); DISTR_OR_SWZ(8); DISTR_OR_SWZ(16);
-#undef DISTR_OR_SWZ
-  const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, 32);
-  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32);
-  // lane (j, h) holds rows (r & 3) + 8 * (r >> 2) + 4 * h of a block: interleave the two halves' nibbles into feature order
-  const uint32_t w0 = spread4(a0 & 0xffffu) | (spread4(a1 & 0xffffu) << 4), w1 = spread4(a0 >> 16) | (spread4(a1 >> 16) << 4);
-  const uint32_t w2 = spread4(b0 & 0xffffu) | (spread4(b1 & 0xffffu) << 4), w3 = spread4(b0 >> 16) | (spread4(b1 >> 16) << 4);
-  if (lane == 0) *reinterpret_cast<uint4*>(&C.bits[4 * wave]) = make_uint4(w0, w1, w2, w3);
+  publish_live_words<NOB>(C.bits, lw, wave, lane);
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -432,29 +491,14 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
   constexpr int RW = 32 * NOB;             // rows of a wave
   const int tid = threadIdx.x;
   const int h = lane >> 5, j = lane & 31;
-  uint32_t cnt[4], own[4];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[4 * w]);
-    cnt[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)));
-  }
-  {
-    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[4 * wave]);
-    own[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x); own[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
-    own[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z); own[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w);
-  }
-  const uint32_t base = (wave > 0 ? cnt[0] : 0u) + (wave > 1 ? cnt[1] : 0u) + (wave > 2 ? cnt[2] : 0u);
-  const uint32_t nlive = cnt[0] + cnt[1] + cnt[2] + cnt[3];
   const uint32_t trash_off = lds_off(C.trash) - lds_off(X);
   // lane <-> unit: where each of the wave's rows goes, and the list entry of the live ones
+  const LiveCounts L = live_counts(C.bits, wave);
+  const uint32_t nlive = L.nlive;
 #pragma unroll
   for (int t = 0; t < NOB / 2; ++t) {
-    const uint32_t word = h ? own[2 * t + 1] : own[2 * t];
-    uint32_t below = (uint32_t)__popc(word & ((1u << j) - 1u)) + (h ? (uint32_t)__popc(own[2 * t]) : 0u);
-    if (t) below += (uint32_t)__popc(own[0]) + (uint32_t)__popc(own[1]);
-    const uint32_t pos = base + below;
-    const bool live = (word >> j) & 1u;
-    const uint32_t f = (uint32_t)wave * RW + 64 * t + lane;
+    uint32_t f, pos;
+    const bool live = unit_position<NOB>(L, t, wave, lane, f, pos);
     C.postab[f] = live ? pos * 256u : trash_off;
     if (live) C.klist[pos] = (uint16_t)f;
   }
@@ -488,8 +532,7 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
     }
     nl += 3;
   }
-  uint32_t npad = (nl + 15u) & ~15u;
-  if (npad < 32u) npad = 32u;
+  const uint32_t npad = compact_npad(nl);
   for (uint32_t p = nl + (uint32_t)wave; p < npad; p += 4) {      // zero rows: exact no-op links; their list entries name any valid unit
     X[p * 64 + lane] = 0.f;
     if (lane == 0) C.klist[p] = 0;
@@ -560,6 +603,21 @@ __device__ __forceinline__ void load_mask_chunk(const uint4* blk, uint32_t (&mas
   }
 }
 
+// ---------------------------------------------------------------------------------------- the decoder chain
+// lin1..lin7 as the 64- / 32-ray tiles walk them (lin0 and lin8 are written out in mlp_forward / mlp_backward). Layer l multiplies K(l)
+// rows of X, a wave owns NOB(l) row blocks of 32 outputs; the tile's xyz rows join X behind lin3's outputs at XYZ_ROW, as lin4's last three
+// input features. Everything else a layer needs follows: its waves' first row (wave * 32 * NOB), the prefetch width its k-loop is handed
+// (the NOB of the layer that runs next; 0 behind the last one), and the backward's shapes -- lin_l transposed has NOB(l) * 128 input rows
+// and K(l) / 128 row blocks per wave.
+template <bool WIDE>
+struct Chain {
+  static constexpr int K(int l) { return (!WIDE && l == 4) ? 256 : 512; }
+  static constexpr int NOB(int l) { return (l < 0 || l > 7) ? 0 : (!WIDE && l == 3) ? 2 : 4; }    // (l = 0: lin0, for the fragments lin1 finds prefetched)
+  static constexpr int XYZ_ROW = WIDE ? 509 : 253;
+  static constexpr int KT(int l) { return 128 * NOB(l); }                     // lin_l^T: delta_l -> delta_{l-1}
+  static constexpr int NOBT(int l) { return (l < 1) ? 0 : K(l) / 128; }
+};
+
 // ---------------------------------------------------------------------------------------- forward tile
 // Preconditions: S.xyz rows 0..2 hold the TILE points (x row, y row, z row), visible to all threads (barrier done).
 // One row of lin8 on the h7 activations in S.X: four 128-long chains per ray (one per wave), combined in fixed order.
@@ -602,7 +660,7 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
   const int ray = tid & (TILE - 1);
   float* X = S.X;
   static_assert(!COMPACT || (RB == 2 && !WIDE), "the compacted tile is the 64-ray tile of the narrow layout");
-  constexpr bool compact = COMPACT;
+  using CH = Chain<WIDE>;
   uint32_t npad = HID;   // compacted tile: rows of X the next layer walks
   // first weight group of every layer travels while the previous layer finishes (dense_pf)
   f32x4 wpre[4];
@@ -621,14 +679,8 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 0), wave * 128, h);
     dense_pf<8, 4, RB, 4, 4, 4>(D.Wf[0], X, acc, wave, lane, wpre, COMPACT ? nullptr : D.Wf[1]);
     DISTR_TS(1);
-    if constexpr (COMPACT) {
-      if (compact && !(DEBUG_STOP && stop == 0)) {
-        npad = writeback_compact<4, KEEP, false>(S, acc, wave, lane, masks[0]);
-      } else {
-        __syncthreads();
-        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[0]);
-        __syncthreads();
-      }
+    if (COMPACT && !(DEBUG_STOP && stop == 0)) {
+      if constexpr (COMPACT) npad = writeback_compact<4, KEEP, false>(S, acc, wave, lane, masks[0]);
     } else {
       __syncthreads();
       writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[0]);
@@ -637,237 +689,63 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     DISTR_TS(2);
   }
   if (DEBUG_STOP && stop == 0) return 0.f;
-  if constexpr (COMPACT) {
-    if (compact) {
-      // layers 1..7 over the live units of the tile (dense_asm_compact_*): every layer but the last -- and, in a DEBUG_STOP build, the one
-      // whose activations are dumped by feature -- leaves its output compacted for the next one; lin8_row reads the dense h7
-      CompactLds& C = *reinterpret_cast<CompactLds*>(S.part);
-      const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)(lane & 31) * 4;
-      const uint32_t kaddr = lds_off(C.klist) + (uint32_t)h * 2;
-      const uint32_t bias4 = lds_off(S.bias) + (uint32_t)wave * 512 + (uint32_t)h * 16;
-      const uint32_t bias2 = lds_off(S.bias) + 3 * 2048 + (uint32_t)wave * 256 + (uint32_t)h * 16;
-      // (static_for, not a loop with an unroll pragma: every layer must be straight-line code with its own masks[l] registers)
-      bool stopped = false;
-      static_for<7>([&](auto LI) {
-        constexpr int l = decltype(LI)::value + 1;
-        if (DEBUG_STOP && stopped) return;
-        if constexpr (l == 3) {  // lin3: 512 -> 253; the xyz rows join the list as units 253..255
-          f32x16 acc[2][2];
-          dense_asm_compact_n2_bias(acc, xaddr, kaddr, (uint32_t)(lane & 31) * 8, kmajor_rsrc(D.Wk + wk_offset(3), 1024, 512), (uint32_t)wave * 256,
-                                    compact_trips(npad, 512), bias2);
-          DISTR_TS(7);
-          masks[3][2] = 0; masks[3][3] = 0;
-          if (DEBUG_STOP && stop == 3) {
-            __syncthreads();
-            writeback<2, RB, true, false, KEEP>(X, acc, wave * 64, lane, masks[3]);
-            __syncthreads();
-            if (tid < 3 * TILE) X[253 * TILE + tid] = S.xyz[tid];
-            __syncthreads();
-            stopped = true;
-            return;
-          }
-          npad = writeback_compact<2, KEEP, true>(S, acc, wave, lane, masks[3]);
-          DISTR_TS(8);
-        } else {
-          f32x16 acc[4][2];
-          constexpr int K = (l == 4) ? 256 : 512;
-          dense_asm_compact_n4_bias(acc, xaddr, kaddr, (uint32_t)(lane & 31) * 16, kmajor_rsrc(D.Wk + wk_offset(l), 2048, K), (uint32_t)wave * 512,
-                                    compact_trips(npad, K), bias4 + l * 2048);
-          DISTR_TS(2 * l + 1);
-          if (l == 7 || (DEBUG_STOP && stop == l)) {
-            __syncthreads();
-            writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
-            __syncthreads();
-            DISTR_TS(2 * l + 2);
-            if (DEBUG_STOP && stop == l) stopped = true;
-          } else {
-            npad = writeback_compact<4, KEEP, false>(S, acc, wave, lane, masks[l]);
-            DISTR_TS(2 * l + 2);
-          }
-        }
-      });
-      if (DEBUG_STOP && stopped) return 0.f;
-      const float pre_c = lin8_row<RB>(D.w8, D.b8, S);
-      DISTR_TS(17);
-      return pre_c;
-    }
-  }
+  // Layers 1..7 on one of three k-loop engines:
+  //   compacted (COMPACT): dense_asm_compact_* over the live units of the tile. Every layer but the last -- and, in a DEBUG_STOP build, the one
+  //     whose activations are dumped by feature -- leaves its output compacted for the next one; lin8_row reads the dense h7.
+  //   hand-scheduled (64-ray tile): dense_asm_k* (distr_dense_asm.hpp). Every layer's accumulators start from the LDS copy of its bias (srcC of
+  //     the first MFMAs); the next layer's first weight group travels in `wpre` across the write-back; S.part..S.aux (4 KiB, idle during the
+  //     layers) is the scratch of the tuple -> register move.
+  //   C++ (32-ray tile): acc_init + dense_pf, the first weight group in `wpre` likewise.
+  // per-thread operands of the two asm engines, each marked with the engine that reads it (an engine that is not instantiated leaves
+  // its operands unused; the C++ engine reads none of them: it takes pointers)
+  const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)(lane & 31) * 4;            // (compacted, hand-scheduled) this lane's column of X
+  const uint32_t bias0 = lds_off(bias_base(S)) + (uint32_t)h * 16;     // (compacted, hand-scheduled) + l * 2048 + (the wave's first row) * 4: start values of layer l's rows
+  const uint32_t kaddr = lds_off(reinterpret_cast<CompactLds*>(S.part)->klist) + (uint32_t)h * 2;      // (compacted only) this half-wave's entries of klist
+  const uint32_t voff = (uint32_t)lane * 16;                                                            // (hand-scheduled only) lane offset into a weight fragment
+  const uint32_t scratch = lds_off(S.part) + (uint32_t)wave * 1024 + (uint32_t)lane * 16;              // (hand-scheduled only) tuple -> register scratch
+  rsrc_t rs[8];                                                                                         // (hand-scheduled only) fragment streams of lin1..lin7
   if constexpr (RB == 2 && !COMPACT) {
-    // 64-ray tile: layers 1..7 on the hand-scheduled loop (distr_dense_asm.hpp). Every layer's accumulators start from the
-    // LDS copy of its bias (srcC of the first MFMAs); the next layer's first weight group travels in `wpre` across the
-    // write-back; S.part..S.aux (4 KiB, idle during the layers) is the scratch of the tuple -> register move.
-    const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)(lane & 31) * 4;
-    const uint32_t voff = (uint32_t)lane * 16;
-    const uint32_t scratch = lds_off(S.part) + (uint32_t)wave * 1024 + (uint32_t)lane * 16;
-    const uint32_t bias4 = lds_off(S.bias) + (uint32_t)wave * 512 + (uint32_t)h * 16;   // + l * 2048: rows wave*128 .. of layer l
-    const uint32_t bias2 = lds_off(S.bias) + 3 * 2048 + (uint32_t)wave * 256 + (uint32_t)h * 16;   // lin3: rows wave*64 ..
-    const uint32_t soff4 = (uint32_t)wave * 4096, soff2 = (uint32_t)wave * 2048;
-    rsrc_t rs[8];
 #pragma unroll
     for (int l = 1; l < 8; ++l) rs[l] = weight_rsrc(D.Wf[l]);
-    {
-      f32x16 acc[4][2];
-      dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[1], rs[2], soff4, soff4, bias4 + 1 * 2048, scratch);
-      DISTR_TS(3);
-      __syncthreads();
-      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[1]);
-      __syncthreads();
-      DISTR_TS(4);
-      if (DEBUG_STOP && stop == 1) return 0.f;
+  }
+  // (static_for, not a loop with an unroll pragma: every layer must be straight-line code with its own masks[l] registers)
+  bool stopped = false;
+  static_for<7>([&](auto LI) {
+    constexpr int l = decltype(LI)::value + 1;
+    constexpr int K = CH::K(l), NOB = CH::NOB(l), NOBN = CH::NOB(l + 1), LN = NOBN ? l + 1 : l;   // LN: the layer whose first fragments a k-loop prefetches
+    if (DEBUG_STOP && stopped) return;
+    const int row0 = wave * (32 * NOB);     // the wave's first output row
+    f32x16 acc[NOB][RB];
+    if constexpr (COMPACT) {
+      dense_asm_compact<NOB, true>(acc, xaddr, kaddr, (uint32_t)(lane & 31) * (4 * NOB), kmajor_rsrc(D.Wk + wk_offset(l), 512 * NOB, K),
+                                   (uint32_t)wave * (128 * NOB), compact_trips(npad, K), bias0 + l * 2048 + (uint32_t)wave * (128 * NOB));
+    } else if constexpr (RB == 2) {
+      dense_asm<K, NOB, NOBN, true>(acc, wpre, xaddr, voff, rs[l], rs[LN], (uint32_t)wave * (1024 * NOB),
+                                    (uint32_t)wave * (1024 * (NOBN ? NOBN : NOB)), bias0 + l * 2048 + (uint32_t)wave * (128 * NOB), scratch);
+    } else {
+      // dense_pf's prefetch slots: the previous layer left min(its NOB, this NOB) fragments of this layer's first group in wpre (NIN); this one
+      // leaves min(NOB, NOBN) of the next layer's (NOUT). Behind lin7 nothing is fetched (nullptr) and NOUT / NOBN only keep their static_assert.
+      constexpr int NIN = CH::NOB(l - 1) < NOB ? CH::NOB(l - 1) : NOB, NOUT = (NOBN && NOBN < NOB) ? NOBN : NOB;
+      acc_init<NOB, RB>(acc, layer_init<RB>(D, c0, c4, S, l), row0, h);
+      dense_pf<K, NOB, RB, NIN, NOUT, (NOBN ? NOBN : NOB)>(D.Wf[l], X, acc, wave, lane, wpre, NOBN ? D.Wf[LN] : nullptr);
     }
-    {
-      f32x16 acc[4][2];
-      if constexpr (WIDE) dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[2], rs[3], soff4, soff4, bias4 + 2 * 2048, scratch);
-      else dense_asm_k512_n4_o2_bias(acc, wpre, xaddr, voff, rs[2], rs[3], soff4, soff2, bias4 + 2 * 2048, scratch);
-      DISTR_TS(5);
+    DISTR_TS(2 * l + 1);
+    if constexpr (NOB < 4) { masks[l][2] = 0; masks[l][3] = 0; }   // lin3 of the narrow layout: two row blocks per wave
+    if (!COMPACT || l == 7 || (DEBUG_STOP && stop == l)) {
       __syncthreads();
-      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[2]);
+      writeback<NOB, RB, true, false, KEEP>(X, acc, row0, lane, masks[l]);   // (wide lin3, rows 509..511: zero weights and bias, mask 0)
       __syncthreads();
-      DISTR_TS(6);
-      if (DEBUG_STOP && stop == 2) return 0.f;
-    }
-    if constexpr (WIDE) {  // lin3: 512 -> 509 (+3 rows that carry xyz into lin4); lin4: [x3 (509) | xyz (3)] -> 512
-      {
-        f32x16 acc[4][2];
-        dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[3], rs[4], soff4, soff4, bias4 + 3 * 2048, scratch);
-        DISTR_TS(7);
+      if constexpr (l == 3) {  // the rows that carry xyz into lin4: [x3 | xyz] -> 512, latent part folded into c4
+        if (tid < 3 * TILE) X[CH::XYZ_ROW * TILE + tid] = S.xyz[tid];
         __syncthreads();
-        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[3]);   // rows 509..511: zero weights and bias, mask 0
-        __syncthreads();
-        if (tid < 3 * TILE) X[509 * TILE + tid] = S.xyz[tid];
-        __syncthreads();
-        DISTR_TS(8);
-        if (DEBUG_STOP && stop == 3) return 0.f;
-      }
-      {
-        f32x16 acc[4][2];
-        dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[4], rs[5], soff4, soff4, bias4 + 4 * 2048, scratch);
-        DISTR_TS(9);
-        __syncthreads();
-        writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[4]);
-        __syncthreads();
-        DISTR_TS(10);
-        if (DEBUG_STOP && stop == 4) return 0.f;
       }
     } else {
-    {  // lin3: 512 -> 253 (+3 rows that carry xyz into lin4)
-      f32x16 acc[2][2];
-      dense_asm_k512_n2_o4_bias(acc, wpre, xaddr, voff, rs[3], rs[4], soff2, soff4, bias2, scratch);
-      DISTR_TS(7);
-      __syncthreads();
-      masks[3][2] = 0; masks[3][3] = 0;
-      writeback<2, RB, true, false, KEEP>(X, acc, wave * 64, lane, masks[3]);
-      __syncthreads();
-      if (tid < 3 * TILE) X[253 * TILE + tid] = S.xyz[tid];
-      __syncthreads();
-      DISTR_TS(8);
-      if (DEBUG_STOP && stop == 3) return 0.f;
+      if constexpr (COMPACT) npad = writeback_compact<NOB, KEEP, l == 3>(S, acc, wave, lane, masks[l]);   // (lin3: xyz joins the list as units 253..255)
     }
-    {  // lin4: [x3(253) | xyz(3)] -> 512, latent part folded into c4
-      f32x16 acc[4][2];
-      dense_asm_k256_n4_o4_bias(acc, wpre, xaddr, voff, rs[4], rs[5], soff4, soff4, bias4 + 4 * 2048, scratch);
-      DISTR_TS(9);
-      __syncthreads();
-      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[4]);
-      __syncthreads();
-      DISTR_TS(10);
-      if (DEBUG_STOP && stop == 4) return 0.f;
-    }
-    }
-#pragma unroll
-    for (int l = 5; l <= 7; ++l) {
-      f32x16 acc[4][2];
-      if (l < 7) dense_asm_k512_n4_o4_bias(acc, wpre, xaddr, voff, rs[l], rs[l < 7 ? l + 1 : l], soff4, soff4, bias4 + l * 2048, scratch);
-      else dense_asm_k512_n4_o0_bias(acc, wpre, xaddr, voff, rs[l], rs[l], soff4, soff4, bias4 + l * 2048, scratch);
-      DISTR_TS(2 * l + 1);
-      __syncthreads();
-      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
-      __syncthreads();
-      DISTR_TS(2 * l + 2);
-      if (DEBUG_STOP && stop == l) return 0.f;
-    }
-    const float pre_asm = lin8_row<RB>(D.w8, D.b8, S);
-    DISTR_TS(17);
-    return pre_asm;
-  }
-  {
-    f32x16 acc[4][RB];
-    acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 1), wave * 128, h);
-    dense_pf<512, 4, RB, 4, 4, 4>(D.Wf[1], X, acc, wave, lane, wpre, D.Wf[2]);
-    DISTR_TS(3);
-    __syncthreads();
-    writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[1]);
-    __syncthreads();
-    DISTR_TS(4);
-    if (DEBUG_STOP && stop == 1) return 0.f;
-  }
-  if constexpr (WIDE) {   // lin2, lin3 (512 -> 509 + 3 xyz rows), lin4 ([x3 (509) | xyz (3)] -> 512): the shape of lin1
-#pragma unroll
-    for (int l = 2; l <= 4; ++l) {
-      f32x16 acc[4][RB];
-      acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, l), wave * 128, h);
-      dense_pf<512, 4, RB, 4, 4, 4>(D.Wf[l], X, acc, wave, lane, wpre, D.Wf[l + 1]);
-      DISTR_TS(2 * l + 1);
-      __syncthreads();
-      writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
-      __syncthreads();
-      if (l == 3) {
-        if (tid < 3 * TILE) X[509 * TILE + tid] = S.xyz[tid];
-        __syncthreads();
-      }
-      DISTR_TS(2 * l + 2);
-      if (DEBUG_STOP && stop == l) return 0.f;
-    }
-  } else {
-  {
-    f32x16 acc[4][RB];
-    acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 2), wave * 128, h);
-    dense_pf<512, 4, RB, 4, 2, 2>(D.Wf[2], X, acc, wave, lane, wpre, D.Wf[3]);
-    DISTR_TS(5);
-    __syncthreads();
-    writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[2]);
-    __syncthreads();
-    DISTR_TS(6);
-    if (DEBUG_STOP && stop == 2) return 0.f;
-  }
-  {  // lin3: 512 -> 253 (+3 rows that carry xyz into lin4)
-    f32x16 acc[2][RB];
-    acc_init<2, RB>(acc, layer_init<RB>(D, c0, c4, S, 3), wave * 64, h);
-    dense_pf<512, 2, RB, 2, 2, 4>(D.Wf[3], X, acc, wave, lane, wpre, D.Wf[4]);
-    DISTR_TS(7);
-    __syncthreads();
-    masks[3][2] = 0; masks[3][3] = 0;
-    writeback<2, RB, true, false, KEEP>(X, acc, wave * 64, lane, masks[3]);
-    __syncthreads();
-    if (tid < 3 * TILE) X[253 * TILE + tid] = S.xyz[tid];
-    __syncthreads();
-    DISTR_TS(8);
-  }
-  if (DEBUG_STOP && stop == 3) return 0.f;
-  {  // lin4: [x3(253) | xyz(3)] -> 512, latent part folded into c4
-    f32x16 acc[4][RB];
-    acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, 4), wave * 128, h);
-    dense_pf<256, 4, RB, 2, 4, 4>(D.Wf[4], X, acc, wave, lane, wpre, D.Wf[5]);
-    DISTR_TS(9);
-    __syncthreads();
-    writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[4]);
-    __syncthreads();
-    DISTR_TS(10);
-  }
-  if (DEBUG_STOP && stop == 4) return 0.f;
-  }
-#pragma unroll
-  for (int l = 5; l <= 7; ++l) {
-    f32x16 acc[4][RB];
-    acc_init<4, RB>(acc, layer_init<RB>(D, c0, c4, S, l), wave * 128, h);
-    dense_pf<512, 4, RB, 4, 4, 4>(D.Wf[l], X, acc, wave, lane, wpre, (l < 7) ? D.Wf[l + 1] : nullptr);
-    DISTR_TS(2 * l + 1);
-    __syncthreads();
-    writeback<4, RB, true, false, KEEP>(X, acc, wave * 128, lane, masks[l]);
-    __syncthreads();
-    DISTR_TS(2 * l + 2);
-    if (DEBUG_STOP && stop == l) return 0.f;
-  }
+    if (!(COMPACT && l == 3 && DEBUG_STOP && stop == 3)) DISTR_TS(2 * l + 2);   // (the compacted tile's lin3 dump returns unstamped, as it always has)
+    if (DEBUG_STOP && stop == l) stopped = true;
+  });
+  if (DEBUG_STOP && stopped) return 0.f;
   const float pre = lin8_row<RB>(D.w8, D.b8, S);
   DISTR_TS(17);
 #undef DISTR_TS
@@ -916,48 +794,18 @@ __device__ __forceinline__ void bwd_publish_bits(uint32_t* bits, const uint32_t 
   uint32_t lw[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob) lw[ob] = (mask[ob] | (mask[ob] >> 16)) & 0xffffu;
-  uint32_t a = lw[0] | (lw[1] << 16), b = lw[2] | (lw[3] << 16);
-#define DISTR_OR_SWZ(x) do { a |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)a, ((x) << 10) | 0x1f); if (NOB == 4) b |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)b, ((x) << 10) | 0x1f); } while (0)
-  DISTR_OR_SWZ(1); DISTR_OR_SWZ(2); DISTR_OR_SWZ(4); DISTR_OR_SWZ(8); DISTR_OR_SWZ(16);
-#undef DISTR_OR_SWZ
-  const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)a, 0), a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, 32);
-  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)b, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)b, 32);
-  const uint32_t w0 = spread4(a0 & 0xffffu) | (spread4(a1 & 0xffffu) << 4), w1 = spread4(a0 >> 16) | (spread4(a1 >> 16) << 4);
-  const uint32_t w2 = spread4(b0 & 0xffffu) | (spread4(b1 & 0xffffu) << 4), w3 = spread4(b0 >> 16) | (spread4(b1 >> 16) << 4);
-  if (lane == 0) *reinterpret_cast<uint4*>(&bits[4 * wave]) = make_uint4(w0, w1, w2, w3);
-}
-
-__device__ __forceinline__ uint32_t compact_npad(uint32_t nlive) {
-  const uint32_t npad = (nlive + 15u) & ~15u;
-  return npad < 32u ? 32u : npad;
+  publish_live_words<NOB>(bits, lw, wave, lane);
 }
 
 // positions of one layer from its published bits (compact_store's assignment): postab, klist, the list entries of the zero rows, nlive
 template <int NOB>
 __device__ __forceinline__ void bwd_build_table(CompactBwdLds& C, int li, int wave, int lane) {
-  constexpr int RW = 32 * NOB;
-  const int h = lane >> 5, j = lane & 31;
-  uint32_t cnt[4], own[4];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[li][4 * w]);
-    cnt[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w)));
-  }
-  {
-    const uint4 q = *reinterpret_cast<const uint4*>(&C.bits[li][4 * wave]);
-    own[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.x); own[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.y);
-    own[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.z); own[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w);
-  }
-  const uint32_t base = (wave > 0 ? cnt[0] : 0u) + (wave > 1 ? cnt[1] : 0u) + (wave > 2 ? cnt[2] : 0u);
-  const uint32_t nlive = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  const LiveCounts L = live_counts(C.bits[li], wave);
+  const uint32_t nlive = L.nlive;
 #pragma unroll
   for (int t = 0; t < NOB / 2; ++t) {
-    const uint32_t word = h ? own[2 * t + 1] : own[2 * t];
-    uint32_t below = (uint32_t)__popc(word & ((1u << j) - 1u)) + (h ? (uint32_t)__popc(own[2 * t]) : 0u);
-    if (t) below += (uint32_t)__popc(own[0]) + (uint32_t)__popc(own[1]);
-    const uint32_t pos = base + below;
-    const bool live = (word >> j) & 1u;
-    const uint32_t f = (uint32_t)wave * RW + 64 * t + lane;
+    uint32_t f, pos;
+    const bool live = unit_position<NOB>(L, t, wave, lane, f, pos);
     C.postab[li][f] = (uint16_t)(live ? pos : (uint32_t)HID);
     if (live) C.klist[li][pos] = (uint16_t)f;
   }
@@ -970,6 +818,12 @@ __device__ __forceinline__ void bwd_build_table(CompactBwdLds& C, int li, int wa
 __device__ __forceinline__ void bwd_zero_rows(float* X, uint32_t nlive, int wave, int lane) {
   const uint32_t npad = compact_npad(nlive);
   for (uint32_t p = nlive + (uint32_t)wave; p < npad; p += 4) X[p * 64 + lane] = 0.f;
+}
+
+// byte offsets from X of the rows that four consecutive units' deltas are stored to (postab4: the units' table entries, 8-byte aligned)
+__device__ __forceinline__ void bwd_row_offsets(const uint16_t* postab4, uint32_t (&po)[4]) {
+  const uint2 pw = *reinterpret_cast<const uint2*>(postab4);
+  po[0] = (pw.x & 0xffffu) << 8; po[1] = (pw.x >> 16) << 8; po[2] = (pw.y & 0xffffu) << 8; po[3] = (pw.y >> 16) << 8;
 }
 
 // writeback<NOB, 2, false, true> through the position table of the layer being written: live rows to their positions, dead rows (all
@@ -985,8 +839,8 @@ __device__ __forceinline__ void writeback_gate_compact(float* X, const uint16_t*
     const uint32_t m = mask[ob];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const uint2 pw = *reinterpret_cast<const uint2*>(postab + row0 + 32 * ob + 8 * q + 4 * h);
-      const uint32_t po[4] = {(pw.x & 0xffffu) << 8, (pw.x >> 16) << 8, (pw.y & 0xffffu) << 8, (pw.y >> 16) << 8};
+      uint32_t po[4];
+      bwd_row_offsets(postab + row0 + 32 * ob + 8 * q + 4 * h, po);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float* dst = reinterpret_cast<float*>(xl + po[i]);
@@ -1030,83 +884,23 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
   const int ray = tid & (TILE - 1);
   float* X = S.X;
   static_assert(!COMPACT || (RB == 2 && NOUT == 1 && !WIDE), "the compacted backward tile: 64 samples, one lin8 row, narrow layout");
+  using CH = Chain<WIDE>;
+  CompactBwdLds* const C = reinterpret_cast<CompactBwdLds*>(bias_base(S));     // (compacted only; null and unused otherwise)
   if constexpr (COMPACT) {
     static_assert(sizeof(Smem<RB>) == sizeof(SmemBias<RB>) + sizeof(float) * (HID + 4 + 12 + 4) * TILE, "no padding: the trash row (position HID) is S.xyz");
-    CompactBwdLds& C = *reinterpret_cast<CompactBwdLds*>(S.bias);
-    // live sets of layers 1..7 (layer 3: 256 rows, two row blocks per wave) and their tables, once per tile
+    // live sets of layers 1..7 (narrow lin3: 256 rows, two row blocks per wave) and their tables, once per tile
     static_for<7>([&](auto LI) {
       constexpr int l = decltype(LI)::value + 1;
-      bwd_publish_bits<(l == 3) ? 2 : 4>(C.bits[l - 1], masks[l], wave, lane);
+      bwd_publish_bits<CH::NOB(l)>(C->bits[l - 1], masks[l], wave, lane);
     });
     __syncthreads();
     static_for<7>([&](auto LI) {
       constexpr int l = decltype(LI)::value + 1;
-      bwd_build_table<(l == 3) ? 2 : 4>(C, l - 1, wave, lane);
+      bwd_build_table<CH::NOB(l)>(*C, l - 1, wave, lane);
     });
     __syncthreads();
-    {  // delta7[k][ray] = relu'(h7) * w8[k] * d8[ray], live rows at their positions
-      float d8[2];
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) d8[rb] = S.aux[32 * rb + j];
-      char* xl = reinterpret_cast<char*>(X) + 4 * j;
-#pragma unroll
-      for (int ob = 0; ob < 4; ++ob) {
-        const uint32_t m = masks[7][ob];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = wave * 128 + 32 * ob + 8 * q + 4 * h;
-          const uint2 pw = *reinterpret_cast<const uint2*>(&C.postab[6][row]);
-          const uint32_t po[4] = {(pw.x & 0xffffu) << 8, (pw.x >> 16) << 8, (pw.y & 0xffffu) << 8, (pw.y >> 16) << 8};
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float* dst = reinterpret_cast<float*>(xl + po[i]);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) dst[32 * rb] = gate(D.w8[row + i] * d8[rb], (m >> (16 * rb + 4 * q + i)) & 1u);
-          }
-        }
-      }
-      bwd_zero_rows(X, C.nlive[6], wave, lane);
-    }
-    __syncthreads();
-    const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)j * 4;
-    // (static_for: every layer straight-line code with its own masks[l] registers; K operand delta_l, weights lin_l^T, output delta_{l-1})
-    static_for<7>([&](auto LI) {
-      constexpr int l = 7 - decltype(LI)::value;
-      const uint32_t kaddr = lds_off(C.klist[l - 1]) + (uint32_t)h * 2;
-      const uint32_t npad = compact_npad(C.nlive[l - 1]);
-      if constexpr (l == 4) {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
-        f32x16 acc[2][2];
-        dense_asm_compact_n2_zero(acc, xaddr, kaddr, (uint32_t)j * 8, kmajor_rsrc(D.Wkb + wk_offset(4), 1024, 512), (uint32_t)wave * 256,
-                                  compact_trips(npad, 512));
-        __syncthreads();
-        writeback_gate_compact<2>(X, C.postab[2], acc, wave * 64, lane, masks[3]);  // rows 253..255 have mask 0: dead
-        bwd_zero_rows(X, C.nlive[2], wave, lane);
-        if (wave == 3 && h == 1) {
-#pragma unroll
-          for (int r = 13; r < 16; ++r)
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[1][rb][r];
-        }
-        __syncthreads();
-      } else {
-        constexpr int K = (l == 3) ? 256 : 512;   // lin3^T: delta3 (256 rows, 253 real)
-        f32x16 acc[4][2];
-        dense_asm_compact_n4_zero(acc, xaddr, kaddr, (uint32_t)j * 16, kmajor_rsrc(D.Wkb + wk_offset(l), 2048, K), (uint32_t)wave * 512,
-                                  compact_trips(npad, K));
-        __syncthreads();
-        if constexpr (l == 1) {
-          writeback<4, 2, false, true>(X, acc, wave * 128, lane, masks[0]);      // delta0: dense (row_sums, the W0x chains)
-        } else {
-          writeback_gate_compact<4>(X, C.postab[l - 2], acc, wave * 128, lane, masks[l - 1]);
-          bwd_zero_rows(X, C.nlive[l - 2], wave, lane);
-        }
-        __syncthreads();
-        if constexpr (l == 5) { if (sd4) row_sums_compact(X, C.postab[3], sd4, tid); }  // X = delta4
-      }
-    });
-  } else {
-  // delta7[k][ray] = relu'(h7) * w8[k] * d8[ray]
-  {
+  }
+  {  // delta7[k][ray] = relu'(h7) * w8[k] * d8[ray] (compacted: live rows at their positions)
     float d8[NOUT][RB];
 #pragma unroll
     for (int c = 0; c < NOUT; ++c)
@@ -1116,166 +910,83 @@ __device__ __forceinline__ void mlp_backward(const DecoderDev& D, Smem<RB>& S, u
     for (int ob = 0; ob < 4; ++ob) {
       const uint32_t m = masks[7][ob];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wave * 128 + 32 * ob + (r & 3) + 8 * (r >> 2) + 4 * h;
+      for (int q = 0; q < 4; ++q) {
+        const int row4 = wave * 128 + 32 * ob + 8 * q + 4 * h;     // rows of accumulator registers 4 * q .. 4 * q + 3
+        uint32_t po[4] = {0u, 0u, 0u, 0u};
+        if constexpr (COMPACT) bwd_row_offsets(C->postab[6] + row4, po);
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          float v = D.w8[row] * d8[0][rb];
+        for (int i = 0; i < 4; ++i) {
+          const int row = row4 + i;
+          float* dst = COMPACT ? reinterpret_cast<float*>(reinterpret_cast<char*>(X) + 4 * j + po[i]) : &X[row * TILE + j];
 #pragma unroll
-          for (int c = 1; c < NOUT; ++c) v = __builtin_fmaf(D.w8[c * HID + row], d8[c][rb], v);
-          X[row * TILE + 32 * rb + j] = gate(v, (m >> (16 * rb + r)) & 1u);
+          for (int rb = 0; rb < RB; ++rb) {
+            float v = D.w8[row] * d8[0][rb];
+#pragma unroll
+            for (int c = 1; c < NOUT; ++c) v = __builtin_fmaf(D.w8[c * HID + row], d8[c][rb], v);
+            dst[32 * rb] = gate(v, (m >> (16 * rb + 4 * q + i)) & 1u);
+          }
         }
       }
     }
+    if constexpr (COMPACT) bwd_zero_rows(X, C->nlive[6], wave, lane);
   }
   __syncthreads();
-  if constexpr (RB == 2) {
-    // 64-sample tile: the dX chain on the hand-scheduled loop (distr_dense_asm.hpp), accumulators starting from zero, the next
-    // layer's first transposed weight group travelling in `t` across each write-back; scratch = S.xyz..S.part (4 KiB, idle here)
-    const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)j * 4;
-    const uint32_t voff = (uint32_t)lane * 16;
-    const uint32_t scratch = lds_off(S.xyz) + (uint32_t)wave * 1024 + (uint32_t)lane * 16;
-    const uint32_t soff4 = (uint32_t)wave * 4096, soff2 = (uint32_t)wave * 2048;
-    rsrc_t rs[8];
+  // The dX chain, layers 7..1 (K operand delta_l, weights lin_l^T, output delta_{l-1}), accumulators starting from zero, on one of:
+  //   compacted (COMPACT): dense_asm_compact_*_zero over the live units of delta_l; the write-back stores delta_{l-1} compacted by its own table
+  //   hand-scheduled (64-sample tile): dense_asm_k*_zero (distr_dense_asm.hpp), the next layer's first transposed weight group travelling in `t`
+  //     across each write-back; scratch = S.xyz..S.part (4 KiB, idle here)
+  //   C++ (32-sample tile): acc_zero + dense
+  // operands of the asm engines, marked with the engine that reads them (the C++ engine reads none)
+  const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)j * 4;                     // (compacted, hand-scheduled) this lane's column of X
+  const uint32_t voff = (uint32_t)lane * 16;                                                           // (hand-scheduled only)
+  const uint32_t scratch = lds_off(S.xyz) + (uint32_t)wave * 1024 + (uint32_t)lane * 16;              // (hand-scheduled only)
+  rsrc_t rs[8];                                                                                        // (hand-scheduled only) fragment streams of lin1^T..lin7^T
+  f32x4 t[4];                                                                                          // (hand-scheduled only) the next layer's first weight group
+  if constexpr (RB == 2 && !COMPACT) {
 #pragma unroll
     for (int l = 1; l < 8; ++l) rs[l] = weight_rsrc(D.Wb[l]);
-    f32x4 t[4];
-    {
-      const f32x4* w7 = reinterpret_cast<const f32x4*>(D.Wb[7]) + (size_t)wave * 4 * 64 + lane;
+    const f32x4* w7 = reinterpret_cast<const f32x4*>(D.Wb[7]) + (size_t)wave * 4 * 64 + lane;
 #pragma unroll
-      for (int ob = 0; ob < 4; ++ob) t[ob] = w7[ob * 64];
-    }
-#pragma unroll
-    for (int l = 7; l >= 5; --l) {  // delta_l (512) -> delta_{l-1} (512)
-      f32x16 acc[4][2];
-      if (l > 5 || WIDE) dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[l], rs[l - 1], soff4, soff4, 0u, scratch);
-      else dense_asm_k512_n4_o2_zero(acc, t, xaddr, voff, rs[5], rs[4], soff4, soff2, 0u, scratch);
-      __syncthreads();
-      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[l - 1]);
-      __syncthreads();
-    }
-    if (sd4) row_sums<RB>(X, sd4, tid);  // X = delta4
-    if constexpr (WIDE) {
-      {  // lin4^T: delta4 (512) -> [delta3 (509) | d xyz (3)]
-        f32x16 acc[4][2];
-        dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[4], rs[3], soff4, soff4, 0u, scratch);
-        __syncthreads();
-        writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[3]);  // rows 509..511 have mask 0 -> written as 0
-        if (wave == 3 && h == 1) {
-#pragma unroll
-          for (int r = 13; r < 16; ++r)
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[3][rb][r];
-        }
-        __syncthreads();
-      }
-      {  // lin3^T: delta3 (512 rows, 509 real) -> delta2 (512)
-        f32x16 acc[4][2];
-        dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[3], rs[2], soff4, soff4, 0u, scratch);
-        __syncthreads();
-        writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
-        __syncthreads();
-      }
+    for (int ob = 0; ob < 4; ++ob) t[ob] = w7[ob * 64];
+  }
+  // (static_for: every layer straight-line code with its own masks[l] registers)
+  static_for<7>([&](auto LI) {
+    constexpr int l = 7 - decltype(LI)::value;
+    constexpr int K = CH::KT(l), NOB = CH::NOBT(l), NOBN = CH::NOBT(l - 1), LN = NOBN ? l - 1 : l;
+    const int row0 = wave * (32 * NOB);     // the wave's first output row
+    f32x16 acc[NOB][RB];
+    if constexpr (COMPACT) {
+      dense_asm_compact<NOB, false>(acc, xaddr, lds_off(C->klist[l - 1]) + (uint32_t)h * 2, (uint32_t)j * (4 * NOB),
+                                    kmajor_rsrc(D.Wkb + wk_offset(l), 512 * NOB, K), (uint32_t)wave * (128 * NOB),
+                                    compact_trips(compact_npad(C->nlive[l - 1]), K), 0u);
+    } else if constexpr (RB == 2) {
+      dense_asm<K, NOB, NOBN, false>(acc, t, xaddr, voff, rs[l], rs[LN], (uint32_t)wave * (1024 * NOB),
+                                     (uint32_t)wave * (1024 * (NOBN ? NOBN : NOB)), 0u, scratch);
     } else {
-    {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
-      f32x16 acc[2][2];
-      dense_asm_k512_n2_o4_zero(acc, t, xaddr, voff, rs[4], rs[3], soff2, soff4, 0u, scratch);
-      __syncthreads();
-      writeback<2, RB, false, true>(X, acc, wave * 64, lane, masks[3]);  // rows 253..255 have mask 0 -> written as 0
+      acc_zero<NOB, RB>(acc);
+      dense<K, NOB, RB>(D.Wb[l], X, acc, wave, lane);
+    }
+    __syncthreads();
+    if constexpr (COMPACT && l > 1) {      // (delta0 is written dense: row_sums, the W0x chains)
+      writeback_gate_compact<NOB>(X, C->postab[l - 2], acc, row0, lane, masks[l - 1]);
+      bwd_zero_rows(X, C->nlive[l - 2], wave, lane);
+    } else {
+      writeback<NOB, RB, false, true>(X, acc, row0, lane, masks[l - 1]);
+    }
+    if constexpr (l == 4) {  // lin4^T: delta4 -> [delta3 | d xyz (3)]: the last three rows (mask 0: written as 0 / dead) are d xyz through lin4's xyz columns
       if (wave == 3 && h == 1) {
 #pragma unroll
         for (int r = 13; r < 16; ++r)
 #pragma unroll
-          for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[1][rb][r];
+          for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[NOB - 1][rb][r];
       }
-      __syncthreads();
-    }
-    {  // lin3^T: delta3 (256 rows, 253 real) -> delta2 (512)
-      f32x16 acc[4][2];
-      dense_asm_k256_n4_o4_zero(acc, t, xaddr, voff, rs[3], rs[2], soff4, soff4, 0u, scratch);
-      __syncthreads();
-      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
-      __syncthreads();
-    }
-    }
-#pragma unroll
-    for (int l = 2; l >= 1; --l) {
-      f32x16 acc[4][2];
-      if (l > 1) dense_asm_k512_n4_o4_zero(acc, t, xaddr, voff, rs[2], rs[1], soff4, soff4, 0u, scratch);
-      else dense_asm_k512_n4_o0_zero(acc, t, xaddr, voff, rs[1], rs[1], soff4, soff4, 0u, scratch);
-      __syncthreads();
-      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[l - 1]);
-      __syncthreads();
-    }
-  } else {
-#pragma unroll
-  for (int l = 7; l >= 5; --l) {  // delta_l (512) -> delta_{l-1} (512)
-    f32x16 acc[4][RB];
-    acc_zero<4, RB>(acc);
-    dense<512, 4, RB>(D.Wb[l], X, acc, wave, lane);
-    __syncthreads();
-    writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[l - 1]);
-    __syncthreads();
-  }
-  if (sd4) row_sums<RB>(X, sd4, tid);  // X = delta4
-  if constexpr (WIDE) {
-    {  // lin4^T: delta4 (512) -> [delta3 (509) | d xyz (3)]
-      f32x16 acc[4][RB];
-      acc_zero<4, RB>(acc);
-      dense<512, 4, RB>(D.Wb[4], X, acc, wave, lane);
-      __syncthreads();
-      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[3]);  // rows 509..511 have mask 0 -> written as 0
-      if (wave == 3 && h == 1) {
-#pragma unroll
-        for (int r = 13; r < 16; ++r)
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[3][rb][r];
-      }
-      __syncthreads();
-    }
-    {  // lin3^T: delta3 (512 rows, 509 real) -> delta2 (512)
-      f32x16 acc[4][RB];
-      acc_zero<4, RB>(acc);
-      dense<512, 4, RB>(D.Wb[3], X, acc, wave, lane);
-      __syncthreads();
-      writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
-      __syncthreads();
-    }
-  } else {
-  {  // lin4^T: delta4 (512) -> [delta3 (253) | d xyz (3)]
-    f32x16 acc[2][RB];
-    acc_zero<2, RB>(acc);
-    dense<512, 2, RB>(D.Wb[4], X, acc, wave, lane);
-    __syncthreads();
-    writeback<2, RB, false, true>(X, acc, wave * 64, lane, masks[3]);  // rows 253..255 have mask 0 -> written as 0
-    if (wave == 3 && h == 1) {
-#pragma unroll
-      for (int r = 13; r < 16; ++r)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) S.aux[(1 + r - 13) * TILE + 32 * rb + j] = acc[1][rb][r];
     }
     __syncthreads();
-  }
-  {  // lin3^T: delta3 (256 rows, 253 real) -> delta2 (512)
-    f32x16 acc[4][RB];
-    acc_zero<4, RB>(acc);
-    dense<256, 4, RB>(D.Wb[3], X, acc, wave, lane);
-    __syncthreads();
-    writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[2]);
-    __syncthreads();
-  }
-  }
-#pragma unroll
-  for (int l = 2; l >= 1; --l) {
-    f32x16 acc[4][RB];
-    acc_zero<4, RB>(acc);
-    dense<512, 4, RB>(D.Wb[l], X, acc, wave, lane);
-    __syncthreads();
-    writeback<4, RB, false, true>(X, acc, wave * 128, lane, masks[l - 1]);
-    __syncthreads();
-  }
-  }
-  }  // !COMPACT
+    if constexpr (l == 5) {  // X = delta4
+      if constexpr (COMPACT) { if (sd4) row_sums_compact(X, C->postab[3], sd4, tid); }
+      else { if (sd4) row_sums<RB>(X, sd4, tid); }
+    }
+  });
   if (sd0) row_sums<RB>(X, sd0, tid);  // X = delta0
   // d xyz through lin0's xyz columns: 3 x four 128-long chains per ray
   {

@@ -470,20 +470,54 @@ __device__ __forceinline__ void %s(f32x16 (&acc)[%d][2], uint32_t xaddr, uint32_
 ''' % (head, name, NOB, tail, body, outs, ins, ', '.join(clob))
 
 
+DENSE_SHAPES = ((512, 4, 4), (512, 4, 2), (512, 2, 4), (256, 4, 4), (512, 4, 0))      # (K, NOB, NOUT) of the 64-ray tile's layers
+COMPACT_SHAPES = (4, 2)                                                              # NOB
+
+
+def gen_dispatch():
+    """dense_asm<K, NOB, NOBN, BIAS> / dense_asm_compact<NOB, BIAS>: the generated function of a layer shape, chosen at compile time
+    (the decoder chain of distr_mlp.hpp derives the shapes from its layer table); a shape without a generated loop does not compile."""
+    L = ['// the generated k-loop of a layer shape: K input features, NOB row blocks per wave, NOBN fragments of the next layer prefetched, BIAS: accumulators',
+         '// start from the LDS bias tuples (else from zero)',
+         'template <int K, int NOB, int NOBN, bool BIAS>',
+         '__device__ __forceinline__ void dense_asm(f32x16 (&acc)[NOB][2], f32x4 (&t)[4], uint32_t xaddr, uint32_t voff, rsrc_t rs, rsrc_t rsn,',
+         '    uint32_t soff, uint32_t soffn, uint32_t biasaddr, uint32_t scratch) {']
+    kw = 'if'
+    for init in ('bias', 'zero'):
+        for (K, NOB, NOUT) in DENSE_SHAPES:
+            L.append('  %s constexpr (K == %d && NOB == %d && NOBN == %d && %sBIAS) dense_asm_k%d_n%d_o%d_%s(acc, t, xaddr, voff, rs, rsn, soff, soffn, biasaddr, scratch);'
+                     % (kw, K, NOB, NOUT, '' if init == 'bias' else '!', K, NOB, NOUT, init))
+            kw = 'else if'
+    L += ['  else static_assert(K < 0, "no generated k-loop of this layer shape");', '}', '',
+          '// ... of the compacted tile (biasaddr: unused when the accumulators start from zero)',
+          'template <int NOB, bool BIAS>',
+          '__device__ __forceinline__ void dense_asm_compact(f32x16 (&acc)[NOB][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff,',
+          '    uint32_t nit, uint32_t biasaddr) {']
+    kw = 'if'
+    for init in ('bias', 'zero'):
+        for NOB in COMPACT_SHAPES:
+            L.append('  %s constexpr (NOB == %d && %sBIAS) dense_asm_compact_n%d_%s(acc, xaddr, kaddr, voff, rs, soff, nit%s);'
+                     % (kw, NOB, '' if init == 'bias' else '!', NOB, init, ', biasaddr' if init == 'bias' else ''))
+            kw = 'else if'
+    L += ['  else static_assert(NOB < 0, "no generated compacted k-loop of this layer shape");', '}', '']
+    return '\n'.join(L)
+
+
 def main():
     out = ['// GENERATED by gen_dense_asm.py -- do not edit; see that file for the design notes.',
            '#pragma once', '#include <hip/hip_runtime.h>', '#include <stdint.h>', '', 'namespace distr {', '',
            'typedef float f32x16 __attribute__((ext_vector_type(16)));', 'typedef float f32x4 __attribute__((ext_vector_type(4)));',
            'typedef __amdgpu_buffer_rsrc_t rsrc_t;', '']
     for init in ('bias', 'zero'):
-        for (K, NOB, NOUT) in ((512, 4, 4), (512, 4, 2), (512, 2, 4), (256, 4, 4), (512, 4, 0)):
+        for (K, NOB, NOUT) in DENSE_SHAPES:
             out.append(gen(K, NOB, NOUT, init)[1])
     for (K, NB, NOUT) in ((512, 8, 8), (512, 8, 4), (512, 4, 8), (256, 8, 8), (512, 8, 0)):
         out.append(gen16(K, NB, NOUT)[1])
-    for NOB in (4, 2):
+    for NOB in COMPACT_SHAPES:
         out.append(gen_compact(NOB)[1])
-    for NOB in (4, 2):
+    for NOB in COMPACT_SHAPES:
         out.append(gen_compact(NOB, 'zero')[1])
+    out.append(gen_dispatch())
     out.append('}  // namespace distr')
     sys.stdout.write('\n'.join(out) + '\n')
 
