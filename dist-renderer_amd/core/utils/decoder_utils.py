@@ -126,21 +126,31 @@ def _train_layout(Cn, latent_vectors, points, counts):
     return _batch_layout(Cn, latent_vectors, points, counts)
 
 
-def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.1):
+def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.1, dropout_seed=None):
     """decode_sdf_batch that is differentiable w.r.t. `decoder.parameters()` AND the codes (not in the reference, which trains through
     the torch Decoder): the layer-wise path of DESIGN.md section 8f -- one f32-MFMA GEMM per layer over the whole point list, the layer
     inputs kept for the backward (24 KB of workspace per point; above DISTR_TRAIN_MAX_BYTES, default 32 GiB, the call is refused
     rather than chunked, since chunking would change the sum order of the gradients). Arguments, shapes and ValueErrors as
-    decode_sdf_batch; points with requires_grad are refused. The decoder must be in eval mode (dropout in training mode raises, as
-    everywhere); weight norm is folded on the autograd graph, so the gradients arrive at weight_g / weight_v. The fused engine is not
-    involved: after an optimiser step the renderers and decode_sdf re-pack the weights by themselves."""
+    decode_sdf_batch; points with requires_grad are refused. Without `dropout_seed` the decoder must be in eval mode (dropout in
+    training mode raises, as everywhere). With an int `dropout_seed` (functions.draw_dropout_seed()) a decoder in training mode gets the
+    dropout of its `dropout` / `dropout_prob` behind the relus, by the counter-based mask of DESIGN.md section 8g: a pure function of
+    (seed, segment, point in segment, layer, unit), segment = the index into latent_vectors -- the same call gives the same bytes; in
+    eval mode the seed changes nothing. latent_dropout in training mode stays refused. Weight norm is folded on the autograd graph, so
+    the gradients arrive at weight_g / weight_v. The fused engine is not involved: after an optimiser step the renderers and
+    decode_sdf re-pack the weights by themselves."""
     from distr import decoder_pack
-    functions._check_eval(decoder.module if hasattr(decoder, 'module') else decoder)
+    module = decoder.module if hasattr(decoder, 'module') else decoder
+    dropout = None
+    if dropout_seed is None:
+        functions._check_eval(module)
+    else:
+        params = functions.train_dropout_params(module, dropout_seed)
+        dropout = None if params is None else params + (int(dropout_seed), 0)
     Ws, bs = decoder_pack.effective_weights_torch(decoder)
     x, counts, shape = _train_layout(Ws[0].shape[1] - 3, latent_vectors, points, counts)
     if x.device.type != 'cuda':
         raise RuntimeError('decode_sdf_train: tensors must be on the GPU (no CPU path in this build)')
-    out = functions.decode_sdf_train_call(Ws + bs, latent_vectors, x, counts, clamp_dist)
+    out = functions.decode_sdf_train_call(Ws + bs, latent_vectors, x, counts, clamp_dist, dropout)
     return out.reshape(shape + (1,))
 
 

@@ -2540,7 +2540,7 @@ struct TrainPlan {
   train::Segs sg;
   int32_t seg_row[DISTR_MAX_VIEWS + 1];
   // workspace
-  int32_t *rowpt, *blkseg;
+  int32_t *rowpt, *blkseg, *blkpt0;
   float *c0c4, *xyz4, *X[9] /* 1..8 */, *z, *th, *dz, *D[2], *colpart, *colseg[3] /* lin0, lin4, the others */, *slabs;
   int out_w[9], in_w[9];     // GEMM widths: rows of W_l, and the columns of W_l that multiply the saved activation (lin4: 509 - C)
 };
@@ -2585,17 +2585,42 @@ size_t train_carve(void* base, TrainPlan& p) {
   p.colpart = c.take<float>((size_t)p.blocks * 4 * HID);
   for (int i = 0; i < 3; ++i) p.colseg[i] = c.take<float>((size_t)p.nseg * 4 * HID);
   p.slabs = c.take<float>((size_t)p.nslab * HID * HID);
+  p.blkpt0 = c.take<int32_t>((size_t)p.blocks);      // (last: the offsets of everything above are those of the path without dropout)
   return c.bytes();
 }
 
 inline int vec_ok(const void* p, int ld) { return ((uintptr_t)p % 16 == 0 && ld % 4 == 0) ? 1 : 0; }
 
+// drop: null = the kernel without dropout, the code of the plain calls
 template <bool A_K, bool B_K, int EPI>
-int train_gemm(distr_ctx* ctx, const char* name, train::GemmArgs& g, int nz, hipStream_t s) {
+int train_gemm(distr_ctx* ctx, const char* name, train::GemmArgs& g, int nz, hipStream_t s, const train::DropArgs* drop = nullptr) {
   g.vecA = vec_ok(g.A, g.lda); g.vecB = vec_ok(g.B, g.ldb);
   const dim3 grid((unsigned)((g.M + train::TBM - 1) / train::TBM), (unsigned)((g.N + train::TBN - 1) / train::TBN), (unsigned)nz);
+  if constexpr (EPI != train::EPI_PART) {      // (the weight-gradient form has no dropout variant)
+    if (drop) {
+      hipLaunchKernelGGL((train::k_train_gemm_drop<A_K, B_K, EPI>), grid, dim3(256), 0, s, g, *drop);
+      LAUNCH_CHECK(name);
+      return DISTR_OK;
+    }
+  }
   hipLaunchKernelGGL((train::k_train_gemm<A_K, B_K, EPI>), grid, dim3(256), 0, s, g);
   LAUNCH_CHECK(name);
+  return DISTR_OK;
+}
+
+// distr_train_dropout -> the kernels' arguments; active = false for null / layer_mask 0 (the plain path)
+int train_drop_args(distr_ctx* ctx, const distr_train_dropout* d, int32_t nseg, train::DropArgs& a, uint32_t& layer_mask) {
+  memset(&a, 0, sizeof(a));
+  layer_mask = 0;
+  if (!d) return DISTR_OK;
+  if (d->struct_size != sizeof(distr_train_dropout)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_dropout: struct_size (use DISTR_INIT)");
+  if (d->layer_mask > 0xffu) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_dropout: layer_mask 0x%x: bits 0..7 (lin0..lin7)", d->layer_mask);
+  if (!std::isfinite(d->scale) || d->scale < 1.f) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_dropout: scale %g: finite and >= 1", (double)d->scale);
+  if (d->segment_base < 0 || d->segment_base + (int64_t)nseg > ((int64_t)1 << 32))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_dropout: segment_base %lld: 0 .. 2^32 - nseg", (long long)d->segment_base);
+  a.key0 = (uint32_t)(d->seed & 0xffffffffu); a.key1 = (uint32_t)(d->seed >> 32);
+  a.thr = d->threshold; a.scale = d->scale; a.seg_base = (uint32_t)d->segment_base;
+  layer_mask = d->layer_mask;
   return DISTR_OK;
 }
 
@@ -2653,6 +2678,11 @@ int64_t distr_train_segment_row(int32_t nseg, const int64_t* counts_host, int32_
   return p.seg_row[seg];
 }
 
+int distr_train_dropout_keep(uint64_t seed, uint32_t threshold, int32_t layer, int64_t segment, int64_t point, int32_t unit) {
+  const Philox4 u = dropout_draws((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)layer, (uint32_t)segment, (uint32_t)(point >> 2), (uint32_t)unit);
+  return u.v[point & 3] >= threshold ? 1 : 0;
+}
+
 void distr_train_slab_plan(int64_t rows, int64_t* slab_len, int32_t* num_slabs) {
   int64_t L = 0; int n = 0;
   train_slab_plan(rows < 0 ? 0 : rows, &L, &n);
@@ -2662,11 +2692,19 @@ void distr_train_slab_plan(int64_t rows, int64_t* slab_len, int32_t* num_slabs) 
 
 int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                         const float* xyz, float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream) {
+  return distr_train_forward_dropout(ctx, w, nseg, counts_host, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, stream, nullptr);
+}
+
+int distr_train_forward_dropout(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                                const float* xyz, float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (int rc = train_weights_ok(ctx, w)) return rc;
   TrainPlan p;
   if (int rc = train_plan(ctx, w->latent_size, nseg, counts_host, p)) return rc;
+  train::DropArgs da;
+  uint32_t drop_mask;
+  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
   const int C = p.C;
   if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
   if (!latent || !ws || (p.n > 0 && (!xyz || !sdf))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
@@ -2674,12 +2712,18 @@ int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t ns
   train_carve(ws, p);
   if (p.rows == 0) return DISTR_OK;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg);
+  hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg, p.blkpt0);
   LAUNCH_CHECK("k_train_rows");
+  da.blkseg = p.blkseg; da.blkpt0 = p.blkpt0;
   hipLaunchKernelGGL(train::k_train_consts, dim3(4, (unsigned)p.nseg), dim3(256), 0, s, p.c0c4, w->W[0], w->b[0], w->W[4], w->b[4], C, latent, latent_stride);
   LAUNCH_CHECK("k_train_consts");
-  hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
-                     p.X[1], p.xyz4);
+  if (drop_mask & 1u) {
+    da.layer = 0;
+    hipLaunchKernelGGL(train::k_train_lin0_drop, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4,
+                       w->W[0], C, p.X[1], p.xyz4, da);
+  } else
+    hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
+                       p.X[1], p.xyz4);
   LAUNCH_CHECK("k_train_lin0");
   for (int l = 1; l <= 8; ++l) {
     train::GemmArgs g;
@@ -2690,7 +2734,8 @@ int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t ns
       g.ctab = p.c0c4 + HID; g.ctab_stride = 2 * HID; g.blkseg = p.blkseg;
       g.tailW = w->W[4] + (HID - 3); g.tail_ld = HID; g.xyz4 = p.xyz4;
     } else g.bias = w->b[l];
-    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s)) return rc;
+    da.layer = (uint32_t)l;
+    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s, (l < 8 && (drop_mask >> l & 1u)) ? &da : nullptr)) return rc;
   }
   hipLaunchKernelGGL(train::k_train_out, grid1(p.rows), dim3(256), 0, s, (const float*)p.z, (const int32_t*)p.rowpt, p.rows, clamp, p.th, sdf);
   LAUNCH_CHECK("k_train_out");
@@ -2699,9 +2744,18 @@ int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t ns
 
 int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                          const float* g_sdf, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream) {
+  return distr_train_backward_dropout(ctx, w, nseg, counts_host, latent, latent_stride, g_sdf, clamp, ws, gr, g_latent, stream, nullptr);
+}
+
+int distr_train_backward_dropout(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                                 const float* g_sdf, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
+                                 const distr_train_dropout* drop) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
   EntryGuard guard_(ctx);
   if (int rc = train_weights_ok(ctx, w)) return rc;
+  train::DropArgs da;
+  uint32_t drop_mask;
+  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
   if (!gr || gr->struct_size != sizeof(distr_train_grads)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: struct_size (use DISTR_INIT)");
   for (int l = 0; l < 9; ++l)
     if (!gr->g_W[l] || !gr->g_b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: null pointer for lin%d", l);
@@ -2734,7 +2788,8 @@ int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t n
     memset(&g, 0, sizeof(g));
     g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
     g.Cout = p.D[cur]; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
-    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s)) return rc;
+    // X_l went through lin(l-1)'s dropout: a dropped unit is an exact zero there, a kept one carries the factor scale
+    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (drop_mask >> (l - 1) & 1u) ? &da : nullptr)) return rc;
     delta = p.D[cur]; ldd = HID; cur ^= 1;
     const int m = l - 1;       // delta now belongs to lin m
     if (m >= 1) {

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "distr_mlp.hpp"        // HID, tanh_spec, DISTR_GLOBAL
+#include "distr_philox.hpp"     // the dropout mask (section 8g)
 
 namespace distr {
 namespace train {
@@ -34,19 +35,30 @@ struct Segs { int32_t n[DISTR_MAX_VIEWS]; };     // points per segment (0 behind
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// rowpt[row] = index of the row's point in the caller's list, -1 for a padded row; blkseg[row / 64] = the block's segment
-DISTR_GLOBAL void __launch_bounds__(256) k_train_rows(Segs sg, int nseg, int rows, int32_t* __restrict__ rowpt, int32_t* __restrict__ blkseg) {
+// rowpt[row] = index of the row's point in the caller's list, -1 for a padded row; blkseg[row / 64] = the block's segment;
+// blkpt0[row / 64] = the index, inside that segment, of the block's first row (a multiple of 64: what the dropout mask counts by)
+DISTR_GLOBAL void __launch_bounds__(256) k_train_rows(Segs sg, int nseg, int rows, int32_t* __restrict__ rowpt, int32_t* __restrict__ blkseg,
+                                                    int32_t* __restrict__ blkpt0) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
-  int r0 = 0, p0 = 0, pt = -1, seg = 0;
+  int r0 = 0, p0 = 0, pt = -1, seg = 0, in_seg = 0;
   for (int s = 0; s < nseg; ++s) {
     const int n = sg.n[s], pad = (n + TROW - 1) / TROW * TROW;
-    if (row >= r0 && row < r0 + pad) { seg = s; pt = (row - r0 < n) ? p0 + (row - r0) : -1; }
+    if (row >= r0 && row < r0 + pad) { seg = s; in_seg = row - r0; pt = (row - r0 < n) ? p0 + (row - r0) : -1; }
     r0 += pad; p0 += n;
   }
   rowpt[row] = pt;
-  if ((row & (TROW - 1)) == 0) blkseg[row / TROW] = seg;
+  if ((row & (TROW - 1)) == 0) { blkseg[row / TROW] = seg; blkpt0[row / TROW] = in_seg; }
 }
+
+// Dropout of one launch (section 8g): keep(row, n) = draw >= thr, the draws of dropout_draws(key, layer, seg_base + blkseg[block],
+// (blkpt0[block] + row in block) >> 2, n); a kept value is multiplied by scale, a dropped one stored as +0. The delta GEMM reads scale only.
+struct DropArgs {
+  uint32_t key0, key1, thr;
+  float scale;
+  uint32_t seg_base, layer;
+  const int32_t* blkseg; const int32_t* blkpt0;
+};
 
 // c0[s] = b0 + W0[:, :C] code_s, c4[s] = b4 + W4[:, 509-C : 509] code_s, one k-ordered fmaf chain each (the arithmetic of
 // k_latent_consts, on row-major weights). grid (4, segments), 256 threads; c0c4[s][1024]
@@ -64,9 +76,11 @@ DISTR_GLOBAL void __launch_bounds__(256) k_train_consts(float* __restrict__ c0c4
 
 // lin0: X1[row] = relu(c0[seg] + W0[:, C:] xyz), and the padded point list xyz4[row] = (x, y, z, 0). One row per thread-column pass:
 // block = one 64-row block, 256 threads; thread t owns outputs t and t + 256 of every row.
-DISTR_GLOBAL void __launch_bounds__(256) k_train_lin0(const float* __restrict__ xyz, const int32_t* __restrict__ rowpt, const int32_t* __restrict__ blkseg,
-                                                    const float* __restrict__ c0c4, const float* __restrict__ W0, int C,
-                                                    float* __restrict__ X1, float* __restrict__ xyz4) {
+// DROP: dropout behind the relu, one Philox call per four rows.
+template <bool DROP>
+__device__ __forceinline__ void lin0_block(const float* __restrict__ xyz, const int32_t* __restrict__ rowpt, const int32_t* __restrict__ blkseg,
+                                           const float* __restrict__ c0c4, const float* __restrict__ W0, int C,
+                                           float* __restrict__ X1, float* __restrict__ xyz4, const DropArgs& d) {
   __shared__ float p[TROW][4];
   const int blk = blockIdx.x, t = threadIdx.x;
   if (t < TROW) {
@@ -83,13 +97,41 @@ DISTR_GLOBAL void __launch_bounds__(256) k_train_lin0(const float* __restrict__ 
     const int o = t + h * 256;
     const float* w = W0 + (size_t)o * (C + 3) + C;
     const float wx = w[0], wy = w[1], wz = w[2], c = c0[o];
-    for (int r = 0; r < TROW; ++r) {
-      float a = __builtin_fmaf(wx, p[r][0], c);
-      a = __builtin_fmaf(wy, p[r][1], a);
-      a = __builtin_fmaf(wz, p[r][2], a);
-      X1[((size_t)blk * TROW + r) * HID + o] = a > 0.f ? a : 0.f;
+    if (DROP) {
+      const uint32_t gs = d.seg_base + (uint32_t)d.blkseg[blk], q0 = (uint32_t)d.blkpt0[blk] >> 2;
+      for (int r4 = 0; r4 < TROW; r4 += 4) {
+        const Philox4 u = dropout_draws(d.key0, d.key1, d.layer, gs, q0 + (uint32_t)(r4 >> 2), (uint32_t)o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = r4 + e;
+          float a = __builtin_fmaf(wx, p[r][0], c);
+          a = __builtin_fmaf(wy, p[r][1], a);
+          a = __builtin_fmaf(wz, p[r][2], a);
+          a = a > 0.f ? a : 0.f;
+          X1[((size_t)blk * TROW + r) * HID + o] = u.v[e] >= d.thr ? a * d.scale : 0.f;
+        }
+      }
+    } else {
+      for (int r = 0; r < TROW; ++r) {
+        float a = __builtin_fmaf(wx, p[r][0], c);
+        a = __builtin_fmaf(wy, p[r][1], a);
+        a = __builtin_fmaf(wz, p[r][2], a);
+        X1[((size_t)blk * TROW + r) * HID + o] = a > 0.f ? a : 0.f;
+      }
     }
   }
+}
+
+DISTR_GLOBAL void __launch_bounds__(256) k_train_lin0(const float* __restrict__ xyz, const int32_t* __restrict__ rowpt, const int32_t* __restrict__ blkseg,
+                                                    const float* __restrict__ c0c4, const float* __restrict__ W0, int C,
+                                                    float* __restrict__ X1, float* __restrict__ xyz4) {
+  lin0_block<false>(xyz, rowpt, blkseg, c0c4, W0, C, X1, xyz4, DropArgs());
+}
+
+DISTR_GLOBAL void __launch_bounds__(256) k_train_lin0_drop(const float* __restrict__ xyz, const int32_t* __restrict__ rowpt, const int32_t* __restrict__ blkseg,
+                                                         const float* __restrict__ c0c4, const float* __restrict__ W0, int C,
+                                                         float* __restrict__ X1, float* __restrict__ xyz4, DropArgs d) {
+  lin0_block<true>(xyz, rowpt, blkseg, c0c4, W0, C, X1, xyz4, d);
 }
 
 // ---- the GEMM tile: C[m][n] = init + sum_k A(m, k) B(k, n), k in natural order.
@@ -169,8 +211,10 @@ __device__ __forceinline__ void stage_store(float (*S)[TLD], const float4 (&r)[2
   }
 }
 
-template <bool A_K, bool B_K, int EPI>
-DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm(GemmArgs g) {      // (2 waves per SIMD: at most 256 registers)
+// DROP (section 8g): EPI_FWD drops behind the relu -- a lane's four consecutive rows (r & 3) are the points 4q .. 4q + 3 of one segment, one
+// Philox call serves them; EPI_GATE multiplies the gated delta by d.scale (the saved activation of a dropped unit is an exact zero).
+template <bool A_K, bool B_K, int EPI, bool DROP>
+__device__ __forceinline__ void gemm_tile(const GemmArgs& g, const DropArgs& d) {
   __shared__ __attribute__((aligned(16))) float As[TBK][TLD];
   __shared__ __attribute__((aligned(16))) float Bs[TBK][TLD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -239,8 +283,17 @@ DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm(GemmArgs g) {      // (
         const float* w = g.tailW + (size_t)n * g.tail_ld;
         tw0 = w[0]; tw1 = w[1]; tw2 = w[2];
       }
+      uint32_t gs = 0, q0 = 0;
+      Philox4 u = {{0u, 0u, 0u, 0u}};
+      if (EPI == EPI_FWD && DROP) {
+        if (m0 + wm >= g.M) continue;                    // (a wave's 64 rows are one 64-row block)
+        const int blk = (m0 + wm) / TROW;
+        gs = d.seg_base + (uint32_t)d.blkseg[blk];
+        q0 = ((uint32_t)d.blkpt0[blk] >> 2) + (uint32_t)(i * 8 + lh);
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        if (EPI == EPI_FWD && DROP && (r & 3) == 0) u = dropout_draws(d.key0, d.key1, d.layer, gs, q0 + (uint32_t)(2 * (r >> 2)), (uint32_t)n);
         const int m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;      // C/D map of the 32 x 32 MFMA: col = lane & 31
         if (m >= g.M) continue;
         float v = acc[i][j][r];
@@ -252,11 +305,25 @@ DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm(GemmArgs g) {      // (
             v = __builtin_fmaf(tw2, q[2], v);
           }
           if (g.relu) v = v > 0.f ? v : 0.f;
+          if (DROP) v = u.v[r & 3] >= d.thr ? v * d.scale : 0.f;
         }
-        if (EPI == EPI_GATE) v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v : 0.f;
+        if (EPI == EPI_GATE) {
+          if (DROP) v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v * d.scale : 0.f;
+          else v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v : 0.f;
+        }
         out[(size_t)m * g.ldc + n] = v;
       }
     }
+}
+
+template <bool A_K, bool B_K, int EPI>
+DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm(GemmArgs g) {      // (2 waves per SIMD: at most 256 registers)
+  gemm_tile<A_K, B_K, EPI, false>(g, DropArgs());
+}
+
+template <bool A_K, bool B_K, int EPI>
+DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm_drop(GemmArgs g, DropArgs d) {
+  gemm_tile<A_K, B_K, EPI, true>(g, d);
 }
 
 // sdf = tanh(z), clamped, into the caller's order; th[row] = tanh(z) (unclamped) for the backward

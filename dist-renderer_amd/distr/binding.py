@@ -42,7 +42,8 @@ COLOR_BATCH_EXPORTS = ['distr_color_multi_workspace_bytes', 'distr_color_backwar
                        'distr_color_stage_backward_batch', 'distr_color_relight']
 # the layer-wise decoder path (include/distr_train.h, included by distr.h): decode_sdf with gradients to the decoder's weights
 TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset', 'distr_train_segment_row', 'distr_train_slab_plan',
-                 'distr_train_forward', 'distr_train_backward']
+                 'distr_train_forward', 'distr_train_backward', 'distr_train_forward_dropout', 'distr_train_backward_dropout',
+                 'distr_train_dropout_keep']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -149,6 +150,12 @@ class TrainGrads(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('reserved', C.c_uint32), ('g_W', C.c_void_p * 9), ('g_b', C.c_void_p * 9)]
 
 
+class TrainDropout(_Sized):
+    """distr_train_dropout: the counter-based dropout of one train call (include/distr_train.h)."""
+    _fields_ = [('struct_size', C.c_uint32), ('layer_mask', C.c_uint32), ('threshold', C.c_uint32), ('scale', C.c_float), ('seed', C.c_uint64),
+                ('segment_base', C.c_int64)]
+
+
 class RenderStats(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('reserved', C.c_uint32), ('num_in_sphere', C.c_int64), ('num_march_launches', C.c_int64), ('num_point_evals', C.c_int64),
                 ('num_valid', C.c_int64), ('num_grad_samples', C.c_int64), ('cluster_fallbacks', C.c_int64), ('f16_overflows', C.c_int64),
@@ -156,7 +163,7 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_b6.hpp', 'distr_mlp_h3.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp')
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp', 'distr_philox.hpp')
 HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h')                    # include/: the C ABI
 INST_GROUPS = 10           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
@@ -407,6 +414,10 @@ def lib():
             L.distr_train_slab_plan.restype = None
             L.distr_train_forward.argtypes = [vp, tw, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp]
             L.distr_train_backward.argtypes = [vp, tw, i32, i64p, fp, i64, fp, C.c_float, vp, tg, fp, vp]
+            td = C.POINTER(TrainDropout)
+            L.distr_train_forward_dropout.argtypes = L.distr_train_forward.argtypes + [td]
+            L.distr_train_backward_dropout.argtypes = L.distr_train_backward.argtypes + [td]
+            L.distr_train_dropout_keep.argtypes = [C.c_uint64, C.c_uint32, i32, i64, i64, i32]
             _lib = L
     return _lib
 

@@ -634,12 +634,51 @@ def _train_context(device_index):
     return _train_contexts[device_index]
 
 
+def train_dropout_params(module, seed, segment_base=0):
+    """The dropout of one train call from a decoder's `dropout` / `dropout_prob`: (layer_mask, threshold, scale)
+    with threshold = min(2^32 - 1, floor(p * 2^32)) and scale = float32(1 / (1 - p)), both from double arithmetic. None when nothing is
+    dropped: the module in eval mode, p == 0 or an empty list. ValueError for p outside [0, 1) and a layer outside 0..7. `seed` and
+    `segment_base` are checked here and travel separately (train_forward(..., dropout=(mask, threshold, scale, seed, segment_base)))."""
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError('dropout seed %r: an integer in 0 .. 2^64 - 1' % (seed,))
+    if int(segment_base) < 0:
+        raise ValueError('segment_base %r: >= 0' % (segment_base,))
+    layers = getattr(module, 'dropout', None)
+    p = float(getattr(module, 'dropout_prob', 0.0) or 0.0)
+    layers = [] if layers is None else [int(l) for l in layers]
+    if not 0.0 <= p < 1.0:
+        raise ValueError('dropout_prob %r: 0 <= p < 1' % (p,))
+    mask = 0
+    for l in layers:
+        if not 0 <= l <= 7:
+            raise ValueError('dropout layer %d: this decoder has relu outputs lin0..lin7' % l)
+        mask |= 1 << l
+    if not module.training or p == 0.0 or mask == 0:
+        return None
+    threshold = min((1 << 32) - 1, int(np.floor(np.float64(p) * 4294967296.0)))
+    return mask, threshold, float(np.float32(1.0 / (1.0 - np.float64(p))))
+
+
+def draw_dropout_seed(generator=None):
+    """A seed below 2^63 - 1 from torch's CPU generator (the default one, or `generator`): no device sync, reproducible under
+    torch.manual_seed."""
+    return int(torch.randint(0, (1 << 63) - 1, (1,), generator=generator, dtype=torch.int64, device='cpu').item())
+
+
+def _train_dropout_struct(dropout, chunk_base=0):
+    """dropout = None or (layer_mask, threshold, scale, seed, segment_base) -> distr_train_dropout (None: the plain calls)"""
+    if dropout is None:
+        return None
+    mask, threshold, scale, seed, base = dropout
+    return binding.TrainDropout(layer_mask=int(mask), threshold=int(threshold), scale=float(scale), seed=int(seed), segment_base=int(base) + int(chunk_base))
+
+
 class TrainSaved(object):
     """What train_forward keeps for train_backward: the workspace with the saved layer inputs, and the call it belongs to."""
 
-    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp):
+    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp, dropout=None):
         self.ctx, self.ws, self.latent_size, self.counts = ctx, ws, C_len, list(counts)
-        self.weights, self.lat, self.stride, self.clamp = weights, lat, stride, clamp
+        self.weights, self.lat, self.stride, self.clamp, self.dropout = weights, lat, stride, clamp, dropout
         self.seg_rows = train_segment_rows(counts)
 
     def _cnt(self):
@@ -668,10 +707,12 @@ def _train_weight_struct(weights, C_len):
     return tw
 
 
-def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None):
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None):
     """Layer-wise decode_sdf of one segmented list of at most 64 segments (distr_train_forward): weights = [W0..W8, b0..b8] f32 device
     tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
-    A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed."""
+    A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed.
+    dropout: None, or (layer_mask, threshold, scale, seed, segment_base) -- train_dropout_params(...) + (seed, global index of segment 0)
+    (distr_train_forward_dropout); the saved activations are then those behind the dropout, and train_backward follows."""
     counts = [int(c) for c in counts]
     dev = points.device
     if dev.type != 'cuda':
@@ -697,9 +738,14 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     stride = 0 if lat.shape[0] == 1 else C_len
     out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
     p = binding.ptr
-    ctx.check(ctx.L.distr_train_forward(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
-                                        p(out), p(ws), ws.numel(), ctx.stream()))
-    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist)
+    td = _train_dropout_struct(dropout)
+    if td is None:
+        ctx.check(ctx.L.distr_train_forward(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
+                                            p(out), p(ws), ws.numel(), ctx.stream()))
+    else:
+        ctx.check(ctx.L.distr_train_forward_dropout(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x),
+                                                    _clamp_arg(clamp_dist), p(out), p(ws), ws.numel(), ctx.stream(), C.byref(td)))
+    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist, dropout)
 
 
 def train_backward(saved, g_sdf):
@@ -716,18 +762,25 @@ def train_backward(saved, g_sdf):
         tg.g_W[l] = grads[l].data_ptr()
         tg.g_b[l] = grads[9 + l].data_ptr()
     p = binding.ptr
-    ctx.check(ctx.L.distr_train_backward(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(), p(saved.lat),
-                                         saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream()))
+    td = _train_dropout_struct(saved.dropout)
+    if td is None:
+        ctx.check(ctx.L.distr_train_backward(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(), p(saved.lat),
+                                             saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream()))
+    else:
+        ctx.check(ctx.L.distr_train_backward_dropout(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(),
+                                                     p(saved.lat), saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream(),
+                                                     C.byref(td)))
     return grads, g_lat
 
 
 class DecodeSdfTrainFunction(torch.autograd.Function):
     """decode_sdf on the layer-wise path with autograd to the codes AND the eighteen weight tensors: (codes (S, C) or (1, C), flat points
     (sum counts, 3), counts, clamp, W0..W8, b0..b8) -> (sum counts, 1). The forward keeps the workspaces (the layer inputs) for the
-    backward. More than 64 segments run in chunks of 64; the weight gradients of the chunks are added in chunk order. Points are data."""
+    backward. More than 64 segments run in chunks of 64; the weight gradients of the chunks are added in chunk order. Points are data.
+    dropout: None or (layer_mask, threshold, scale, seed, segment_base); a chunk's segment_base is segment_base + its first segment."""
 
     @staticmethod
-    def forward(ctx, codes, points, counts, clamp_dist, *weights):
+    def forward(ctx, codes, points, counts, clamp_dist, dropout, *weights):
         if len(weights) != 18:
             raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
         counts = [int(c) for c in counts]
@@ -737,7 +790,8 @@ class DecodeSdfTrainFunction(torch.autograd.Function):
         outs, ctx.saved_chunks = [], []
         for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
             n = sum(counts[s0:s0 + ns])
-            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist)
+            drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
+            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist, dropout=drop)
             outs.append(out)
             ctx.saved_chunks.append((saved, p0, n, s0, ns))
         ctx.codes_shape, ctx.shared = codes.shape, lat.shape[0] == 1
@@ -757,11 +811,11 @@ class DecodeSdfTrainFunction(torch.autograd.Function):
                     a += b
         g_rows = rows[0] if len(rows) == 1 else torch.cat(rows)
         g_codes = (g_rows.sum(0) if ctx.shared and g_rows.shape[0] > 1 else g_rows).reshape(ctx.codes_shape)
-        return (g_codes, None, None, None) + tuple(total)
+        return (g_codes, None, None, None, None) + tuple(total)
 
 
-def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None):
-    return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, *weights)
+def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None, dropout=None):
+    return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, dropout, *weights)
 
 
 def depth_samples_count(engine, cfg, depth):

@@ -73,6 +73,34 @@ int distr_train_backward(distr_ctx* ctx, const distr_train_weights* weights, int
                          const float* latent_dev, int64_t latent_stride, const float* g_sdf, float clamp, void* ws_dev,
                          const distr_train_grads* grads, float* g_latent, void* stream);
 
+/* ---- dropout in training mode. The mask is a pure function, no generator state and no stored mask:
+ *   keep(seed, l, g, i, n) = out[i & 3] >= threshold
+ *   out = philox4x32_10(counter = (i >> 2, g, n, l), key = (seed & 0xffffffff, seed >> 32))
+ * l = 0..7: the layer whose relu output is dropped (lin_l); n: its output unit; g = segment_base + s: the segment's global index
+ * (its low 32 bits); i: the point's index inside its segment. threshold = min(2^32 - 1, floor(p * 2^32)) and scale = float(1 / (1 - p))
+ * are the caller's (computed in double). A kept value is multiplied by scale, a dropped one is stored as +0: the saved X_(l+1) is the
+ * activation behind the dropout. The mask does not depend on the padding, on how a list is cut into calls, or on the machine.
+ * drop == NULL or layer_mask == 0: exactly the calls above. The backward takes the struct of its forward. Refused
+ * (DISTR_ERR_INVALID_ARG): a wrong struct_size, layer_mask above 0xff, a scale that is not finite or below 1, segment_base < 0 or
+ * segment_base + nseg > 2^32. */
+typedef struct distr_train_dropout {
+  uint32_t struct_size;
+  uint32_t layer_mask;      /* bit l: drop lin_l's output, l = 0..7 */
+  uint32_t threshold;       /* T */
+  float    scale;
+  uint64_t seed;
+  int64_t  segment_base;    /* global index of segment 0 of this call */
+} distr_train_dropout;
+
+int distr_train_forward_dropout(distr_ctx* ctx, const distr_train_weights* weights, int32_t nseg, const int64_t* counts_host,
+                                const float* latent_dev, int64_t latent_stride, const float* xyz_dev, float clamp_dist, float* sdf_dev,
+                                void* ws_dev, size_t ws_bytes, void* stream, const distr_train_dropout* drop);
+int distr_train_backward_dropout(distr_ctx* ctx, const distr_train_weights* weights, int32_t nseg, const int64_t* counts_host,
+                                 const float* latent_dev, int64_t latent_stride, const float* g_sdf, float clamp, void* ws_dev,
+                                 const distr_train_grads* grads, float* g_latent, void* stream, const distr_train_dropout* drop);
+/* host code, no GPU: the definition above (1 = kept), for tests and callers */
+int distr_train_dropout_keep(uint64_t seed, uint32_t threshold, int32_t layer, int64_t segment, int64_t point, int32_t unit);
+
 #ifdef __cplusplus
 }
 #endif
