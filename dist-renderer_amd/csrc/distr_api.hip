@@ -16,7 +16,7 @@
 #include "distr_inst.hpp"      // distr_kernels.hpp + the big template kernels as extern templates (their code: distr_inst.hip, per group)
 #include "distr_losses.hpp"
 #include "distr_mesh.hpp"
-#include "distr_mlp_b6.hpp"
+#include "distr_mlp_split.hpp"
 #include "distr_samples.hpp"
 #include "distr_normal_grad.hpp"
 #include "distr_color_batch.hpp"
@@ -34,11 +34,10 @@ struct distr_ctx {
   bool has_color = false;
   DecoderDev D{};
   DecoderDev16 D16{};
-  DecoderB6 B6{};                   // split-bf16 weight planes of the shape decoder (distr_mlp_eval_bf16x6), own allocation
-  uint32_t* dec_buf_b6 = nullptr;
-  DecoderH3 H3{};                   // split-f16 weight planes (distr_mlp_h3.hpp), in the same allocation; h3_ok: every layer's largest
-  bool h3_ok = false;               // |weight| lies in [H3_WMIN, H3_WMAX); otherwise h3_why names the first layer outside it
-  std::string h3_why;
+  DecoderSplit planes[2]{};         // [arith - 1]: split-bf16 / split-f16 weight planes of the shape decoder (distr_mlp_split.hpp) ...
+  uint32_t* dec_buf_split = nullptr;   // ... in one allocation of their own
+  bool h3_ok = false;               // f16x3: every layer's largest |weight| lies in [H3_WMIN, H3_WMAX); otherwise h3_why names the first
+  std::string h3_why;               // layer outside it
   bool has_decoder = false;
   bool profiling = false;
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
@@ -172,33 +171,29 @@ inline float from_bf16(uint16_t b) {
   return f;
 }
 
-// Split-bf16 A-fragment planes of v_mfma_f32_32x32x16_bf16 (distr_mlp_b6.hpp::dense_b6): W = w0 + w1 + w2 with w0 = bf16(W),
-// w1 = bf16(W - w0), w2 = bf16(W - w0 - w1); fragment index (((kb * 4 + wave) * NOB + ob) * 3 + plane) * 64 + lane holds the 8 bf16
-// W_plane[o][16 kb + 8 h + 0..7], o = wave * 32 NOB + 32 ob + (lane & 31), h = lane >> 5.
-void pack_fragments_b6(const float* W, int K, int O, uint16_t* dst) {
-  const int NOB = O / 128, NKB = K / 16;
-  for (int kb = 0; kb < NKB; ++kb)
-    for (int w = 0; w < 4; ++w)
-      for (int ob = 0; ob < NOB; ++ob)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int o = w * 32 * NOB + 32 * ob + (lane & 31), h = lane >> 5;
-          for (int i = 0; i < 8; ++i) {
-            const float v = W[(size_t)o * K + 16 * kb + 8 * h + i];
-            const uint16_t p0 = to_bf16(v);
-            const float r1 = v - from_bf16(p0);
-            const uint16_t p1 = to_bf16(r1);
-            const uint16_t p2 = to_bf16(r1 - from_bf16(p1));
-            const uint16_t pl[3] = {p0, p1, p2};
-            for (int p = 0; p < 3; ++p)
-              dst[((((((size_t)kb * 4 + w) * NOB + ob) * 3 + p) * 64 + lane) * 8) + i] = pl[p];
-          }
-        }
+// One f32 as the planes of a split format (distr_mlp_split.hpp), round to nearest even of the running remainder; false: left the range.
+// bf16x6: W = w0 + w1 + w2 with w0 = bf16(W), w1 = bf16(W - w0), w2 = bf16(W - w0 - w1)
+inline bool split_bf16x3(float v, uint16_t* pl) {
+  pl[0] = to_bf16(v);
+  const float r1 = v - from_bf16(pl[0]);
+  pl[1] = to_bf16(r1);
+  pl[2] = to_bf16(r1 - from_bf16(pl[1]));
+  return true;
+}
+// f16x3: SW W = w0 + w1 with w0 = f16(SW W), w1 = f16(SW W - w0) (denormals kept)
+inline bool split_f16x2(float w, uint16_t* pl) {
+  const float v = FmtH3::SW * w;
+  const _Float16 h0 = (_Float16)v;
+  const _Float16 h1 = (_Float16)(v - (float)h0);
+  memcpy(&pl[0], &h0, 2); memcpy(&pl[1], &h1, 2);
+  return fabsf(v) < 65504.f;
 }
 
-// Split-f16 A-fragment planes of v_mfma_f32_32x32x16_f16 (distr_mlp_h3.hpp::dense_h3): SW W = w0 + w1 with w0 = f16(SW W),
-// w1 = f16(SW W - w0) (round to nearest even, denormals kept); fragment index (((kb * 4 + wave) * NOB + ob) * 2 + plane) * 64 + lane
-// holds the 8 f16 W_plane[o][16 kb + 8 h + 0..7]. Returns false when a scaled weight leaves the f16 range.
-bool pack_fragments_h3(const float* W, int K, int O, uint16_t* dst) {
+// A-fragment planes of v_mfma_f32_32x32x16_{bf16,f16} (distr_mlp_split.hpp::split_dense): fragment index
+// (((kb * 4 + wave) * NOB + ob) * NP + plane) * 64 + lane holds the 8 values W_plane[o][16 kb + 8 h + 0..7],
+// o = wave * 32 NOB + 32 ob + (lane & 31), h = lane >> 5. Returns false when a weight leaves the format's range.
+template <class Split>
+bool pack_fragments_split(const float* W, int K, int O, int NP, Split split, uint16_t* dst) {
   const int NOB = O / 128, NKB = K / 16;
   bool ok = true;
   for (int kb = 0; kb < NKB; ++kb)
@@ -207,14 +202,10 @@ bool pack_fragments_h3(const float* W, int K, int O, uint16_t* dst) {
         for (int lane = 0; lane < 64; ++lane) {
           const int o = w * 32 * NOB + 32 * ob + (lane & 31), h = lane >> 5;
           for (int i = 0; i < 8; ++i) {
-            const float v = H3_SW * W[(size_t)o * K + 16 * kb + 8 * h + i];
-            if (!(fabsf(v) < 65504.f)) ok = false;
-            const _Float16 h0 = (_Float16)v;
-            const _Float16 h1 = (_Float16)(v - (float)h0);
-            uint16_t pl[2];
-            memcpy(&pl[0], &h0, 2); memcpy(&pl[1], &h1, 2);
-            for (int p = 0; p < 2; ++p)
-              dst[((((((size_t)kb * 4 + w) * NOB + ob) * 2 + p) * 64 + lane) * 8) + i] = pl[p];
+            uint16_t pl[3];
+            if (!split(W[(size_t)o * K + 16 * kb + 8 * h + i], pl)) ok = false;
+            for (int p = 0; p < NP; ++p)
+              dst[((((((size_t)kb * 4 + w) * NOB + ob) * NP + p) * 64 + lane) * 8) + i] = pl[p];
           }
         }
   return ok;
@@ -678,7 +669,7 @@ void distr_destroy(distr_ctx* ctx) {
   if (!ctx) return;
   if (ctx->dec_buf) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->dec_buf); }
   if (ctx->dec_buf_color) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->dec_buf_color); }
-  if (ctx->dec_buf_b6) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->dec_buf_b6); }
+  if (ctx->dec_buf_split) { (void)hipSetDevice(ctx->device); (void)hipFree(ctx->dec_buf_split); }
   for (auto& r : ctx->xr) { if (r.buf) (void)hipFree(r.buf); if (r.flags) (void)hipFree(r.flags); }
   if (ctx->hint_host) (void)hipHostFree(ctx->hint_host);
   for (auto& p : ctx->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -694,7 +685,7 @@ const char* distr_last_error(const distr_ctx* ctx) { return ctx ? ctx->err.c_str
 // lin4's K stays 256. Wide layout (rows3 > 253, code length < 256): lin3 has 512 rows the same way (real, zero up to 509, xyz at
 // 509..511) and lin4 K = 512. The split-bf16 / split-f16 planes are packed for C = 256 only (the only decoders they may run).
 static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const float* w, size_t n_floats, float** dev_buf, DecoderDev& D,
-                         DecoderDev16* D16, DecoderB6* B6 = nullptr, uint32_t** dev_buf_b6 = nullptr, DecoderH3* H3 = nullptr,
+                         DecoderDev16* D16, DecoderSplit* planes = nullptr, uint32_t** dev_buf_split = nullptr,
                          bool* h3_ok = nullptr, bool compact = false, std::string* h3_why = nullptr) {
   if (rows3 < 1 || rows3 > 509) return fail(ctx, DISTR_ERR_UNSUPPORTED, "lin3 with %d rows does not fit the 509-row tile", rows3);
   const bool wide = rows3 > 253;
@@ -799,61 +790,46 @@ static int build_decoder(distr_ctx* ctx, int nlat, int rows3, int nout, const fl
     for (int l : {2, 5, 6, 7}) D16->Wf[l] = D16->Wf[1];
   }
 #endif
-  if (B6) {   // split-bf16 planes of lin1..lin7 for the opt-in arithmetic mode (distr_mlp_eval_bf16x6): 9.4 MB, own allocation
-    std::vector<uint16_t> hb;
-    size_t offb[8] = {0}, offbt[8] = {0};
+  if (planes) {   // split planes of lin1..lin7 and of their transposes (backward dX chain: K' = Op[l], O' = Kp[l]) for the opt-in arithmetic
+    std::vector<uint16_t> hb;   // modes: bf16x6 2 x 9.4 MB, f16x3 2 x 6.3 MB, own allocation
+    size_t off[2][2][8] = {};   // [format][transposed][layer]
+    bool fits[2][8] = {};       // [format][layer]: every weight stayed inside the format's range
+    auto pack = [&](int f, int NP, auto split) {
+      for (int t = 0; t < 2; ++t)
+        for (int l = 1; l < 8; ++l) {
+          const std::vector<float> W = t ? transposed(l) : std::vector<float>();
+          off[f][t][l] = (hb.size() + 127) & ~(size_t)127;
+          hb.resize(off[f][t][l] + Wp[l].size() * NP, 0);
+          const bool ok = pack_fragments_split(t ? W.data() : Wp[l].data(), t ? Op[l] : Kp[l], t ? Kp[l] : Op[l], NP, split, hb.data() + off[f][t][l]);
+          if (!t) fits[f][l] = ok;
+        }
+    };
+    pack(0, FmtB6::NP, split_bf16x3);
+    pack(1, FmtH3::NP, split_f16x2);
+    *h3_ok = true;
     for (int l = 1; l < 8; ++l) {
-      offb[l] = (hb.size() + 127) & ~(size_t)127;
-      hb.resize(offb[l] + Wp[l].size() * 3, 0);
-      pack_fragments_b6(Wp[l].data(), Kp[l], Op[l], hb.data() + offb[l]);
-    }
-    for (int l = 1; l < 8; ++l) {   // transposed matrices (backward dX chain): K' = Op[l], O' = Kp[l]
-      const std::vector<float> Wt = transposed(l);
-      offbt[l] = (hb.size() + 127) & ~(size_t)127;
-      hb.resize(offbt[l] + Wt.size() * 3, 0);
-      pack_fragments_b6(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], hb.data() + offbt[l]);
-    }
-    size_t offh[8] = {0}, offht[8] = {0};
-    if (H3) {   // split-f16 planes of lin1..lin7 and of their transposes: 2 x 6.3 MB
-      *h3_ok = true;
-      for (int l = 1; l < 8; ++l) {
-        offh[l] = (hb.size() + 127) & ~(size_t)127;
-        hb.resize(offh[l] + Wp[l].size() * 2, 0);
-        const bool fits = pack_fragments_h3(Wp[l].data(), Kp[l], Op[l], hb.data() + offh[l]);
-        // the accepted range of the mode, per layer and on both sides (distr_mlp_h3.hpp: H3_WMAX, H3_WMIN)
-        float wmax = 0.f;
-        for (float v : Wp[l]) wmax = fmaxf(wmax, fabsf(v));
-        const bool high = !fits || !(wmax < H3_WMAX), low = wmax < H3_WMIN;
-        if ((high || low) && *h3_ok) {
-          *h3_ok = false;
-          if (h3_why) {
-            char msg[200];
-            if (high) snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g times %g leaves the f16 range (the bound is %g)", l, (double)wmax, (double)H3_SW, (double)H3_WMAX);
-            else snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g is below %g: its outputs' second f16 plane falls into the denormals and accuracy is lost silently", l, (double)wmax, (double)H3_WMIN);
-            *h3_why = msg;
-          }
+      // the accepted range of the f16x3 mode, per layer and on both sides (distr_mlp_split.hpp: H3_WMAX, H3_WMIN)
+      float wmax = 0.f;
+      for (float v : Wp[l]) wmax = fmaxf(wmax, fabsf(v));
+      const bool high = !fits[1][l] || !(wmax < H3_WMAX), low = wmax < H3_WMIN;
+      if ((high || low) && *h3_ok) {
+        *h3_ok = false;
+        if (h3_why) {
+          char msg[200];
+          if (high) snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g times %g leaves the f16 range (the bound is %g)", l, (double)wmax, (double)FmtH3::SW, (double)H3_WMAX);
+          else snprintf(msg, sizeof(msg), "lin%d's largest |weight| %g is below %g: its outputs' second f16 plane falls into the denormals and accuracy is lost silently", l, (double)wmax, (double)H3_WMIN);
+          *h3_why = msg;
         }
       }
-      for (int l = 1; l < 8; ++l) {
-        const std::vector<float> Wt = transposed(l);
-        offht[l] = (hb.size() + 127) & ~(size_t)127;
-        hb.resize(offht[l] + Wt.size() * 2, 0);
-        (void)pack_fragments_h3(Wt.data(), /*K'=*/Op[l], /*O'=*/Kp[l], hb.data() + offht[l]);
-      }
     }
-    if (*dev_buf_b6) { HIP_TRY(hipFree(*dev_buf_b6)); *dev_buf_b6 = nullptr; }
-    HIP_TRY(hipMalloc((void**)dev_buf_b6, hb.size() * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(*dev_buf_b6, hb.data(), hb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    B6->Wp[0] = nullptr; B6->Wb[0] = nullptr;
-    for (int l = 1; l < 8; ++l) {
-      B6->Wp[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_b6) + offb[l]);
-      B6->Wb[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_b6) + offbt[l]);
-    }
-    if (H3) {
-      H3->Wp[0] = nullptr; H3->Wb[0] = nullptr;
+    if (*dev_buf_split) { HIP_TRY(hipFree(*dev_buf_split)); *dev_buf_split = nullptr; }
+    HIP_TRY(hipMalloc((void**)dev_buf_split, hb.size() * sizeof(uint16_t)));
+    HIP_TRY(hipMemcpy(*dev_buf_split, hb.data(), hb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    for (int f = 0; f < 2; ++f) {
+      planes[f].Wp[0] = nullptr; planes[f].Wb[0] = nullptr;
       for (int l = 1; l < 8; ++l) {
-        H3->Wp[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_b6) + offh[l]);
-        H3->Wb[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_b6) + offht[l]);
+        planes[f].Wp[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_split) + off[f][0][l]);
+        planes[f].Wb[l] = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(*dev_buf_split) + off[f][1][l]);
       }
     }
   }
@@ -871,10 +847,10 @@ int distr_set_decoder(distr_ctx* ctx, const distr_decoder_desc* desc, const floa
   const int nlat = desc->latent_size;
   int rc;
   if (nlat == LAT) {
-    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, &ctx->B6, &ctx->dec_buf_b6, &ctx->H3, &ctx->h3_ok, ctx->dense_compact, &ctx->h3_why);
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, ctx->planes, &ctx->dec_buf_split, &ctx->h3_ok, ctx->dense_compact, &ctx->h3_why);
   } else {   // no split-arithmetic planes: bf16x6 / f16x3 refuse other code lengths (check_cfg, distr_mlp_eval_*)
-    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, nullptr, nullptr, nullptr, nullptr, ctx->dense_compact);
-    if (!rc && ctx->dec_buf_b6) { HIP_TRY(hipFree(ctx->dec_buf_b6)); ctx->dec_buf_b6 = nullptr; ctx->B6 = DecoderB6{}; ctx->H3 = DecoderH3{}; ctx->h3_ok = false; }
+    rc = build_decoder(ctx, nlat, 509 - nlat, 1, w, n_floats, &ctx->dec_buf, ctx->D, &ctx->D16, nullptr, nullptr, nullptr, ctx->dense_compact);
+    if (!rc && ctx->dec_buf_split) { HIP_TRY(hipFree(ctx->dec_buf_split)); ctx->dec_buf_split = nullptr; ctx->planes[0] = ctx->planes[1] = DecoderSplit{}; ctx->h3_ok = false; }
   }
   if (rc) return rc;
   ctx->has_decoder = true;
@@ -1259,8 +1235,7 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   MarchArgs A;
   memset(&A, 0, sizeof(A));
   A.V = V;
-  A.B6 = ctx->B6;
-  A.H3 = ctx->H3;
+  A.planes[0] = ctx->planes[0]; A.planes[1] = ctx->planes[1];
   const bool split = p.recursive && !p.wide;         // else every ray on 64-ray tiles
   A.t16 = split ? p.t16 : 0; A.t32 = split ? p.t32 : 0; A.which = 64;
   // f(origin) of every view (sample point of padded rows) is evaluated by nviews extra workgroups of ONE march launch: for the
@@ -1310,7 +1285,7 @@ int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews
   LAUNCH_CHECK("k_bwd_prep<emit>");
   BwdArgs B;
   memset(&B, 0, sizeof(B));
-  B.V = V; B.samples = W.samples; B.partial = W.partial; B.bstride = W.bstride; B.B6 = ctx->B6; B.H3 = ctx->H3;
+  B.V = V; B.samples = W.samples; B.partial = W.partial; B.bstride = W.bstride; B.planes[0] = ctx->planes[0]; B.planes[1] = ctx->planes[1];
   // tile-size split of every view's sample list (bwd_range): full rounds on 64-sample tiles, a small remainder on 32-sample tiles
   const bool wide = wide_decoder(ctx);       // (wide decoders: the same tile split, so the same partial rows and reduction order)
   const bool bsplit = V.save_masks != 0;
@@ -1522,10 +1497,10 @@ static int mlp_eval_split(distr_ctx* ctx, bool h3, const float* latent, const fl
   if (rc || n == 0) return rc;
   MarchTimer timer(ctx, s);
   timer.begin();
-  if (h3) hipLaunchKernelGGL(k_eval_h3, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, clamp, sdf, ctx->D, ctx->H3);
-  else hipLaunchKernelGGL(k_eval_b6, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, clamp, sdf, ctx->D, ctx->B6);
+  auto* kernel = h3 ? k_eval_split<DISTR_ARITH_F16X3> : k_eval_split<DISTR_ARITH_BF16X6>;
+  hipLaunchKernelGGL(kernel, dim3(pl.tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, clamp, sdf, ctx->D, ctx->planes[h3 ? 1 : 0]);
   timer.end();
-  LAUNCH_CHECK(h3 ? "k_eval_h3" : "k_eval_b6");
+  LAUNCH_CHECK(h3 ? "k_eval_split<f16x3>" : "k_eval_split<bf16x6>");
   return DISTR_OK;
 }
 

@@ -12,8 +12,7 @@
 #include <type_traits>
 
 #include "distr_mlp.hpp"
-#include "distr_mlp_b6.hpp"
-#include "distr_mlp_h3.hpp"
+#include "distr_mlp_split.hpp"
 #include "../../include/distr.h"
 
 namespace distr {
@@ -735,8 +734,7 @@ struct MarchArgs {
   // 32-ray tiles; which = tile size of THIS launch (a plain k_march launch; the roles of k_step pass their own)
   int32_t t16, t32, which;
   Xchg xc;                   // 16-ray launches: exchange region of the cluster tiles (buf == null: single-workgroup tiles only)
-  DecoderB6 B6;              // split-bf16 weight planes (kernels instantiated with ARITH = 1, distr_render_cfg.arith)
-  DecoderH3 H3;              // split-f16 weight planes (ARITH = 2)
+  DecoderSplit planes[2];    // [ARITH - 1]: split-bf16 / split-f16 weight planes (kernels instantiated with ARITH = 1 / 2, distr_render_cfg.arith)
   int32_t tail_absent;       // tests (DISTR_TAIL_TEST_ABSENT=n): workgroups 0 .. n-1 of k_tail leave at once, as if they never became resident
   const SegTable* seg;       // MODE_EVAL on 64-point tiles: segmented list (c0c4 = [segments][1024], n unused); null: one code, n points
 };
@@ -760,11 +758,10 @@ __device__ __forceinline__ int64_t moff_at(int l) { return (&kernarg_ref<MarchAr
 // Body of one 32*RB-ray tile; `tile` / `ntile_grid` = index and count of the tiles this launch (or this role of a merged
 // launch, k_step) provides, `which` = the tile size the split rule (fine_range) knows this role by.
 // Returns false when the tile lies beyond this role's range (nothing done).
-// ARITH = 0: exact f32 MFMA tile (distr_mlp.hpp); 1: six-product split-bf16 tile (distr_mlp_b6.hpp); 2: three-product split-f16
-// tile (distr_mlp_h3.hpp)   (distr_render_cfg.arith)
-template <int RB, int ARITH> struct TileSmem { using type = Smem<RB>; };
-template <int RB> struct TileSmem<RB, 1> { using type = SmemB6<RB>; };
-template <int RB> struct TileSmem<RB, 2> { using type = SmemH3<RB>; };
+// ARITH = 0: exact f32 MFMA tile (distr_mlp.hpp); 1: six-product split-bf16, 2: three-product split-f16 -- the split tile
+// (distr_mlp_split.hpp) in the format SplitFmt<ARITH>   (distr_render_cfg.arith)
+template <int RB, int ARITH> struct TileSmem { using type = SmemSplit<SplitFmt<ARITH>, RB>; };
+template <int RB> struct TileSmem<RB, 0> { using type = Smem<RB>; };
 
 template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
 __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev& D, typename TileSmem<RB, ARITH>::type& S, int tile, int ntile_grid,
@@ -855,8 +852,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   uint32_t masks[8][4];
   float pre;
   if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true, WIDE, COMPACT>(D, c0, c4, S, masks);
-  else if constexpr (ARITH == 1) pre = mlp_forward_b6<RB, KEEP>(D, A.B6, c0, c4, S, masks);
-  else pre = mlp_forward_h3<RB, KEEP>(D, A.H3, c0, c4, S, masks);
+  else pre = split_forward<SplitFmt<ARITH>, RB, KEEP>(D, A.planes[ARITH - 1], c0, c4, S, masks);
 
   // epilogue: wave 0 (kept whole for the ballot), lane = ray of the tile; lanes >= TILE are invalid
   int64_t mblock = -1;   // mask block this ray's row goes to (KEEP), -1: row not kept
@@ -1704,8 +1700,8 @@ struct StepGrid { int32_t n64, n32, n16; };
 
 template <bool KEEP, int ARITH = 0, bool COMPACT = false>
 __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, DecoderDev16 D16, StepGrid G) {
-  __shared__ __attribute__((aligned(16))) unsigned char raw[(sizeof(Smem<2>) > sizeof(SmemB6<2>)) ? sizeof(Smem<2>) : sizeof(SmemB6<2>)];
-  static_assert(sizeof(Smem<2>) >= sizeof(Smem<1>) && sizeof(Smem<2>) >= sizeof(Smem16CLX) && sizeof(SmemB6<2>) >= sizeof(SmemB6<1>), "role shared memory");
+  __shared__ __attribute__((aligned(16))) unsigned char raw[(sizeof(Smem<2>) > sizeof(SmemSplit<FmtB6, 2>)) ? sizeof(Smem<2>) : sizeof(SmemSplit<FmtB6, 2>)];
+  static_assert(sizeof(Smem<2>) >= sizeof(Smem<1>) && sizeof(Smem<2>) >= sizeof(Smem16CLX) && sizeof(SmemSplit<FmtB6, 2>) >= sizeof(SmemSplit<FmtB6, 1>), "role shared memory");
   // role order in the grid: 32-ray tiles, 16-ray / cluster tiles, 64-ray tiles. On a tail step the cluster tiles start
   // after one wave of idle 32-ray workgroups and the idle 64-ray workgroups retire on the free CUs while the clusters
   // run; on a dense step the remainder tiles start first and the persistent 64-ray workgroups follow as CUs free up.
@@ -1986,8 +1982,7 @@ struct BwdArgs {
   int32_t split;             // SAVED / FULL: 1 = the sample list is split by tile size like a march step (bwd_range)
   float* out_sdf;            // POINTGRAD explicit: [n]   (pixel lists: V.n_sdf)
   float* out_g;              // POINTGRAD explicit: [n][3] (pixel lists: V.n_g)
-  DecoderB6 B6;              // split-bf16 weight planes (k_bwd<BWD_SAVED, RB, 1>: distr_render_cfg.arith)
-  DecoderH3 H3;              // split-f16 weight planes (k_bwd<BWD_SAVED, RB, 2>)
+  DecoderSplit planes[2];    // [ARITH - 1]: split-bf16 / split-f16 weight planes (k_bwd<BWD_SAVED, RB, 1 / 2>: distr_render_cfg.arith)
   const SegTable* seg;       // POINTGRAD explicit on 64-point tiles: segmented list (c0c4 = [segments][1024], n unused); null: one code
 };
 
@@ -2148,8 +2143,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
   }
   float* part = (MODE != BWD_POINTGRAD || partial) ? partial + (size_t)tile * PSTRIDE : nullptr;
   if constexpr (ARITH == 0) mlp_backward<RB, 1, WIDE, COMPACT>(D, S, masks, part, part ? part + HID : nullptr);
-  else if constexpr (ARITH == 1) mlp_backward_b6<RB>(D, A.B6, S, masks, part, part ? part + HID : nullptr);
-  else mlp_backward_h3<RB>(D, A.H3, S, masks, part, part ? part + HID : nullptr);
+  else split_backward<SplitFmt<ARITH>, RB>(D, A.planes[ARITH - 1], S, masks, part, part ? part + HID : nullptr);
 
   if (tid >= 64) return;   // wave 0 stays whole for the shuffle reduction; lanes >= TILE carry zeros
   const int rl = tid & (TILE - 1);

@@ -122,10 +122,10 @@ typedef struct distr_render_cfg {
                                  crop it (distr/functions.py::render_band_call). */
   int32_t arith;              /* DISTR_ARITH_*: arithmetic of the decoder evaluations of the MARCH (no counterpart in the reference, which has
                                  one arithmetic: f32). 0 (default, also what a zeroed struct selects): exact f32. 1: every f32 product of
-                                 the seven wide layers as six bf16 products with f32 accumulation (csrc/distr_mlp_b6.hpp): values within
+                                 the seven wide layers as six bf16 products with f32 accumulation (csrc/distr_mlp_split.hpp, FmtB6): values within
                                  ~1e-6 of the exact ones, on 64- / 32-ray tiles only (no cluster tiles: meant for large, dense renders). The
                                  backward pass is the split-bf16 dX chain on the ReLU masks this forward saved. 2: three f16 products per f32
-                                 product with the activations kept as two f16 planes in LDS (csrc/distr_mlp_h3.hpp): same accuracy class and
+                                 product with the activations kept as two f16 planes in LDS (csrc/distr_mlp_split.hpp, FmtH3): same accuracy class and
                                  tile set as 1 for decoders inside the f16 range (see DISTR_ARITH_F16X3), backward = that of mode 1. */
   int32_t concurrent;         /* hint, 0 by default: 1 = the caller has OTHER renders in flight on other streams of this device (a pool of
                                  streams over the scales of a multi-scale renderer list or the view pairs of a round). The tail of the march

@@ -4,7 +4,7 @@ decoder do to the render? Every f32 product a*w of the decoder's layers is repla
     3 products:  a0*w0 + a0*w1 + a1*w0                          (3 bf16 MFMAs per f32 MFMA: 5.3x the f32 MFMA rate at best)
     6 products:  + a1*w1 + a0*w2 + a2*w0                        (2.7x at best)
 Round 3 adds the split-f16 form (products = 'h3'): a = (a0 + a1) / 64, w = (w0 + w1) / 64 with f16 pieces of the scaled operands,
-    3 products:  a0*w0 + a0*w1 + a1*w0                          (11 + 11 significant bits per operand: what distr_mlp_h3.hpp computes)
+    3 products:  a0*w0 + a0*w1 + a1*w0                          (11 + 11 significant bits per operand: what distr_mlp_split.hpp's FmtH3 computes)
 and compares every form with a float64 decoder as well.
 The whole render (march, sample selection, depth2normal, loss, backward through a straight-through rounding) runs with that
 decoder and is compared with the exact f32 render of the same restatement: mask flips, depth / min-sdf residuals, latent-gradient

@@ -1,9 +1,9 @@
-"""Plane-exact CPU models of the two split arithmetics of the decoder tile (csrc/distr_mlp_b6.hpp, csrc/distr_mlp_h3.hpp) and the
+"""Plane-exact CPU models of the two split arithmetics of the decoder tile (csrc/distr_mlp_split.hpp: FmtB6, FmtH3) and the
 function-preserving rescales of a decoder that probe the range of the split-f16 form. Test infrastructure only.
 
 What is modelled exactly: the planes. Every operand of lin1..lin7 is the sum of bf16 (three) or f16 (two, of the operand times 64)
 planes, each the round-to-nearest-even conversion of the running remainder (torch's conversions, denormals kept); the products
-that are formed are the ones the tiles form (PW / PA of dense_b6 / dense_h3); lin0 and lin8 are plain f32; lin4's latent part is
+that are formed are the ones the tiles form (PW / PA of FmtB6 / FmtH3); lin0 and lin8 are plain f32; lin4's latent part is
 folded into c4 in f32; biases start the accumulator. What is NOT modelled bit for bit is the order of the f32 accumulation inside
 the MFMA: a product of two planes is exact in f32, their sum over k is taken by torch's f32 matmul. The float64 decoder is
 tests/train_restatement.py; it is not restated here.
@@ -11,10 +11,10 @@ tests/train_restatement.py; it is not restated here.
 import numpy as np
 import torch
 
-H3_S = 64.0                      # H3_SX = H3_SW
+H3_S = 64.0                      # FmtH3::SX = FmtH3::SW
 F16_MAX = 65504.0
-B6_PRODUCTS = ((0, 0), (1, 0), (0, 1), (1, 1), (2, 0), (0, 2))      # (weight plane, activation plane): PW / PA of dense_b6
-H3_PRODUCTS = ((0, 0), (1, 0), (0, 1))                              # the same of dense_h3
+B6_PRODUCTS = ((0, 0), (1, 0), (0, 1), (1, 1), (2, 0), (0, 2))      # (weight plane, activation plane): PW / PA of FmtB6
+H3_PRODUCTS = ((0, 0), (1, 0), (0, 1))                              # the same of FmtH3
 PRODUCTS = {'bf16x6': B6_PRODUCTS, 'f16x3': H3_PRODUCTS}
 
 
@@ -33,7 +33,7 @@ def planes(x, n, dtype, ftz=False):
 
 
 def f16_overflowed(v):
-    """store4_h3's flag: the leading f16 plane of a (non-negative) scaled value is inf or NaN (bit pattern >= 0x7c00)."""
+    """The flag of FmtH3's store4: the leading f16 plane of a (non-negative) scaled value is inf or NaN (bit pattern >= 0x7c00)."""
     return ~torch.isfinite(v.to(torch.float16))
 
 
@@ -56,7 +56,7 @@ def forward(Ws, bs, latent, pts, mode, drop=None, clamp=None, ftz=False):
     'bf16x6': six products of three bf16 planes per operand, activations kept in f32 between the layers;
     'f16x3' : three products of two f16 planes of the operands times 64; the activations live as planes, so lin8 reads their sum.
     drop: a (weight plane, activation plane) pair left out of every layer -- a tile that lost a product.
-    The flag is always False except for 'f16x3', where it is raised as store4_h3 raises it; a flagged point's sdf is NaN."""
+    The flag is always False except for 'f16x3', where it is raised as FmtH3's store4 raises it; a flagged point's sdf is NaN."""
     with torch.no_grad():
         Ws, bs = _f32(Ws), _f32(bs)
         latent, pts = _f32([latent, pts])
@@ -106,15 +106,15 @@ def forward(Ws, bs, latent, pts, mode, drop=None, clamp=None, ftz=False):
         y = torch.tanh((x @ Ws[8].t() + bs[8]).reshape(-1))
         if clamp is not None:
             y = torch.clamp(y, -clamp, clamp)
-        return torch.where(over, torch.full_like(y, float('nan')), y), over       # k_eval_h3: NaN for a flagged point
+        return torch.where(over, torch.full_like(y, float('nan')), y), over       # k_eval_split: NaN for a flagged point
 
 
 def h3_weights_in_range(Ws):
-    """pack_fragments_h3's rule on lin1..lin7: every weight times 64 below the largest finite f16."""
+    """split_f16x2's rule (pack_fragments_split) on lin1..lin7: every weight times 64 below the largest finite f16."""
     return all(float(np.abs(np.asarray(Ws[l], np.float32) * np.float32(H3_S)).max()) < F16_MAX for l in range(1, 8))
 
 
-H3_WMIN, H3_WMAX = 2.0 ** -8, F16_MAX / H3_S         # csrc/distr_mlp_h3.hpp
+H3_WMIN, H3_WMAX = 2.0 ** -8, F16_MAX / H3_S         # csrc/distr_mlp_split.hpp
 
 
 def h3_refused_layer(Ws):

@@ -96,6 +96,21 @@ def test_forward_against_float64(decoders, engines, points, fix, code):
                 print(line)
 
 
+@pytest.mark.parametrize('arith', MODES)
+def test_eval_value_is_independent_of_column_and_company(decoders, engines, points, arith):
+    """The claim of the split tile's header for the point-list entry: a point's sdf depends neither on the column of the 64-ray tile it
+    lands in nor on the points that share its tile. 97 points (one full tile and a tail of 33): the same bytes from one call, from the
+    same points in reversed order (every point in another tile and column), and from the chunks [0:1], [1:34], [34:97]."""
+    _, _, latent = decoders['f1']
+    eng, pts = engines['f1'], points[:97]
+    whole = _eval(eng, latent, pts, arith)
+    assert np.isfinite(whole).all()
+    reverse = _eval(eng, latent, np.ascontiguousarray(pts[::-1]), arith)[::-1]
+    chunks = np.concatenate([_eval(eng, latent, pts[a:b], arith) for a, b in ((0, 1), (1, 34), (34, 97))])
+    assert whole.tobytes() == reverse.tobytes(), np.flatnonzero(whole != reverse)
+    assert whole.tobytes() == chunks.tobytes(), np.flatnonzero(whole != chunks)
+
+
 # ------------------------------------------------------------------------------------------------ (b) the range of f16x3
 def _single_weight(Ws, bs, value):
     W1 = [w.copy() for w in Ws]
@@ -277,7 +292,7 @@ def _check_split_probes(eng, arith, probes, floor, key):
 
 @pytest.mark.parametrize('arith', MODES)
 def test_probes_split_match_float64(engine, probes, probe_floor, arith):
-    """mlp_backward_b6 / mlp_backward_h3 on one sample per view, upstream gradients from 2^-40 to 2^40: every probe whose ReLU pattern
+    """split_backward in both formats on one sample per view, upstream gradients from 2^-40 to 2^40: every probe whose ReLU pattern
     is unambiguous (no float64 pre-activation within 1e-5 of zero: the forward's sample point differs from the oracle's by the march's
     1e-6-level drift) is within 3 x the f32 floor of float64."""
     _check_split_probes(engine, arith, probes, probe_floor, 'f1')

@@ -50,7 +50,7 @@ def test_rescales_keep_the_float64_function_exactly(f1, k):
     for Ws, bs in members:
         assert torch.equal(sdf64(Ws, bs, f1['latent'], f1['pts']), f1['ref'])
         assert k == 0 or any(not np.array_equal(a, b) for a, b in zip(Ws, f1['Ws']))
-        assert sr.h3_weights_in_range(Ws)                    # k = 10: largest weight 332, inside pack_fragments_h3's range
+        assert sr.h3_weights_in_range(Ws)                    # k = 10: largest weight 332, inside split_f16x2's range
 
 
 @pytest.mark.parametrize('mode', ['bf16x6', 'f16x3'])
@@ -76,7 +76,7 @@ def test_a_lost_product_exceeds_the_bar(f1, f32_err, mode, drop):
 
 
 def test_model_predicts_the_silent_loss_of_f16x3(f1, f32_err):
-    """Inside the range pack_fragments_h3 accepts, small activations cost accuracy with nothing reported (the second f16 plane
+    """Inside the range split_f16x2 accepts, small activations cost accuracy with nothing reported (the second f16 plane
     falls into the denormals); bf16x6 has f32's exponent range and does not care."""
     for name, Ws, bs in [('chain k=10',) + sr.rescale_chain(f1['Ws'], f1['bs'], 10), ('pair lin1 k=10',) + sr.rescale_pair(f1['Ws'], f1['bs'], 10, 1)]:
         a = sr.errors(sr.forward(Ws, bs, f1['latent'], f1['pts'], 'f32')[0], f1['ref'])
@@ -109,7 +109,7 @@ def test_acceptance_rule_refuses_what_the_model_loses(f1, f32_err):
 
 
 def test_f16x3_model_marks_overflow_at_the_f16_range():
-    """store4_h3 flags a ray when the leading f16 plane of 64 x is inf: round to nearest turns into inf from 65520 on, half a unit
+    """FmtH3's store4 flags a ray when the leading f16 plane of 64 x is inf: round to nearest turns into inf from 65520 on, half a unit
     in the last place above the largest finite f16, 65504; values in [65504, 65520) round to 65504, keep a finite second plane and
     stay exact to 2^-22, so nothing is lost where they are not flagged. Below 65504 nothing may be flagged, from 65520 on everything."""
     v = torch.tensor([0.0, 1.0, 65503.0, 65503.996, 65504.0, 65519.996, 65520.0, 65536.0, 1e6, float('inf'), float('nan')])
