@@ -43,6 +43,9 @@ struct distr_ctx {
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
   int tail16_threshold = 4096;  // t16: ... and on 16-ray tiles (16x16x4 MFMA)
   bool dense_compact = true;    // DISTR_DENSE_COMPACT=0: the exact-f32 64-ray tile (march and saved-mask backward) multiplies every hidden unit, live for the tile or not (a time knob)
+  bool live_order = true;       // DISTR_LIVE_ORDER=0: every full-resolution step appends its survivors atomically, in completion order (no k_live_pack; a time knob)
+  bool ray_blocks = true;       // DISTR_RAY_BLOCKS=0: the setup kernels enumerate pixels in strips of 256 instead of 16 x 16 blocks (a time knob)
+  int debug_steps = -1;         // distr_debug_live_list: the forward stops behind this many full-resolution steps (no tail launch, no finalize)
   bool save_masks = true;       // save ReLU masks in the forward so that the backward skips the decoder recompute
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
@@ -77,7 +80,7 @@ struct distr_ctx {
   struct TailHint { int32_t key[16]; bool used = false; uint64_t last_use = 0; };
   static constexpr int NHINT = 16;
   TailHint hints[NHINT];
-  int32_t* hint_host = nullptr; // NHINT host-mapped words (hipHostMalloc): -1 = nothing written yet
+  int32_t* hint_host = nullptr; // 2 x NHINT host-mapped words (hipHostMalloc): -1 = nothing written yet; [i] tail launch, [NHINT + i] end of the ordered steps
   int32_t* hint_dev = nullptr;
   bool hint_failed = false;
 };
@@ -373,14 +376,15 @@ int32_t* tail_hint_slot(distr_ctx* ctx, const distr_render_cfg& c, int nviews, b
     if (capturing) return nullptr;
     void* h = nullptr;
     void* d = nullptr;
-    if (hipHostMalloc(&h, distr_ctx::NHINT * sizeof(int32_t), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+    if (hipHostMalloc(&h, 2 * distr_ctx::NHINT * sizeof(int32_t), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
       (void)hipGetLastError();
       if (h) (void)hipHostFree(h);
       ctx->hint_failed = true;
       return nullptr;
     }
     ctx->hint_host = (int32_t*)h; ctx->hint_dev = (int32_t*)d;
-    for (int i = 0; i < distr_ctx::NHINT; ++i) ctx->hint_host[i] = -1;
+    static_assert(distr_ctx::NHINT == HINT_ORDER_OFF, "k_finalize writes the order hint NHINT words behind the tail hint");
+    for (int i = 0; i < 2 * distr_ctx::NHINT; ++i) ctx->hint_host[i] = -1;
   }
   Pyramid py;
   (void)pyramid_of(c, py);
@@ -399,6 +403,7 @@ int32_t* tail_hint_slot(distr_ctx* ctx, const distr_render_cfg& c, int nviews, b
   memcpy(h.key, key, sizeof(key));
   h.used = true; h.last_use = ++clock;
   __atomic_store_n(ctx->hint_host + lru, -1, __ATOMIC_RELAXED);
+  __atomic_store_n(ctx->hint_host + distr_ctx::NHINT + lru, -1, __ATOMIC_RELAXED);
   *dev_word = ctx->hint_dev + lru;
   return ctx->hint_host + lru;
 }
@@ -451,6 +456,8 @@ size_t make_view(const distr_render_cfg& c, void* base, View& V, bool save_masks
   const size_t P = V.P, bs = c.buffer_size;
   V.live[0] = cv.take<int32_t>(P);
   V.live[1] = cv.take<int32_t>(P);
+  V.lslot = cv.take<int32_t>(P + 64);
+  V.tcount = cv.take<int32_t>(P / 16 + 4);
   V.m = cv.take<float>(P); V.init_now = cv.take<float>(P); V.maxbound = cv.take<float>(P);
   V.minabs = cv.take<float>(P); V.first_sdf = cv.take<float>(P);
   V.tk_s = cv.take<float>(bs * P); V.tk_zb = cv.take<float>(bs * P); V.tk_za = cv.take<float>(bs * P);
@@ -458,6 +465,7 @@ size_t make_view(const distr_render_cfg& c, void* base, View& V, bool save_masks
   V.tk_slot = cv.take<int32_t>(bs * P);
   V.tclaim = cv.take<int32_t>(P / 16 + 2);
   V.tail_from = V.fine_steps;
+  V.order_until = V.fine_steps;
   V.zdepth_s = cv.take<float>(P); V.depth_pre = cv.take<float>(P); V.nrm_t = cv.take<float>(3 * P);
   V.mask_s = cv.take<uint8_t>(P);
   V.nlist = cv.take<int32_t>(P); V.n_sdf = cv.take<float>(P); V.n_g = cv.take<float>(3 * P);
@@ -487,6 +495,8 @@ size_t bwd_bytes(const distr_render_cfg& c) {
 
 inline dim3 grid1(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
 inline dim3 gridv(const View& V, int64_t n) { return dim3((unsigned)((n + 255) / 256), (unsigned)V.nviews); }   // (blocks of 256, view)
+// the setup kernels over a w x h grid (setup_pixel): 16 x 16 pixel blocks, or strips of 256 pixels
+inline dim3 grid_setup(const View& V, int w, int h) { return V.blocks ? dim3((unsigned)block_grid(w, h), (unsigned)V.nviews) : gridv(V, (int64_t)w * h); }
 
 struct MarchTimer {  // optional hipEvent bracket around the march kernel launches
   distr_ctx* ctx; hipStream_t s; bool on;
@@ -633,6 +643,15 @@ int distr_create_abi(distr_ctx** out, int hip_device, uint32_t abi_version) {
     }
     ctx->dense_compact = e[0] == '1';
   }
+  for (const char* name : {"DISTR_LIVE_ORDER", "DISTR_RAY_BLOCKS"})
+    if (const char* e = getenv(name)) {
+      if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
+        ctx->err = std::string(name) + " must be 0 or 1 (got '" + e + "')";
+        *out = ctx;
+        return DISTR_ERR_INVALID_ARG;
+      }
+      (strcmp(name, "DISTR_LIVE_ORDER") == 0 ? ctx->live_order : ctx->ray_blocks) = e[0] == '1';
+    }
   if (const char* e = getenv("DISTR_STICKY")) ctx->sticky = atoi(e) != 0;
   if (const char* e = getenv("DISTR_XCHG_SC1")) ctx->xchg_sc1 = atoi(e) != 0;
   if (const char* e = getenv("DISTR_CLUSTER_SPREAD")) ctx->cluster_spread = atoi(e) != 0;
@@ -1072,12 +1091,18 @@ int32_t* choose_tail_from(distr_ctx* ctx, View& V, hipStream_t s) {
   if (V.cfg.marcher == DISTR_MARCH_TRIVIAL || V.cfg.arith != DISTR_ARITH_F32 || !ctx->tail || V.cfg.concurrent || ctx->tail16_threshold <= 0 ||
       wide_decoder(ctx))
     return hint_dev;
+  if (ctx->debug_steps >= 0) return nullptr;      // (distr_debug_live_list: one launch per step, a pack behind each, no hint read or written)
   int32_t* hint = tail_hint_slot(ctx, V.cfg, V.nviews, is_capturing(s), &hint_dev);
   if (ctx->tail_force >= 0) V.tail_from = std::min(ctx->tail_force, V.fine_steps);
   else if ((int64_t)V.nviews * V.P <= ctx->tail_px) V.tail_from = 0;
   else if (hint) {
     const int32_t h = __atomic_load_n(hint, __ATOMIC_RELAXED);
     if (h >= 0 && h + 2 <= V.fine_steps) V.tail_from = h;      // (nothing to gain from a tail of one step)
+  }
+  if (hint) {
+    // the previous render's first step without rounds, plus one step of margin: behind it no k_live_pack is launched
+    const int32_t o = __atomic_load_n(hint + distr_ctx::NHINT, __ATOMIC_RELAXED);
+    if (o >= 0) V.order_until = std::min(o + 1, V.fine_steps);
   }
   return hint_dev;
 }
@@ -1087,7 +1112,7 @@ int setup_levels(distr_ctx* ctx, const View& V, const float* latent, int64_t lat
   hipLaunchKernelGGL(k_prep, dim3(4, (unsigned)V.nviews), dim3(256), 0, s, V, ctx->D, latent, lat_stride, R, T, vf);
   LAUNCH_CHECK("k_prep");
   for (int l = 0; l < V.nlev; ++l) {
-    hipLaunchKernelGGL(k_setup_level, gridv(V, V.lv[l].n), dim3(256), 0, s, V, l);
+    hipLaunchKernelGGL(k_setup_level, grid_setup(V, V.lv[l].w, V.lv[l].h), dim3(256), 0, s, V, l);
     LAUNCH_CHECK("k_setup_level");
     if (V.band) {
       hipLaunchKernelGGL(k_maxinit_full, gridv(V, (int64_t)V.lv[l].full_h * V.lv[l].w), dim3(256), 0, s, V, l);
@@ -1131,11 +1156,12 @@ int march_fine(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p,
   const int nviews = V.nviews, P = V.P, t16 = p.t16, t32 = p.t32;
   const unsigned NV = (unsigned)nviews;
   const bool keep = V.save_masks != 0;
-  hipLaunchKernelGGL(k_fine_init, gridv(V, P), dim3(256), 0, s, V);
+  hipLaunchKernelGGL(k_fine_init, grid_setup(V, V.lv[0].w, V.lv[0].h), dim3(256), 0, s, V);
   LAUNCH_CHECK("k_fine_init");
   // upper bounds of a step's live rays in the virtual concatenation of the views (every view padded to 16 / 64 rays)
   const int64_t N64 = (int64_t)nviews * pad_to(P, 64);
   for (int st = 0; st < V.fine_steps; ++st) {
+    if (ctx->debug_steps >= 0 && st >= ctx->debug_steps) break;
     A.lvl = 0; A.step = st;
     timer.begin();
     if (st == V.tail_from) {
@@ -1163,6 +1189,8 @@ int march_fine(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p,
     // one round, distr_create), with N64 <= t16 the 32-ray role stays empty too.
     const int64_t bound = (t16 < t32) ? (int64_t)t32 + t16 : t32;
     const bool skip64 = N64 <= bound;
+    // ordered live list (step_ordered): only a step whose 64-ray role has work keeps it, only the compacted 64-ray tile gains from it
+    A.live_order = (ctx->live_order && !skip64 && st + 1 < V.fine_steps && st < V.order_until && compact_tile(ctx, 2, p.arith())) ? 1 : 0;   // (the last step leaves no list anybody reads)
     const bool skip32 = t32 <= t16 || N64 <= t16;
     StepGrid G;
     G.n64 = skip64 ? 0 : std::min(up8(N64 / 64), 256);            // persistent: at most one 64-ray workgroup per CU
@@ -1182,6 +1210,12 @@ int march_fine(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p,
     }
     if (int rc = launch_step(ctx, "k_step", keep, p.arith(), (unsigned)(G.n64 + G.n32 + G.n16), s, A, G)) return rc;
     timer.end();
+    if (A.live_order) {
+      // closes the gaps of the slots an ordered step left (the device decides from the step's count; behind any other step its workgroups
+      // leave at once). Outside the timer's bracket: the profile lists march launches.
+      hipLaunchKernelGGL(k_live_pack, dim3((unsigned)((P / 16 + PACK_CHUNKS) / PACK_CHUNKS), NV), dim3(256), 0, s, V, st, t16, t32);
+      LAUNCH_CHECK("k_live_pack");
+    }
   }
   return DISTR_OK;
 }
@@ -1189,7 +1223,8 @@ int march_fine(distr_ctx* ctx, const View& V, MarchArgs& A, const RenderPlan& p,
 int finalize_and_normals(distr_ctx* ctx, const View& V, bool wide, int32_t* hint_dev, float* zdepth, uint8_t* mask,
                          float* min_sdf, float* depth, float* normal, hipStream_t s) {
   const int P = V.P;
-  hipLaunchKernelGGL(k_finalize, gridv(V, P), dim3(256), 0, s, V, zdepth, mask, min_sdf, depth, hint_dev, (int32_t)ctx->tail_rays);
+  hipLaunchKernelGGL(k_finalize, gridv(V, P), dim3(256), 0, s, V, zdepth, mask, min_sdf, depth, hint_dev, (int32_t)ctx->tail_rays,
+                     (int32_t)((V.cfg.arith != DISTR_ARITH_F32) ? 0 : std::min(ctx->tail16_threshold, ctx->hybrid_threshold)), (int32_t)ctx->hybrid_threshold);
   LAUNCH_CHECK("k_finalize");
   if (!V.cfg.want_normal) return DISTR_OK;
   if (V.cfg.use_depth2normal) {
@@ -1219,6 +1254,7 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   View V;
   const size_t single = make_view(*cfg, ws, V, ctx->save_masks, nviews);
   if (ws_bytes < single * nviews) return fail(ctx, DISTR_ERR_WORKSPACE, "forward workspace too small: %zu < %zu", ws_bytes, single * nviews);
+  V.blocks = ctx->ray_blocks ? 1 : 0;
   ViewFlags vf;
   rc = make_view_flags(ctx, *cfg, nviews, view_flags, vf);
   if (rc) return rc;
@@ -1243,6 +1279,7 @@ int render_forward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews,
   p.xr = (split && !p.b6) ? xchg_region(ctx, s) : nullptr;
   if ((rc = march_coarse(ctx, V, A, p, timer, s))) return rc;
   if ((rc = march_fine(ctx, V, A, p, timer, s))) return rc;
+  if (ctx->debug_steps >= 0) return DISTR_OK;
   return finalize_and_normals(ctx, V, p.wide, hint_dev, zdepth, mask, min_sdf, depth, normal, s);
 }
 
@@ -1673,6 +1710,69 @@ int distr_get_live_counts(distr_ctx* ctx, const distr_render_cfg* cfg, const voi
     for (int st = 0; st < V.lv[l].steps; ++st) { if (k < cap) out[k] = C->cnt_level[l]; ++k; }
   for (int t = 0; t < V.fine_steps; ++t) { if (k < cap) out[k] = (cfg->marcher == DISTR_MARCH_TRIVIAL) ? C->cnt_level[0] : C->cnt_live[t] + C->cnt_sticky[t]; ++k; }
   *n = k;
+  return DISTR_OK;
+}
+
+// ---- the ordered live list seen from outside (include/distr_live_order.h)
+int32_t distr_block_grid(int32_t w, int32_t h) { return block_grid(w, h); }
+
+int32_t distr_block_pixel(int32_t w, int32_t h, int32_t block, int32_t thread) {
+  if (block < 0 || block >= block_grid(w, h) || thread < 0 || thread >= 256) return -1;
+  return block_pixel(w, h, block, thread);
+}
+
+int distr_get_kstep_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws, int64_t* out, int32_t cap, int32_t* n, void* stream) {
+  if (!ctx || !ws || !out || !n) return fail(ctx, DISTR_ERR_INVALID_ARG, "null argument");
+  EntryGuard guard_(ctx);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  View V;
+  const Consts* C;
+  if ((rc = read_consts(ctx, cfg, ws, (hipStream_t)stream, V, &C))) return rc;
+  int k = 0;
+  auto put = [&](unsigned long long word) {
+    if (k < cap) {
+      const int64_t tiles = (int64_t)(word >> KSTEP_BITS);
+      out[3 * k] = tiles; out[3 * k + 1] = (int64_t)(word & ((1ull << KSTEP_BITS) - 1)); out[3 * k + 2] = tiles * KSTEP_DENSE;
+    }
+    ++k;
+  };
+  for (int l = V.nlev - 1; l >= 1; --l)
+    for (int st = 0; st < V.lv[l].steps; ++st) put(C->kstep_coarse[l][st & 15]);
+  for (int t = 0; t < V.fine_steps; ++t) put(C->kstep_fine[t]);
+  *n = k;
+  return DISTR_OK;
+}
+
+int distr_debug_live_list(distr_ctx* ctx, const distr_render_cfg* cfg, const float* latent, const float* R, const float* T, int32_t step,
+                          int32_t* read, int32_t* left, int32_t cap, int32_t* nread, int32_t* nleft, int32_t* ordered, void* ws, size_t ws_bytes,
+                          void* stream) {
+  if (!ctx || !read || !left || !nread || !nleft || !ordered) return fail(ctx, DISTR_ERR_INVALID_ARG, "null argument");
+  EntryGuard guard_(ctx);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  View V;
+  (void)make_view(*cfg, ws, V, ctx->save_masks);
+  if (cfg->marcher == DISTR_MARCH_TRIVIAL || step < 0 || step + 1 >= V.fine_steps)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "step %d: a recursive marcher's step with a successor (full-resolution steps: %d)", step, V.fine_steps);
+  ctx->debug_steps = step + 1;
+  rc = render_forward_impl(ctx, cfg, 1, nullptr, latent, 0, R, T, nullptr, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, stream);
+  ctx->debug_steps = -1;
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const Consts* C;
+  if ((rc = read_consts(ctx, cfg, ws, s, V, &C))) return rc;
+  const int32_t c0 = C->cnt_live[step], c = C->cnt_live[step + 1];
+  if (c0 < 0 || c0 > V.P || c < 0 || c > V.P) return fail(ctx, DISTR_ERR_HIP, "live counts %d -> %d of step %d outside [0, %d]", c0, c, step, V.P);
+  *nread = c0; *nleft = c;
+  const int t32 = ctx->hybrid_threshold, t16 = (cfg->arith != DISTR_ARITH_F32) ? 0 : std::min(ctx->tail16_threshold, ctx->hybrid_threshold);
+  const int64_t prev = c0, N64 = pad_to(V.P, 64);
+  const bool host_on = ctx->live_order && !wide_decoder(ctx) && compact_tile(ctx, 2, cfg->arith) && N64 > ((t16 < t32) ? (int64_t)t32 + t16 : t32);
+  *ordered = (host_on && step_ordered(pad_to(prev, 16), pad_to(prev, 64), t16, t32)) ? 1 : 0;
+  // (the step read one of the two buffers and wrote the other: both lists are still there)
+  if (std::min(c0, cap) > 0) HIP_TRY(hipMemcpyAsync(read, V.live[step & 1], (size_t)std::min(c0, cap) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (std::min(c, cap) > 0) HIP_TRY(hipMemcpyAsync(left, V.live[(step + 1) & 1], (size_t)std::min(c, cap) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return DISTR_OK;
 }
 

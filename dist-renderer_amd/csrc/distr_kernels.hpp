@@ -52,7 +52,14 @@ struct Consts {
   // tail_sync[2k + 1] = THIS view's live rays entering step tail_from + k + 1 (= cnt_live of that step, kept next to the barrier word so
   // that one 8-byte load answers both "is the step over" and "how many rays does the next one have")
   alignas(8) int32_t tail_sync[2 * (MAX_STEPS + 2)];
+  // k-steps (one 16-row trip of a layer's k-loop, times the layer's output blocks per wave) the COMPACTED 64-ray forward tiles executed:
+  // low KSTEP_BITS bits = k-steps, the bits above = tiles (one 64-bit atomic per tile, kstep_count). [t]: full-resolution step t;
+  // kstep_coarse[l][t]: step t of pyramid level l. Statistics only (distr_get_kstep_stats); the dense count is tiles * KSTEP_DENSE.
+  alignas(8) unsigned long long kstep_fine[MAX_STEPS + 2];
+  unsigned long long kstep_coarse[MAX_LEVELS][16];
 };
+constexpr int KSTEP_BITS = 40;
+constexpr int HINT_ORDER_OFF = 16;   // k_finalize's hint words of one render configuration: [0] tail launch, [HINT_ORDER_OFF] end of the ordered steps
 
 struct LevelView {
   int32_t h, w, n, steps;
@@ -74,7 +81,13 @@ struct View {
   LevelView lv[MAX_LEVELS];
   int32_t nlev, P, fine_steps, pyramid;
   int32_t row0, rows, band;   // band: rows [row0, row0+rows) of cfg.H are rendered (band != 0: a proper sub-range)
+  int32_t order_until;        // host only: full-resolution steps from here on launch no k_live_pack and append atomically (fine_steps: none; k_finalize's hint)
+  int32_t blocks;             // the setup kernels enumerate pixels in 16 x 16 blocks of 8 x 8 sub-blocks (block_pixel); 0: strips of 256 pixels
   int32_t* live[2];
+  // ordered live list (step_ordered): a tile of a step writes the rays that stay live to lslot[base + rank] (base = the tile's first
+  // position in the list it read) and their number, per 16 positions, to tcount[base / 16 ..]; k_live_pack closes the gaps
+  int32_t* lslot;                // [P + 64]
+  int32_t* tcount;               // [P / 16 + 4]
   float *m, *init_now, *maxbound, *minabs, *first_sdf;
   float *tk_s, *tk_zb, *tk_za;   // [bs][P] selected rows: sdf, depth before, depth after (pyramid) / marching depth after
   int32_t* tk_src;               // [bs][P] row source (see src_* helpers) or -1 for a padded row
@@ -116,7 +129,7 @@ __device__ __forceinline__ View view_at(const View& V0, int b) {
     adv(V.lv[l].valid, d); adv(V.lv[l].list, d); adv(V.lv[l].cinit, d); adv(V.lv[l].cm, d);
     adv(V.lv[l].rs, d); adv(V.lv[l].rzb, d); adv(V.lv[l].rza, d);
   }
-  adv(V.live[0], d); adv(V.live[1], d);
+  adv(V.live[0], d); adv(V.live[1], d); adv(V.lslot, d); adv(V.tcount, d);
   adv(V.m, d); adv(V.init_now, d); adv(V.maxbound, d); adv(V.minabs, d); adv(V.first_sdf, d);
   adv(V.tk_s, d); adv(V.tk_zb, d); adv(V.tk_za, d); adv(V.tk_src, d); adv(V.tk_slot, d); adv(V.tclaim, d);
   adv(V.mstore, d);
@@ -315,6 +328,26 @@ __device__ __forceinline__ void block_append(bool flag, int32_t id, int32_t* lis
   if (flag) list[base + ballot_rank(ball)] = id;
 }
 
+// Enumeration of a w x h pixel grid by the setup kernels (k_setup_level, k_fine_init): a workgroup of 256 threads covers a 16 x 16 pixel
+// block, each wavefront one 8 x 8 sub-block (row-major inside), the blocks tile the grid row-major. block_append keeps the thread order, so
+// every 64 consecutive entries of a list that a workgroup appends are the live pixels of compact image patches: the rays of a 64-ray tile
+// then share most of their live hidden units (compacted tile), which a 64-pixel strip of one image row does not. Returns the pixel index
+// y * w + x or -1 (outside the grid: no ray). Shared with the host (grid size, distr_block_pixel).
+__host__ __device__ inline int32_t block_grid(int32_t w, int32_t h) { return (w <= 0 || h <= 0) ? 0 : ((w + 15) / 16) * ((h + 15) / 16); }
+__host__ __device__ inline int32_t block_pixel(int32_t w, int32_t h, int32_t block, int32_t thread) {
+  const int32_t bpr = (w + 15) / 16;
+  const int32_t wave = thread >> 6, lane = thread & 63;
+  const int32_t x = (block % bpr) * 16 + (wave & 1) * 8 + (lane & 7);
+  const int32_t y = (block / bpr) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  return (x < w && y < h) ? y * w + x : -1;
+}
+// pixel of this thread in a setup kernel over an n = w x h grid: by blocks (View::blocks) or, DISTR_RAY_BLOCKS=0, by strips of 256 pixels
+__device__ __forceinline__ int32_t setup_pixel(int blocks, int32_t w, int32_t h) {
+  if (blocks) return block_pixel(w, h, (int32_t)blockIdx.x, (int32_t)threadIdx.x);
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  return (i < w * h) ? i : -1;
+}
+
 // after the LAST full-resolution step (step + 1 == fine_steps): one lane of a wave with a ray that stays live records that the march did
 // not break there (Consts::live_end, read by early_dup). Called by the whole wave, by every path that evaluates a fine step
 __device__ __forceinline__ void mark_live_end(Consts* C, bool stay, int step, int fine_steps) {
@@ -354,7 +387,8 @@ DISTR_GLOBAL void __launch_bounds__(256) k_prep(View V0, DecoderDev D, const flo
   if (blockIdx.x == 0) {
     const int t = threadIdx.x;
     for (int k = t; k < D.nlat; k += 256) C->latent[k] = latent[k];
-    for (int i = t; i < MAX_STEPS + 2; i += 256) { C->cnt_live[i] = 0; C->cnt_sticky[i] = 0; C->tail_sync[2 * i] = 0; C->tail_sync[2 * i + 1] = 0; }
+    for (int i = t; i < MAX_STEPS + 2; i += 256) { C->cnt_live[i] = 0; C->cnt_sticky[i] = 0; C->tail_sync[2 * i] = 0; C->tail_sync[2 * i + 1] = 0; C->kstep_fine[i] = 0ull; }
+    if (t < MAX_LEVELS * 16) C->kstep_coarse[t >> 4][t & 15] = 0ull;
     for (int i = t; i < PSTRIDE; i += 256) C->red[i] = 0.f;
     if (t < 12) C->cam_acc[t] = 0.f;
     if (t < MAX_LEVELS) { C->maxinit_bits[t] = 0u; C->cnt_level[t] = 0; }
@@ -413,12 +447,12 @@ DISTR_GLOBAL void __launch_bounds__(256) k_setup_level(View V0, int lvl) {
   const View V = view_at(V0, blockIdx.y);
   const LevelView L = level_sel(V, lvl);
   Consts* C = V.C;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = setup_pixel(V.blocks, L.w, L.h);
   const CamRegs cam = load_cam(C);
   const bool inside = cam.cdist < V.cfg.radius;
   bool valid = false;
   uint32_t mx = 0u;
-  if (i < L.n) {
+  if (i >= 0) {
     float px, py;
     level_center(L, i, px, py);
     const RayGeo g = make_ray(V.cfg.K_inv, cam.R, px, py);
@@ -637,10 +671,10 @@ DISTR_GLOBAL void __launch_bounds__(256) k_fine_init(View V0) {
   const View V = view_at(V0, blockIdx.y);
   const LevelView& L0 = V.lv[0];
   Consts* C = V.C;
-  const int px = blockIdx.x * 256 + threadIdx.x;
+  const int px = setup_pixel(V.blocks, L0.w, L0.h);
   bool live = false;
-  if (px < V.P / 16 + 2) V.tclaim[px] = 0;
-  if (px < V.P && L0.valid[px]) {
+  { const int t = blockIdx.x * 256 + threadIdx.x; if (t < V.P / 16 + 2) V.tclaim[t] = 0; }    // (by thread, not by pixel: one word per 16-ray tile)
+  if (px >= 0 && L0.valid[px]) {
     const CamRegs cam = load_cam(C);
     float cx, cy;
     level_center(L0, px, cx, cy);
@@ -704,7 +738,7 @@ enum { MODE_EVAL = 0, MODE_COARSE = 1, MODE_FINE = 2 };
 //     else                       one more round of 64-ray tiles (362 us).
 // Every role of the step evaluates this on the device-side counts; the host never needs to know them. (Host invariants,
 // distr_create: 16 <= t16 <= t32, t16 + t32 < 16384, both multiples of 64.)
-__device__ __forceinline__ void fine_split(int64_t n16, int64_t n64, int t16, int t32, int which, int64_t& lo, int64_t& hi, int& g) {
+__host__ __device__ inline void fine_split(int64_t n16, int64_t n64, int t16, int t32, int which, int64_t& lo, int64_t& hi, int& g) {
   if (n16 <= t16) { g = 16; lo = 0; hi = (which == 16) ? n16 : 0; return; }
   g = 64;
   const int64_t count = n64;
@@ -719,6 +753,36 @@ __device__ __forceinline__ void fine_split(int64_t n16, int64_t n64, int t16, in
   if (which == 64) { lo = 0; hi = big ? count : full; }
   else if (which == 32) { lo = full; hi = big ? full : cut; }
   else { lo = big ? count : cut; hi = count; }
+}
+
+// A step keeps its live list in ORDER when its 64-ray role has work (whole rounds, or a big remainder): the compacted 64-ray tile of the
+// next step walks the union of its rays' live hidden units, and rays that are neighbours in the image share most of them. Such a step's
+// tiles -- of all three sizes -- leave their survivors in slots (slot_append) and k_live_pack builds the next list from them; every other
+// step appends atomically, in completion order (wave_append). Every role and k_live_pack evaluate this on the same device-side counts.
+__host__ __device__ inline bool step_ordered(int64_t n16, int64_t n64, int t16, int t32) {
+  int64_t lo, hi;
+  int g;
+  fine_split(n16, n64, t16, t32, 64, lo, hi, g);
+  return hi > lo;
+}
+
+// a tile's survivors of an ordered step: ray `id` of every flagged lane to lslot[base + rank], in lane order (base = the tile's first
+// position in its view's list, a multiple of TILE), and per 16 positions how many of them hold a ray (the first n of the tile's TILE
+// positions do). Called by the whole wavefront; a tile without survivors still writes its zeros.
+template <int TILE>
+__device__ __forceinline__ void slot_append(bool flag, int32_t id, const View& V, int64_t base) {
+  const unsigned long long ball = __ballot(flag);
+  const int lane = threadIdx.x & 63;
+  const int n = __popcll(ball);
+  if (flag) V.lslot[base + ballot_rank(ball)] = id;
+  if (lane < TILE / 16) V.tcount[base / 16 + lane] = min(max(n - 16 * lane, 0), 16);
+}
+
+// one compacted 64-ray tile of level `lvl`, step `step` executed `ksteps` k-steps (Consts::kstep_fine / kstep_coarse); one lane, one atomic
+__device__ __forceinline__ void kstep_count(Consts* C, int lvl, int step, uint32_t ksteps) {
+  if (threadIdx.x != 0) return;
+  unsigned long long* p = (lvl == 0) ? &C->kstep_fine[step] : &C->kstep_coarse[lvl][step & 15];
+  atomicAdd(p, (1ull << KSTEP_BITS) | (unsigned long long)ksteps);
 }
 
 struct MarchArgs {
@@ -737,6 +801,7 @@ struct MarchArgs {
   DecoderSplit planes[2];    // [ARITH - 1]: split-bf16 / split-f16 weight planes (kernels instantiated with ARITH = 1 / 2, distr_render_cfg.arith)
   int32_t tail_absent;       // tests (DISTR_TAIL_TEST_ABSENT=n): workgroups 0 .. n-1 of k_tail leave at once, as if they never became resident
   const SegTable* seg;       // MODE_EVAL on 64-point tiles: segmented list (c0c4 = [segments][1024], n unused); null: one code, n points
+  int32_t live_order;        // k_step: steps with 64-ray rounds keep the live list in order (step_ordered, k_live_pack); 0: every step appends atomically
 };
 
 // One pyramid level of view b, read from the kernel-argument segment (MarchArgs is the first argument of every march kernel): a scalar
@@ -772,6 +837,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   const int B = (MODE == MODE_EVAL) ? 1 : V0.nviews;
   const bool split = MODE == MODE_FINE && V0.cfg.marcher != DISTR_MARCH_TRIVIAL;
   bool origin = false;
+  bool ordered = false;      // MODE_FINE: the step keeps its live list in order (step_ordered): survivors go to the tile's slots, k_live_pack follows
   int vb = 0;
   int64_t base = (int64_t)tile * TILE, count = 0;
   int seg = 0;               // MODE_EVAL: this tile's segment and the segment's first point (a plain list: 0, 0)
@@ -797,6 +863,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
       const int32_t i16 = vprefix(c, B, 16), i64 = vprefix(c, B, 64);
       fine_split(vtotal(i16, B), vtotal(i64, B), A.t16, A.t32, which, lo, hi, g);
       incl = (g == 16) ? i16 : i64;
+      ordered = A.live_order && step_ordered(vtotal(i16, B), vtotal(i64, B), A.t16, A.t32);
     } else {
       incl = vprefix(c, B, TILE);
       hi = vtotal(incl, B);
@@ -851,8 +918,11 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
 
   uint32_t masks[8][4];
   float pre;
-  if constexpr (ARITH == 0) pre = mlp_forward<RB, KEEP, false, true, WIDE, COMPACT>(D, c0, c4, S, masks);
-  else pre = split_forward<SplitFmt<ARITH>, RB, KEEP>(D, A.planes[ARITH - 1], c0, c4, S, masks);
+  if constexpr (ARITH == 0) {
+    uint32_t ksteps = 0u;
+    pre = mlp_forward<RB, KEEP, false, true, WIDE, COMPACT>(D, c0, c4, S, masks, 8, nullptr, COMPACT ? &ksteps : nullptr);
+    if constexpr (COMPACT && MODE != MODE_EVAL) { if (!origin) kstep_count(V.C, MODE == MODE_COARSE ? A.lvl : 0, A.step, ksteps); }
+  } else pre = split_forward<SplitFmt<ARITH>, RB, KEEP>(D, A.planes[ARITH - 1], c0, c4, S, masks);
 
   // epilogue: wave 0 (kept whole for the ballot), lane = ray of the tile; lanes >= TILE are invalid
   int64_t mblock = -1;   // mask block this ray's row goes to (KEEP), -1: row not kept
@@ -894,7 +964,8 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
           stay = (za < st.maxbound) && (a >= V.cfg.threshold);
         }
         if (V.cfg.marcher != DISTR_MARCH_TRIVIAL) {
-          wave_append(stay, id, live_sel(V, A.step + 1), &V.C->cnt_live[A.step + 1]);
+          if (ordered) slot_append<TILE>(stay, id, V, base);
+          else wave_append(stay, id, live_sel(V, A.step + 1), &V.C->cnt_live[A.step + 1]);
           mark_live_end(V.C, stay, A.step, V.fine_steps);
         }
       }
@@ -1165,6 +1236,7 @@ struct Tile16 {
                                 // evaluation and looked at before anything is written or a cluster gets its `go`)
   int32_t* count2;              // k_tail: second counter of the rays that stay live (Consts::tail_sync), else null
   int32_t step;                 // MODE_FINE / MODE_COARSE: the march step (of the level) this tile evaluates (a launch: MarchArgs::step)
+  bool ordered;                 // MODE_FINE, a launch only: the step keeps its live list in order (step_ordered) -- survivors go to the tile's slots
 };
 
 // TAIL (k_tail): write-through mask stores of the cluster members (store_own_mask_words), sticky tiles never hand rays back.
@@ -1332,7 +1404,8 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
         if (t.step == 0) Ve.first_sdf[(uint32_t)id] = s;
         stay = (za < sr.maxbound) && (a >= Ve.cfg.threshold);
       }
-      wave_append<false>(stay, id, live_sel(Ve, t.step + 1), &Ve.C->cnt_live[t.step + 1], TAIL ? t.count2 : nullptr);
+      if (!TAIL && t.ordered) slot_append<TILE>(stay, id, Ve, base);
+      else wave_append<false>(stay, id, live_sel(Ve, t.step + 1), &Ve.C->cnt_live[t.step + 1], TAIL ? t.count2 : nullptr);
       mark_live_end(Ve.C, stay, t.step, Ve.fine_steps);
     }
   }
@@ -1367,6 +1440,7 @@ __device__ __forceinline__ void march_tile16(const MarchArgs& A, const DecoderDe
   int64_t lo = 0, hi;
   int gran = TILE;
   int32_t c = 0, incl = 0;
+  bool ordered = false;
   if (MODE == MODE_EVAL) {
     hi = A.n;
   } else {
@@ -1376,6 +1450,7 @@ __device__ __forceinline__ void march_tile16(const MarchArgs& A, const DecoderDe
       const int32_t i16 = vprefix(c, B, 16), i64 = vprefix(c, B, 64);
       fine_split(vtotal(i16, B), vtotal(i64, B), A.t16, A.t32, 16, lo, hi, gran);
       incl = (gran == 16) ? i16 : i64;
+      ordered = A.live_order && step_ordered(vtotal(i16, B), vtotal(i64, B), A.t16, A.t32);
     } else {
       incl = vprefix(c, B, TILE);
       hi = vtotal(incl, B);
@@ -1433,7 +1508,7 @@ __device__ __forceinline__ void march_tile16(const MarchArgs& A, const DecoderDe
   }
   Tile16 t;
   t.tile = tile; t.member = member; t.cl = cl; t.vb = vb; t.origin = origin; t.sticky = sticky_launch; t.solo = false; t.base = base; t.count = count;
-  t.lost = 0; t.count2 = nullptr; t.step = A.step;
+  t.lost = 0; t.count2 = nullptr; t.step = A.step; t.ordered = ordered;
   tile16_run<MODE, KEEP, SM>(A, D, D16, S, t, A.xc);
 }
 
@@ -1521,7 +1596,7 @@ __device__ __forceinline__ void tail_slot(const MarchArgs& A, const DecoderDev& 
   const int tid = threadIdx.x;
   const bool lead = member == cl_lead(cl);
   Tile16 t;
-  t.tile = (int)vt; t.member = member; t.cl = cl; t.vb = 0; t.base = 0; t.count = 0; t.lost = 0; t.step = A.step + k;
+  t.tile = (int)vt; t.member = member; t.cl = cl; t.vb = 0; t.base = 0; t.count = 0; t.lost = 0; t.step = A.step + k; t.ordered = false;
   t.origin = vt >= P.ntiles;
   t.sticky = sticky; t.solo = sticky && cl == 1;
   if (t.solo) t.member = cl_lead(8);          // (sticky_tile16 is written for 8 members: alone = as their lead)
@@ -1719,6 +1794,50 @@ __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, Deco
   }
 }
 
+// Behind an ORDERED step (step_ordered; every other step: nothing to do, the workgroups leave): the next step's live list = the slots the
+// step's tiles filled, gaps closed, in the order of the list the step read -- a stream compaction whose flags the tiles have already
+// reduced to one count per 16 positions. Grid (ceil(P / 4096), nviews): a workgroup owns 256 counts = 4096 positions of its view; it sums
+// the counts in front of its range itself (at most P / 16 words from the L2: nobody waits for anybody), scans its own and copies. The
+// workgroup that owns the view's last count writes cnt_live[step + 1].
+constexpr int PACK_CHUNKS = 256;
+DISTR_GLOBAL void __launch_bounds__(256) k_live_pack(View V0, int step, int t16, int t32) {
+  __shared__ int32_t s_wave[4], s_scan[PACK_CHUNKS];
+  const int B = V0.nviews, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t call = vload(&V0.C->cnt_live[step], V0.vstride, B);
+  if (!step_ordered(vtotal(vprefix(call, B, 16), B), vtotal(vprefix(call, B, 64), B), t16, t32)) return;
+  const View V = view_at(V0, blockIdx.y);
+  const int32_t c = V.C->cnt_live[step];
+  const int nchunks = (c + 15) / 16, first = blockIdx.x * PACK_CHUNKS;
+  if (first >= nchunks) return;
+  // rays in front of this workgroup's range
+  int32_t before = 0;
+  for (int j = tid; j < first; j += 256) before += V.tcount[j];
+  const int j = first + tid;
+  const int32_t own = (j < nchunks) ? V.tcount[j] : 0;
+  int32_t incl = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int32_t t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) before += __shfl_xor(before, o);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int32_t excl = incl - own;
+  for (int w = 0; w < wave; ++w) excl += s_wave[w];
+  const int32_t mine = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  __syncthreads();
+  if (lane == 0) s_wave[wave] = before;
+  s_scan[tid] = excl;
+  __syncthreads();
+  const int32_t start = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  int32_t* dst = live_sel(V, step + 1);
+  for (int i = tid; i < PACK_CHUNKS * 16; i += 256) {
+    const int cj = first + (i >> 4);
+    if (cj >= nchunks) break;
+    if ((i & 15) < V.tcount[cj]) dst[start + s_scan[i >> 4] + (i & 15)] = V.lslot[(size_t)first * 16 + i];
+  }
+  if (first + PACK_CHUNKS >= nchunks && tid == 0) V.C->cnt_live[step + 1] = start + mine;
+}
+
 // decode_color (core/utils/decoder_utils.py:94-112) for the surface points of SDFRenderer_color.render_color
 // (core/sdfrenderer/renderer_rgb.py:20-38): the same fused tile on the colour decoder's weights (latent = shape code |
 // colour code, folded into c0 / c4), lin8 with three rows, tanh on each. Forward only.
@@ -1844,21 +1963,31 @@ __global__ void __launch_bounds__(256, (RB == 1) ? 2 : 1) k_debug_layer(const fl
 // hint_out (host-mapped word, may be null): the first full-resolution step of THIS render that had at most tail_rays live rays over all
 // views (fine_steps: none) -- where the next render of the same configuration lets the persistent tail launch take over (k_tail; the
 // host reads the word without synchronising: a stale or missing value costs time, never rays).
-DISTR_GLOBAL void __launch_bounds__(256) k_finalize(View V0, float* zdepth, uint8_t* mask, float* min_sdf, float* depth, int32_t* hint_out, int32_t tail_rays) {
+// hint_out[HINT_ORDER_OFF] likewise: the first full-resolution step of this render whose counts did NOT ask for an ordered live list
+// (step_ordered; fine_steps: none) -- behind it the next render launches no k_live_pack and its steps append atomically (a stale value costs
+// time or order, never rays: a step is ordered only where the host also launches the pack, MarchArgs::live_order).
+DISTR_GLOBAL void __launch_bounds__(256) k_finalize(View V0, float* zdepth, uint8_t* mask, float* min_sdf, float* depth, int32_t* hint_out, int32_t tail_rays,
+                                                  int32_t t16, int32_t t32) {
   if (hint_out && blockIdx.x == 0 && blockIdx.y == 0 && V0.cfg.marcher != DISTR_MARCH_TRIVIAL) {
-    __shared__ int32_t s_first;
-    if (threadIdx.x == 0) s_first = V0.fine_steps;
+    __shared__ int32_t s_first, s_order;
+    if (threadIdx.x == 0) { s_first = V0.fine_steps; s_order = V0.fine_steps; }
     __syncthreads();
-    for (int t = threadIdx.x; t < V0.fine_steps; t += 256) {
-      int64_t tot = 0;
+    bool tail_seen = false, order_seen = false;
+    for (int t = threadIdx.x; t < V0.fine_steps && !(tail_seen && order_seen); t += 256) {
+      int64_t tot = 0, n16 = 0, n64 = 0;
       for (int b = 0; b < V0.nviews; ++b) {
         const Consts* Cb = reinterpret_cast<const Consts*>(reinterpret_cast<const char*>(V0.C) + (int64_t)b * V0.vstride);
         tot += Cb->cnt_live[t] + Cb->cnt_sticky[t];
+        n16 += vpad(Cb->cnt_live[t], 16); n64 += vpad(Cb->cnt_live[t], 64);
       }
-      if (tot <= tail_rays) { atomicMin(&s_first, t); break; }     // (a thread's steps ascend: its first hit is its smallest)
+      if (!tail_seen && tot <= tail_rays) { atomicMin(&s_first, t); tail_seen = true; }     // (a thread's steps ascend: its first hit is its smallest)
+      if (!order_seen && !step_ordered(n16, n64, t16, t32)) { atomicMin(&s_order, t); order_seen = true; }
     }
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(hint_out, s_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(hint_out, s_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(hint_out + HINT_ORDER_OFF, s_order, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
   const View V = view_at(V0, blockIdx.y);
   {

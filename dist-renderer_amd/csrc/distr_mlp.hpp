@@ -617,6 +617,15 @@ struct Chain {
   static constexpr int KT(int l) { return 128 * NOB(l); }                     // lin_l^T: delta_l -> delta_{l-1}
   static constexpr int NOBT(int l) { return (l < 1) ? 0 : K(l) / 128; }
 };
+// k-steps of layers 1..7 of a DENSE 64-ray tile of the narrow layout, weighted like mlp_forward's `ksteps` (16 rows per k-step, times the
+// layer's output blocks per wave): what a compacted tile's count is set against
+constexpr int kstep_dense() {
+  int n = 0;
+  for (int l = 1; l < 8; ++l) n += Chain<false>::K(l) / 16 * Chain<false>::NOB(l);
+  return n;
+}
+constexpr int KSTEP_DENSE = kstep_dense();
+static_assert(KSTEP_DENSE == 768, "5 layers of 32 x 4, lin3 32 x 2, lin4 16 x 4");
 
 // ---------------------------------------------------------------------------------------- forward tile
 // Preconditions: S.xyz rows 0..2 hold the TILE points (x row, y row, z row), visible to all threads (barrier done).
@@ -648,8 +657,11 @@ __device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float
 template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false, bool COMPACT = false>
 __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* __restrict__ c0,
                                              const float* __restrict__ c4, Smem<RB>& S, uint32_t (&masks)[8][4],
-                                             int stop = 8, long long* ts = nullptr) {
+                                             int stop = 8, long long* ts = nullptr, uint32_t* ksteps = nullptr) {
   constexpr int TILE = 32 * RB;
+  // ksteps (COMPACT only, may be null): receives the k-steps layers 1..7 executed for this tile, weighted by the layer's output blocks
+  // per wave (wave-uniform; the dense tile's figure is KSTEP_DENSE)
+  uint32_t kdone = 0u;
   // test builds: shader-clock / wall-clock stamps of wave 0 at phase boundaries (ts[2i], ts[2i+1])
 #define DISTR_TS(i) do { if (DEBUG_STOP && ts && threadIdx.x == 0) { ts[2 * (i)] = (long long)__builtin_readcyclecounter(); ts[2 * (i) + 1] = (long long)wall_clock64(); } } while (0)
   DISTR_TS(0);
@@ -717,8 +729,10 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     const int row0 = wave * (32 * NOB);     // the wave's first output row
     f32x16 acc[NOB][RB];
     if constexpr (COMPACT) {
+      const uint32_t trips = compact_trips(npad, K);      // (trips + 1 k-steps of 16 rows)
+      kdone += (trips + 1u) * (uint32_t)NOB;
       dense_asm_compact<NOB, true>(acc, xaddr, kaddr, (uint32_t)(lane & 31) * (4 * NOB), kmajor_rsrc(D.Wk + wk_offset(l), 512 * NOB, K),
-                                   (uint32_t)wave * (128 * NOB), compact_trips(npad, K), bias0 + l * 2048 + (uint32_t)wave * (128 * NOB));
+                                   (uint32_t)wave * (128 * NOB), trips, bias0 + l * 2048 + (uint32_t)wave * (128 * NOB));
     } else if constexpr (RB == 2) {
       dense_asm<K, NOB, NOBN, true>(acc, wpre, xaddr, voff, rs[l], rs[LN], (uint32_t)wave * (1024 * NOB),
                                     (uint32_t)wave * (1024 * (NOBN ? NOBN : NOB)), bias0 + l * 2048 + (uint32_t)wave * (128 * NOB), scratch);
@@ -746,6 +760,7 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
     if (DEBUG_STOP && stop == l) stopped = true;
   });
   if (DEBUG_STOP && stopped) return 0.f;
+  if (COMPACT && ksteps) *ksteps = kdone;
   const float pre = lin8_row<RB>(D.w8, D.b8, S);
   DISTR_TS(17);
 #undef DISTR_TS

@@ -44,6 +44,8 @@ COLOR_BATCH_EXPORTS = ['distr_color_multi_workspace_bytes', 'distr_color_backwar
 TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset', 'distr_train_segment_row', 'distr_train_slab_plan',
                  'distr_train_forward', 'distr_train_backward', 'distr_train_forward_dropout', 'distr_train_backward_dropout',
                  'distr_train_dropout_keep']
+# the ordered live list seen from outside (include/distr_live_order.h, included by distr.h): block enumeration, k-step counts, list read-back
+LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -164,7 +166,7 @@ class RenderStats(_Sized):
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_split.hpp', 'distr_losses.hpp',
            'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp', 'distr_philox.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h')                    # include/: the C ABI
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h', 'distr_live_order.h')                    # include/: the C ABI
 INST_GROUPS = 10           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -404,6 +406,13 @@ def lib():
                                                            fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
             L.distr_color_relight.argtypes = [vp, C.POINTER(RenderCfg), i32, fp, fp, fp, u8p, fp, fp, lights, fp, vp]
             tw, tg = C.POINTER(TrainWeights), C.POINTER(TrainGrads)
+            L.distr_block_grid.argtypes = [i32, i32]
+            L.distr_block_grid.restype = i32
+            L.distr_block_pixel.argtypes = [i32, i32, i32, i32]
+            L.distr_block_pixel.restype = i32
+            L.distr_get_kstep_stats.argtypes = [vp, C.POINTER(RenderCfg), vp, i64p, i32, C.POINTER(C.c_int32), vp]
+            i32p = C.POINTER(C.c_int32)
+            L.distr_debug_live_list.argtypes = [vp, C.POINTER(RenderCfg), fp, fp, fp, i32, i32p, i32p, i32, i32p, i32p, i32p, vp, C.c_size_t, vp]
             L.distr_train_workspace_bytes.argtypes = [i32, i32, i64p]
             L.distr_train_workspace_bytes.restype = C.c_size_t
             L.distr_train_activation_offset.argtypes = [i32, i32, i64p, i32]
@@ -566,10 +575,31 @@ class Context(object):
         self.check(self.L.distr_get_live_counts(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), buf, cap, C.byref(n), self.stream()))
         return [buf[i] for i in range(min(cap, n.value))]
 
-    def render_stats(self, cfg, ws):
+    def render_stats(self, cfg, ws, ksteps=False):
+        """Counters of the forward that used `ws`. ksteps=True adds 'ksteps': per march launch (the order of live_counts) a tuple
+        (tiles, k-steps executed, k-steps of as many dense tiles) of the compacted 64-ray forward tiles (distr_get_kstep_stats)."""
         st = RenderStats()
         self.check(self.L.distr_get_render_stats(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), C.byref(st), self.stream()))
-        return {k: getattr(st, k) for k, _ in RenderStats._fields_ if k not in ('struct_size', 'reserved')}
+        out = {k: getattr(st, k) for k, _ in RenderStats._fields_ if k not in ('struct_size', 'reserved')}
+        if ksteps:
+            cap = 4096
+            buf, n = (C.c_int64 * (3 * cap))(), C.c_int32()
+            self.check(self.L.distr_get_kstep_stats(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), buf, cap, C.byref(n), self.stream()))
+            out['ksteps'] = [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(min(cap, n.value))]
+        return out
+
+    def debug_live_list(self, cfg, latent, R, T, step, ws):
+        """Test only: (read, left, ordered) -- the live lists full-resolution step `step` read and left for its successor (pixel indices,
+        numpy int32) and whether the step kept the list in order. Renders one view up to that step into the forward workspace `ws`."""
+        import numpy as np
+        cap = int(cfg.band_rows) * int(cfg.W)
+        a, b = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        na, nb, o = C.c_int32(), C.c_int32(), C.c_int32()
+        i32p = C.POINTER(C.c_int32)
+        self.check(self.L.distr_debug_live_list(self.h, C.byref(cfg), ptr(latent), ptr(R), ptr(T), int(step), a.ctypes.data_as(i32p),
+                                                b.ctypes.data_as(i32p), cap, C.byref(na), C.byref(nb), C.byref(o),
+                                                C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(), self.stream()))
+        return a[:na.value].copy(), b[:nb.value].copy(), bool(o.value)
 
 
 def ptr(t):

@@ -377,5 +377,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_color_batch.h"
 /* the layer-wise decoder path: decode_sdf with gradients to the decoder's weights */
 #include "distr_train.h"
+/* the ordered live list of the full-resolution march seen from outside: block enumeration, k-step counts, list read-back */
+#include "distr_live_order.h"
 
 #endif /* DISTR_H_ */
