@@ -9,7 +9,7 @@
 //     (decoder evaluation on the whole list: k_march<eval>, distr_api.hip)
 //   5 k_samp_epilogue SURFACE: f(p + o) - eta, f(p - o) + eta, in place
 //   backward (after the point-list backward, k_bwd<pointgrad>, has written g_xyz):
-//   6 k_samp_cam_bwd  per valid pixel: g_xyz of its points pulled back through M^T, the ray normalisation and R^T h; 12 sums per block
+//   6 k_samp_cam_bwd  per valid pixel: g_xyz of its points pulled back through M^T, the ray normalisation and R^T h (float64); 12 sums per block
 //   7 k_samp_cam_fin  per view: the block sums in block order, then g_R = ray part - T (x) g_c, g_T = -R g_c
 //
 // Positions come from scans in a fixed order and sums from fixed trees (per-thread serial run -> LDS tree -> block order): no atomics,
@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "distr_kernels.hpp"    // make_ray, make_point, ray_backward_acc
+#include "distr_kernels.hpp"    // make_ray, make_point
 #include "distr_mesh.hpp"       // block_excl_scan, MB / MPER / MTILE
 
 namespace distr {
@@ -180,8 +180,25 @@ __device__ __forceinline__ Cam12 block_sum12(Cam12 x, float* lds /*[MB]*/) {
   return r;
 }
 
+// make_ray for the camera pull-back, in float64: h = K^-1 (x, y, 1), r = R^T h, |r|, calib = h_z / (|h| + 1e-12)
+struct Ray64 { double h[3], r[3], rn, calib; };
+__device__ __forceinline__ Ray64 make_ray64(const Geo& G, const float* RT, int pix) {
+  Ray64 g;
+  const double px = (double)(pix % G.W), py = (double)(pix / G.W);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) g.h[a] = (double)G.Ki[a * 3 + 0] * px + (double)G.Ki[a * 3 + 1] * py + (double)G.Ki[a * 3 + 2];
+  g.calib = g.h[2] / (sqrt(g.h[0] * g.h[0] + g.h[1] * g.h[1] + g.h[2] * g.h[2]) + 1e-12);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) g.r[i] = (double)RT[0 * 4 + i] * g.h[0] + (double)RT[1 * 4 + i] * g.h[1] + (double)RT[2 * 4 + i] * g.h[2];
+  g.rn = sqrt(g.r[0] * g.r[0] + g.r[1] * g.r[1] + g.r[2] * g.r[2]);
+  return g;
+}
+
 // grid (blocks of MTILE valid pixels, views): part[v][block][12]. Point p = M^T q, q = d z + c: g_q = M g_p, g_d = sum_k z_k g_q_k,
 // g_c = sum_k g_q_k (z_k = zdepth, or zdepth * ratio_k; the +-offset of SURFACE does not depend on the camera).
+// A pixel's own twelve terms are formed in float64 and rounded once: g_r = g_d / e - (g_d . r) r / (rn e^2) takes the part of g_d along the
+// ray away component by component, and g_d sums list entries whose upstream gradients differ in sign; in float32 the roundings of the
+// parts are not small against what is left (a view with ONE valid pixel was up to 3e-4 off in an entry). The sums stay float32.
 DISTR_GLOBAL void __launch_bounds__(MB) k_samp_cam_bwd(const Geo G, const Views VW, const int* __restrict__ index, const float* __restrict__ RT,
                                                        const float* __restrict__ depth, const float* __restrict__ draws,
                                                        const float* __restrict__ g_xyz, int nblk, float* __restrict__ part) {
@@ -196,21 +213,29 @@ DISTR_GLOBAL void __launch_bounds__(MB) k_samp_cam_bwd(const Geo G, const Views 
   for (int q = 0; q < MPER && base + q < N; ++q) {
     const int i = base + q;
     const int pix = valid_pixel(G, index[(size_t)v * G.P + i]);
-    const PixelGeo pg = pixel_geo(G, RT + 12 * v, depth + (size_t)v * G.P, pix);
-    float gd[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f};
+    const Ray64 g = make_ray64(G, RT + 12 * v, pix);
+    const double z = (double)depth[(size_t)v * G.P + pix] / g.calib;
+    double gd[3] = {0.0, 0.0, 0.0}, gc[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < G.m; ++k) {
       const float* gp = gx + 3 * ((int64_t)k * N + i);
-      const float zk = G.mode == MODE_SURFACE ? pg.z : pg.z * draws[(int64_t)G.m * off + (int64_t)k * N + i];
+      const double zk = G.mode == MODE_SURFACE ? z : z * (double)draws[(int64_t)G.m * off + (int64_t)k * N + i];
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const float gq = G.M[j * 3 + 0] * gp[0] + G.M[j * 3 + 1] * gp[1] + G.M[j * 3 + 2] * gp[2];
+        const double gq = (double)G.M[j * 3 + 0] * gp[0] + (double)G.M[j * 3 + 1] * gp[1] + (double)G.M[j * 3 + 2] * gp[2];
         gd[j] += gq * zk;
         gc[j] += gq;
       }
     }
-    ray_backward_acc(pg.g, gd, acc.a);
+    const double e = g.rn + 1e-12;
+    const double dot = gd[0] * g.r[0] + gd[1] * g.r[1] + gd[2] * g.r[2];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) acc.a[9 + j] += gc[j];
+    for (int c = 0; c < 3; ++c) {
+      const double gr = gd[c] / e - (g.rn > 0.0 ? dot * g.r[c] / (g.rn * e * e) : 0.0);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc.a[j * 3 + c] += (float)(g.h[j] * gr);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc.a[9 + j] += (float)gc[j];
   }
   const Cam12 tot = block_sum12(acc, lds);
   if (threadIdx.x < 12) {

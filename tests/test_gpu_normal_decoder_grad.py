@@ -150,6 +150,7 @@ def test_term_matches_closed_form_at_every_list_size(engine, fixture_decoder, de
     a = render(engine, cfg, latent, Rs, Ts, wn, option=True)
     counts = [int(a['mask'][v].sum()) for v in range(4)]
     print('valid pixels per view:', counts)
+    assert max(counts) > 2048, ('no view spans two blocks of the camera sums (2048 valid pixels each)', counts)
     for name, lo, hi in SIZE_CLASSES:
         assert any(lo <= c <= hi for c in counts), (name, counts)
     bad = []
