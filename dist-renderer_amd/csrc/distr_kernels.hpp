@@ -46,8 +46,8 @@ struct Consts {
   int32_t live_end;       // != 0: a ray is still live after the LAST full-resolution step (set by whichever tile evaluated it: mark_live_end).
                           // cnt_live[fine_steps] cannot say so: a sticky tile keeps its rays and appends to no list (early_dup)
   // persistent tail kernel (k_tail): fine steps [tail_from, fine_steps) run inside ONE launch (tail_from = fine_steps: no tail launch).
-    int32_t tail_from;
-  int32_t tail_steals;    // tiles a workgroup other than their owner evaluated after waiting too long (owner not resident); statistics
+  int32_t tail_from;
+  int32_t tail_steals;   // tiles a workgroup other than their owner evaluated after waiting too long (owner not resident); statistics
   // tail_sync[2k] = virtual tiles of step tail_from + k evaluated with their stores complete (view 0's only: the step barrier);
   // tail_sync[2k + 1] = THIS view's live rays entering step tail_from + k + 1 (= cnt_live of that step, kept next to the barrier word so
   // that one 8-byte load answers both "is the step over" and "how many rays does the next one have")
@@ -184,6 +184,16 @@ __device__ __forceinline__ void vfind(int32_t c, int32_t incl, int B, int g, int
   b = __builtin_amdgcn_readfirstlane(hit ? (__ffsll((long long)hit) - 1) : 0);
   start = __shfl(excl, b);
   cnt = __shfl(c, b);
+}
+// ... for a tile that starts at virtual index vbase (< total): its view, its first position in the view's list and the view's count. False:
+// the tile is padding behind the view's last ray (tiles smaller than the granularity g; all members of a cluster agree): nothing to do.
+__device__ __forceinline__ bool vtile_find(int32_t c, int32_t incl, int B, int g, int64_t vbase, int& vb, int64_t& base, int64_t& count) {
+  int64_t start;
+  int32_t cnt;
+  vfind(c, incl, B, g, vbase, vb, start, cnt);
+  base = vbase - start;
+  count = cnt;
+  return base < count;
 }
 
 // Segmented point list (distr_mlp_*_multi): segment s = n[s] points from point off[s] on, with its own latent constants, on
@@ -573,26 +583,34 @@ __device__ __forceinline__ void raypre_load(const View& V, int px, RayPre& st) {
   }
 }
 
-// topk_insert with the keys / slots already in registers (same result, same memory image)
-template <bool XC = false>
-__device__ __forceinline__ int topk_insert_pre(const View& V, const RayPre& st, int px, float s, float zb, float za, int32_t src) {
-  const int bs = V.cfg.buffer_size;
-  const uint32_t u = (uint32_t)px;
-  const float key = fabsf(s);
+// The placement rule with the keys / slots already in registers: position by |sdf| from the back (earlier row wins ties) and the free mask
+// slot (the one of {0..bs} no entry uses), slot = -1 when the row does not enter. Written once for every path that evaluates a fine step;
+// topk_insert above (k_fine_init folds the coarse rows) walks memory and stops at the first miss: sharing the rule would make it branch on its caller.
+struct TopkPlace { int pos, slot; };
+__device__ __forceinline__ TopkPlace topk_place(int bs, const float (&ks)[MAX_BS], const int32_t (&sl)[MAX_BS], float key) {
   int pos = bs;
   bool open = true;
 #pragma unroll
   for (int k = MAX_BS - 1; k >= 0; --k) {
-    if (k < bs && open) { if (key < fabsf(st.ks[k])) pos = k; else open = false; }
+    if (k < bs && open) { if (key < fabsf(ks[k])) pos = k; else open = false; }
   }
-  if (pos >= bs) return -1;
+  if (pos >= bs) return {pos, -1};
   int used = 0;
 #pragma unroll
-  for (int k = 0; k < MAX_BS; ++k) used += (k < bs) ? st.sl[k] : 0;
-  const int free_slot = bs * (bs + 1) / 2 - used;
+  for (int k = 0; k < MAX_BS; ++k) used += (k < bs) ? sl[k] : 0;
+  return {pos, bs * (bs + 1) / 2 - used};
+}
+
+// topk_insert with the keys / slots already in registers (same result, same memory image); returns where the row went (topk_place)
+template <bool XC = false>
+__device__ __forceinline__ TopkPlace topk_insert_pre(const View& V, const RayPre& st, int px, float s, float zb, float za, int32_t src) {
+  const int bs = V.cfg.buffer_size;
+  const uint32_t u = (uint32_t)px;
+  const TopkPlace pl = topk_place(bs, st.ks, st.sl, fabsf(s));
+  if (pl.slot < 0) return pl;
 #pragma unroll
   for (int k = MAX_BS - 1; k >= 1; --k) {
-    if (k < bs && k > pos) {
+    if (k < bs && k > pl.pos) {
       st_x<XC>(ray_row(V.tk_s, k, V.P) + u, st.ks[k - 1]);
       st_x<XC>(ray_row(V.tk_slot, k, V.P) + u, st.sl[k - 1]);
       st_x<XC>(ray_row(V.tk_zb, k, V.P) + u, ld_x<XC>(ray_row(V.tk_zb, k - 1, V.P) + u));
@@ -603,33 +621,15 @@ __device__ __forceinline__ int topk_insert_pre(const View& V, const RayPre& st, 
   // (the new row's place is data: one of bs unrolled, uniformly based stores)
 #pragma unroll
   for (int k = 0; k < MAX_BS; ++k) {
-    if (k < bs && k == pos) {
+    if (k < bs && k == pl.pos) {
       st_x<XC>(ray_row(V.tk_s, k, V.P) + u, s);
       st_x<XC>(ray_row(V.tk_zb, k, V.P) + u, zb);
       st_x<XC>(ray_row(V.tk_za, k, V.P) + u, za);
       st_x<XC>(ray_row(V.tk_src, k, V.P) + u, src);
-      st_x<XC>(ray_row(V.tk_slot, k, V.P) + u, (int32_t)free_slot);
+      st_x<XC>(ray_row(V.tk_slot, k, V.P) + u, (int32_t)pl.slot);
     }
   }
-  return free_slot;
-}
-
-// ... the slot only (what topk_insert_pre returns), nothing written: the members of a sticky cluster tile that do not lead mirror the
-// lead's insertion on their copy of the keys to know where this step's mask block goes
-__device__ __forceinline__ int topk_slot_pre(const View& V, const RayPre& st, float s) {
-  const int bs = V.cfg.buffer_size;
-  const float key = fabsf(s);
-  int pos = bs;
-  bool open = true;
-#pragma unroll
-  for (int k = MAX_BS - 1; k >= 0; --k) {
-    if (k < bs && open) { if (key < fabsf(st.ks[k])) pos = k; else open = false; }
-  }
-  if (pos >= bs) return -1;
-  int used = 0;
-#pragma unroll
-  for (int k = 0; k < MAX_BS; ++k) used += (k < bs) ? st.sl[k] : 0;
-  return bs * (bs + 1) / 2 - used;
+  return pl;
 }
 
 // The early break of the recursive march (renderer.py:562-567): when no ray is unfinished after L < buffer_size full-resolution steps, the
@@ -741,18 +741,17 @@ enum { MODE_EVAL = 0, MODE_COARSE = 1, MODE_FINE = 2 };
 __host__ __device__ inline void fine_split(int64_t n16, int64_t n64, int t16, int t32, int which, int64_t& lo, int64_t& hi, int& g) {
   if (n16 <= t16) { g = 16; lo = 0; hi = (which == 16) ? n16 : 0; return; }
   g = 64;
-  const int64_t count = n64;
-  const int64_t full = (count / 16384) * 16384, rem = count - full;
-  // remainder split point: rays [full, cut) on 32-ray tiles, [cut, count) on 16-ray tiles (either part may be empty)
+  const int64_t full = (n64 / 16384) * 16384, rem = n64 - full;
+  // remainder split point: rays [full, cut) on 32-ray tiles, [cut, n64) on 16-ray tiles (either part may be empty)
   int64_t cut;
   bool big = false;
   if (rem <= t16) cut = full;
-  else if (rem <= t32) cut = count;
+  else if (rem <= t32) cut = n64;
   else if (t16 < t32 && rem <= (int64_t)t32 + t16) cut = full + t32;
   else { cut = full; big = true; }                                                 // whole remainder on 64-ray tiles
-  if (which == 64) { lo = 0; hi = big ? count : full; }
+  if (which == 64) { lo = 0; hi = big ? n64 : full; }
   else if (which == 32) { lo = full; hi = big ? full : cut; }
-  else { lo = big ? count : cut; hi = count; }
+  else { lo = big ? n64 : cut; hi = n64; }
 }
 
 // A step keeps its live list in ORDER when its 64-ray role has work (whole rounds, or a big remainder): the compacted 64-ray tile of the
@@ -818,10 +817,62 @@ __device__ __forceinline__ LevelView level_at(int l, int b) {
 }
 __device__ __forceinline__ int64_t moff_at(int l) { return (&kernarg_ref<MarchArgs>(0).V.moff[0])[l]; }
 
+// ---- one march step of one ray (renderer.py:481-494, 528-567), written once for every tile body: march_tile, tile16_run, sticky_tile16
+// sample point of ray `id` of level L at march depth zd (V: the ray's view -- camera constants and cfg)
+__device__ __forceinline__ void ray_point(const View& V, const LevelView& L, int32_t id, float zd, float* p) {
+  const CamRegs cam = load_cam(V.C);
+  float cx, cy;
+  level_center(L, id, cx, cy);
+  const RayGeo g = make_ray(V.cfg.K_inv, cam.R, cx, cy);
+  make_point(V.cfg.M, cam.c, g.d, zd, p);
+}
+
+// mask block (View::mstore) of a full-resolution row that took slot `slot` of its ray's selected-row buffer (-1: the row is not kept) ...
+__device__ __forceinline__ long long fine_mblock(const View& V, int32_t id, int slot) {
+  return slot >= 0 ? (long long)id * (V.cfg.buffer_size + 1) + slot : -1ll;
+}
+// ... and of the row of ray `id` at step `step` of coarse level lvl (L = level_at(lvl, view))
+__device__ __forceinline__ long long coarse_mblock(const View& V, const LevelView& L, int lvl, int step, int32_t id) {
+  return V.mfine + moff_at(lvl) + (long long)((size_t)step * L.n + id);
+}
+
+// a coarse level's step: aggressive march update and the step's row; returns the row's mask block
+__device__ __forceinline__ long long coarse_commit(const LevelView& L, const View& V, int lvl, int step, int32_t id, float s, float zd) {
+  const float cd = V.cfg.clamp_dist;
+  const float mn = L.cm[id] + clampf(s, -cd, cd) * V.cfg.ratio;
+  L.cm[id] = mn;
+  const size_t o = (size_t)step * L.n + id;
+  L.rs[o] = s;
+  L.rzb[o] = zd;
+  L.rza[o] = mn + L.cinit[id];
+  return coarse_mblock(V, L, lvl, step, id);
+}
+
+// a full-resolution step: new march depth mn, depth after the step za, a = |sdf|, and whether the ray stays live (inside its bound, not converged)
+struct FineStep { float mn, za, a; bool stay; };
+__device__ __forceinline__ FineStep fine_step(const distr_render_cfg& cfg, float m, float init_now, float maxbound, float s) {
+  FineStep r;
+  r.mn = m + clampf(s, -cfg.clamp_dist, cfg.clamp_dist) * cfg.ratio;
+  r.za = r.mn + init_now;
+  r.a = fabsf(s);
+  r.stay = (r.za < maxbound) && (r.a >= cfg.threshold);
+  return r;
+}
+// ... and what the tile's lead (or only) workgroup writes for it: march depth, online minimum, first value, the row into the selected-row
+// buffer (st: the ray's state as loaded BEFORE the step). Returns where the row went (slot < 0: nowhere).
+__device__ __forceinline__ TopkPlace fine_commit(const View& V, const RayPre& st, int32_t id, int step, float s, float zd, const FineStep& r) {
+  const uint32_t u = (uint32_t)id;
+  V.m[u] = r.mn;
+  const TopkPlace pl = topk_insert_pre<false>(V, st, id, s, zd, V.pyramid ? r.za : r.mn, step);  // src: level 0 | march step (early_dup)
+  if (r.a < st.minabs) V.minabs[u] = r.a;
+  if (step == 0) V.first_sdf[u] = s;
+  return pl;
+}
+
 // KEEP: also save the ReLU masks of every row that enters a ray's selected-row buffer (and of every coarse row), so
 // that the backward pass does not have to recompute the decoder forward (View::mstore).
 // Body of one 32*RB-ray tile; `tile` / `ntile_grid` = index and count of the tiles this launch (or this role of a merged
-// launch, k_step) provides, `which` = the tile size the split rule (fine_range) knows this role by.
+// launch, k_step) provides, `which` = the tile size the split rule (fine_split) knows this role by.
 // Returns false when the tile lies beyond this role's range (nothing done).
 // ARITH = 0: exact f32 MFMA tile (distr_mlp.hpp); 1: six-product split-bf16, 2: three-product split-f16 -- the split tile
 // (distr_mlp_split.hpp) in the format SplitFmt<ARITH>   (distr_render_cfg.arith)
@@ -870,6 +921,8 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
     }
     const int64_t vbase = lo + (int64_t)tile * TILE;
     if (vbase >= hi) return false;
+    // (vtile_find, written out: through the helper the 64- / 32-ray roles of k_step<KEEP, split-f16> and of the compacted k_step allocate
+    // ~25 more registers and end in scratch -- profiles/march_step_once.md)
     int64_t start;
     int32_t cnt;
     vfind(c, incl, B, g, vbase, vb, start, cnt);
@@ -902,13 +955,9 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
         } else {
           id = list[r];
           const LevelView L = (MODE == MODE_COARSE) ? level_at(A.lvl, vb) : V.lv[0];
-          const CamRegs cam = load_cam(V.C);
-          float cx, cy;
-          level_center(L, id, cx, cy);
-          const RayGeo g = make_ray(V.cfg.K_inv, cam.R, cx, cy);
           if (MODE == MODE_FINE) { raypre_load(V, id, st); zd = st.init_now + st.m; }
           else zd = L.cinit[id] + L.cm[id];
-          make_point(V.cfg.M, cam.c, g.d, zd, p);
+          ray_point(V, L, id, zd, p);
         }
       }
     }
@@ -938,30 +987,14 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
     } else if (MODE == MODE_EVAL) {
       if (valid) A.sdf_out[id] = (A.clamp >= 0.f) ? clampf(s, -A.clamp, A.clamp) : s;
     } else {
-      const float cd = V.cfg.clamp_dist, ratio = V.cfg.ratio;
       if (MODE == MODE_COARSE) {
-        if (valid) {
-          const LevelView L = level_at(A.lvl, vb);
-          const float mn = L.cm[id] + clampf(s, -cd, cd) * ratio;
-          L.cm[id] = mn;
-          const size_t o = (size_t)A.step * L.n + id;
-          L.rs[o] = s;
-          L.rzb[o] = zd;
-          L.rza[o] = mn + L.cinit[id];
-          mblock = V.mfine + moff_at(A.lvl) + (int64_t)o;
-        }
+        if (valid) mblock = coarse_commit(level_at(A.lvl, vb), V, A.lvl, A.step, id, s, zd);
       } else {  // MODE_FINE
         bool stay = false;
         if (valid) {
-          const float mn = st.m + clampf(s, -cd, cd) * ratio;
-          V.m[(uint32_t)id] = mn;
-          const float za = mn + st.init_now;
-          const int slot = topk_insert_pre(V, st, id, s, zd, V.pyramid ? za : mn, A.step);  // src: level 0 | march step (early_dup)
-          if (slot >= 0) mblock = (int64_t)id * (V.cfg.buffer_size + 1) + slot;
-          const float a = fabsf(s);
-          if (a < st.minabs) V.minabs[(uint32_t)id] = a;
-          if (A.step == 0) V.first_sdf[(uint32_t)id] = s;
-          stay = (za < st.maxbound) && (a >= V.cfg.threshold);
+          const FineStep r = fine_step(V.cfg, st.m, st.init_now, st.maxbound, s);
+          mblock = fine_mblock(V, id, fine_commit(V, st, id, A.step, s, zd, r).slot);
+          stay = r.stay;
         }
         if (V.cfg.marcher != DISTR_MARCH_TRIVIAL) {
           if (ordered) slot_append<TILE>(stay, id, V, base);
@@ -1088,7 +1121,6 @@ __device__ __forceinline__ void sticky_tile16(const MarchArgs& A, const DecoderD
     S.c0s[t32] = cb[t32];
     S.c0s[t32 + NTHREADS] = cb[t32 + (uint32_t)NTHREADS];
   }
-  const float cd = V.cfg.clamp_dist, ratio = V.cfg.ratio;
   bool solo = solo0;                  // the cluster broke up: the lead member finishes the tile alone
   bool leaving = false;               // a member other than the lead that gave up after `go`: one evaluation of its own for the mask blocks, then out
   for (int step = step0, k = 0;; ++step, ++k) {
@@ -1096,11 +1128,7 @@ __device__ __forceinline__ void sticky_tile16(const MarchArgs& A, const DecoderD
       float p[3] = {0.f, 0.f, 0.f};
       if (live) {        // (the ray direction is recomputed from the pixel id every step, like the per-step kernels do: ~40 flops
         const View& Vp = kernarg_ref<MarchArgs>(0).V;      // against three registers held across the decoder evaluation); camera constants re-read per step
-        const CamRegs cam = load_cam(view_at(Vp, vb).C);
-        float cx, cy;
-        level_center(Vp.lv[0], id, cx, cy);
-        const RayGeo g = make_ray(Vp.cfg.K_inv, cam.R, cx, cy);
-        make_point(Vp.cfg.M, cam.c, g.d, init_now + m, p);
+        ray_point(view_at(Vp, vb), Vp.lv[0], id, init_now + m, p);
       }
       S.xyz[tid] = p[0]; S.xyz[TILE + tid] = p[1]; S.xyz[2 * TILE + tid] = p[2];
     }
@@ -1152,48 +1180,33 @@ __device__ __forceinline__ void sticky_tile16(const MarchArgs& A, const DecoderD
       const unsigned long long was = __ballot(tid < TILE && live);
       bool stay = false;
       if (tid < TILE && live) {
-        const float mn = m + clampf(s, -cd, cd) * ratio;
-        const float za = mn + init_now;
-        const float a = fabsf(s);
-        {
-          // (the ray's row addresses are recomputed from id + an opaque zero every step: hoisted out of the step loop they would be ~40
-          // 64-bit values alive across the decoder evaluation)
-          const int32_t id_ = id + zero;
-          if (lead) Ve.m[(uint32_t)id_] = mn;
-          RayPre st;                   // this step's view of the selected rows (only the keys and slots are read)
-          st.m = m; st.init_now = init_now; st.maxbound = maxbound; st.minabs = minabs;
+        const FineStep r = fine_step(Ve.cfg, m, init_now, maxbound, s);
+        // (the ray's row addresses are recomputed from id + an opaque zero every step: hoisted out of the step loop they would be ~40
+        // 64-bit values alive across the decoder evaluation)
+        const int32_t id_ = id + zero;
+        RayPre st;                   // the ray's state in front of this step: registers + the LDS copy of the selected rows' keys and slots
+        st.m = m; st.init_now = init_now; st.maxbound = maxbound; st.minabs = minabs;
 #pragma unroll
-          for (int k = 0; k < MAX_BS; ++k) { st.ks[k] = S.sk[k][tid]; st.sl[k] = S.ssl[k][tid]; }
-          // only the lead writes the selected rows; every member mirrors the insertion on its LDS copy of the keys / slots: the slot says
-          // where this step's mask block goes, and every member stores its own words of it (mlp_forward16_cl, MASK_OWN)
-          const int slot = lead ? topk_insert_pre<false>(Ve, st, id_, s, zd, Ve.pyramid ? za : mn, step) : topk_slot_pre(Ve, st, s);
-          if (slot >= 0) {
-            mblock = (long long)id_ * (Ve.cfg.buffer_size + 1) + slot;
-            // the same insertion on the LDS copy: rows behind the new one move down, the new row takes its place
-            const int bs = Ve.cfg.buffer_size;
-            int pos = bs;
-            bool open = true;
+        for (int k = 0; k < MAX_BS; ++k) { st.ks[k] = S.sk[k][tid]; st.sl[k] = S.ssl[k][tid]; }
+        // only the lead writes the step's results; every member mirrors the insertion on its LDS copy of the keys / slots: the slot says
+        // where this step's mask block goes, and every member stores its own words of it (mlp_forward16_cl, MASK_OWN)
+        const TopkPlace pl = lead ? fine_commit(Ve, st, id_, step, s, zd, r) : topk_place(Ve.cfg.buffer_size, st.ks, st.sl, r.a);
+        mblock = fine_mblock(Ve, id_, pl.slot);
+        if (pl.slot >= 0) {
+          // the same insertion on the LDS copy: rows behind the new one move down, the new row takes its place
+          const int bs = Ve.cfg.buffer_size;
 #pragma unroll
-            for (int k = MAX_BS - 1; k >= 0; --k) {
-              if (k < bs && open) { if (a < fabsf(st.ks[k])) pos = k; else open = false; }
-            }
-#pragma unroll
-            for (int k = MAX_BS - 1; k >= 1; --k) {
-              if (k < bs && k > pos) { S.sk[k][tid] = st.ks[k - 1]; S.ssl[k][tid] = st.sl[k - 1]; }
-            }
-#pragma unroll
-            for (int k = 0; k < MAX_BS; ++k) {
-              if (k == pos) { S.sk[k][tid] = s; S.ssl[k][tid] = slot; }
-            }
+          for (int k = MAX_BS - 1; k >= 1; --k) {
+            if (k < bs && k > pl.pos) { S.sk[k][tid] = st.ks[k - 1]; S.ssl[k][tid] = st.sl[k - 1]; }
           }
-          if (lead) {
-            if (a < minabs) Ve.minabs[(uint32_t)id_] = a;
-            if (step == 0) Ve.first_sdf[(uint32_t)id_] = s;
+#pragma unroll
+          for (int k = 0; k < MAX_BS; ++k) {
+            if (k == pl.pos) { S.sk[k][tid] = s; S.ssl[k][tid] = pl.slot; }
           }
         }
-        if (a < minabs) minabs = a;
-        m = mn;
-        stay = (za < maxbound) && (a >= Ve.cfg.threshold);
+        if (r.a < minabs) minabs = r.a;
+        m = r.mn;
+        stay = r.stay;
       }
       if (lead) mark_live_end(Ve.C, tid < TILE && stay, step, Ve.fine_steps);
       if (!TAIL && solo && k == 0 && lead) {
@@ -1273,24 +1286,20 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
       } else {
         id = ld_x<false>(list + r);
         const LevelView L = (MODE == MODE_COARSE) ? level_at(A.lvl, t.vb) : V.lv[0];
-        const CamRegs cam = load_cam(V.C);
-        float cx, cy;
-        level_center(L, id, cx, cy);
-        const RayGeo g = make_ray(V.cfg.K_inv, cam.R, cx, cy);
         if (MODE == MODE_FINE) {
           raypre_load<false>(V, id, st);
           zd = st.init_now + st.m;
           if constexpr (TAIL) {
             // the persistent tail launch parks the ray's state in LDS across the evaluation instead of twenty registers per lane (inside
             // its step loop they end up in scratch). NOT re-read from memory in the epilogue: a cluster's members other than the lead
-            // need the selected rows as they were BEFORE the lead member's epilogue rewrites them (topk_slot_pre: where the mask block goes)
+            // need the selected rows as they were BEFORE the lead member's epilogue rewrites them (topk_place: where the mask block goes)
             S.sst[0][tid] = st.m; S.sst[1][tid] = st.init_now; S.sst[2][tid] = st.maxbound; S.sst[3][tid] = st.minabs;
 #pragma unroll
             for (int k = 0; k < MAX_BS; ++k) { S.sk[k][tid] = st.ks[k]; S.ssl[k][tid] = st.sl[k]; }
           }
         }
         else zd = L.cinit[id] + L.cm[id];
-        make_point(V.cfg.M, cam.c, g.d, zd, p);
+        ray_point(V, L, id, zd, p);
       }
     }
     S.xyz[tid] = p[0]; S.xyz[TILE + tid] = p[1]; S.xyz[2 * TILE + tid] = p[2];
@@ -1303,46 +1312,40 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
   float pre;
   bool clustered = false;               // the tile's value (and, KEEP, its mask blocks in S.mk) came from the cluster path
   bool helper = false;                  // a member of a cluster tile other than the lead (KEEP: it stores its words of the mask blocks, nothing else)
-  if (MODE != MODE_EVAL && cl > 1) {
-    if constexpr (MODE != MODE_EVAL) {
-      // KEEP: every member evaluates lin8 too (ALL_LIN8) and records the ReLU bits of its own rows (MASK_OWN): it then knows where the rays'
-      // mask blocks go and stores its words of them itself -- the lead member does not extract bits from staged rows (that made it the
-      // last to publish in every layer). Without KEEP the other members leave after their last slice.
-      const int32_t lost = TAIL ? t.lost : 0;     // (lead member, lane 0: its claim failed -> the cluster is told to leave)
-      if (cl == 8) pre = mlp_forward16_cl<8, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
-      else if (cl == 4) pre = mlp_forward16_cl<4, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
-      else pre = mlp_forward16_cl<2, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
-    } else pre = 0.f;
-    helper = member != cl_lead(cl);      // only the lead member runs the epilogue; with KEEP the others store their mask words
-    clustered = S.fail == 0;
-    if (helper && !clustered) {
-      // Gave up before `go` (or no masks to save): the lead member evaluates the tile alone and stores whole mask blocks. Gave up AFTER
-      // `go` with masks to save: it may have published every slice already (a timeout while staging h7) -- then the others complete the
-      // tile and store THEIR words of the rays' mask blocks, and this member's words would keep what an earlier render left there (ADVICE
-      // r5). It evaluates the tile on its own and stores the whole blocks (the same bits the others store: harmless where they overlap).
-      if (!KEEP || !S.went) return;
-      if (tid == 0) atomicAdd(&V.C->xchg_err, 1);
-      __syncthreads();
-      pre = mlp_forward16<KEEP>(D, D16, c0, c4, S, nib);
-    } else
-    if (!clustered) {
-      if constexpr (TAIL) {      // ... or its lead's claim had been lost: the tile is somebody else's
-        if (tid == 0) S.cont = t.lost;
-        __syncthreads();
-        if (S.cont) return;
-      }
-      // the cluster did not assemble (compute units held by other streams / ranks) or a barrier timed out: the lead member
-      // evaluates the tile on its own -- identical values; counted in the render stats (cluster_fallbacks)
-      if (tid == 0) atomicAdd(&V.C->xchg_err, 1);
-      __syncthreads();
-      pre = mlp_forward16<KEEP>(D, D16, c0, c4, S, nib);
-    }
-  } else {
+  if (!(MODE != MODE_EVAL && cl > 1)) {
     pre = mlp_forward16<KEEP>(D, D16, c0, c4, S, nib);
     if constexpr (TAIL) {        // the claim (issued before the evaluation) must have been won before anything is written
       if (tid == 0) S.cont = t.lost;
       __syncthreads();
       if (S.cont) return;
+    }
+  } else if constexpr (MODE != MODE_EVAL) {
+    // KEEP: every member evaluates lin8 too (ALL_LIN8) and records the ReLU bits of its own rows (MASK_OWN): it then knows where the rays'
+    // mask blocks go and stores its words of them itself -- the lead member does not extract bits from staged rows (that made it the
+    // last to publish in every layer). Without KEEP the other members leave after their last slice.
+    const int32_t lost = TAIL ? t.lost : 0;     // (lead member, lane 0: its claim failed -> the cluster is told to leave)
+    if (cl == 8) pre = mlp_forward16_cl<8, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
+    else if (cl == 4) pre = mlp_forward16_cl<4, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
+    else pre = mlp_forward16_cl<2, KEEP, KEEP, KEEP>(D, D16, c0, c4, S, xc, tile, member, true, lost);
+    helper = member != cl_lead(cl);      // only the lead member runs the epilogue; with KEEP the others store their mask words
+    clustered = S.fail == 0;
+    if (!clustered) {
+      if (helper) {
+        // Gave up before `go` (or no masks to save): the lead member evaluates the tile alone and stores whole mask blocks. Gave up AFTER
+        // `go` with masks to save: it may have published every slice already (a timeout while staging h7) -- then the others complete the
+        // tile and store THEIR words of the rays' mask blocks, and this member's words would keep what an earlier render left there (ADVICE
+        // r5). It evaluates the tile on its own and stores the whole blocks (the same bits the others store: harmless where they overlap).
+        if (!KEEP || !S.went) return;
+      } else if constexpr (TAIL) {      // the lead's claim had been lost: the tile is somebody else's
+        if (tid == 0) S.cont = t.lost;
+        __syncthreads();
+        if (S.cont) return;
+      }
+      // the cluster did not assemble (compute units held by other streams / ranks) or a barrier timed out: the lead member (or the
+      // member above) evaluates the tile on its own -- identical values; counted in the render stats (cluster_fallbacks)
+      if (tid == 0) atomicAdd(&V.C->xchg_err, 1);
+      __syncthreads();
+      pre = mlp_forward16<KEEP>(D, D16, c0, c4, S, nib);
     }
   }
 
@@ -1368,41 +1371,22 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
       if (origin) {
         if (tid == 0) mblock = Ve.morigin;
       } else if (MODE == MODE_COARSE) {
-        if (valid) mblock = Ve.mfine + moff_at(A.lvl) + (long long)((size_t)t.step * level_at(A.lvl, t.vb).n + id);
+        if (valid) mblock = coarse_mblock(Ve, level_at(A.lvl, t.vb), A.lvl, t.step, id);
       } else if (MODE == MODE_FINE) {
-        if (valid) {
-          const int slot = topk_slot_pre(Ve, sr, s);
-          if (slot >= 0) mblock = (long long)id * (Ve.cfg.buffer_size + 1) + slot;
-        }
+        if (valid) mblock = fine_mblock(Ve, id, topk_place(Ve.cfg.buffer_size, sr.ks, sr.sl, fabsf(s)).slot);
       }
     } else if (origin) {
       if (tid == 0) { Ve.C->f_origin = s; Ve.C->origin_done = 1; mblock = Ve.morigin; }
     } else if (MODE == MODE_EVAL) {
       if (valid) A.sdf_out[id] = (A.clamp >= 0.f) ? clampf(s, -A.clamp, A.clamp) : s;
     } else if (MODE == MODE_COARSE) {
-      if (valid) {
-        const LevelView L = level_at(A.lvl, t.vb);
-        const float mn = L.cm[id] + clampf(s, -Ve.cfg.clamp_dist, Ve.cfg.clamp_dist) * Ve.cfg.ratio;
-        L.cm[id] = mn;
-        const size_t o = (size_t)t.step * L.n + id;
-        L.rs[o] = s;
-        L.rzb[o] = zd;
-        L.rza[o] = mn + L.cinit[id];
-        mblock = Ve.mfine + moff_at(A.lvl) + (long long)o;
-      }
+      if (valid) mblock = coarse_commit(level_at(A.lvl, t.vb), Ve, A.lvl, t.step, id, s, zd);
     } else {
-      const float cd = Ve.cfg.clamp_dist, ratio = Ve.cfg.ratio;
       bool stay = false;
       if (valid) {
-        const float mn = sr.m + clampf(s, -cd, cd) * ratio;
-        Ve.m[(uint32_t)id] = mn;
-        const float za = mn + sr.init_now;
-        const int slot = topk_insert_pre<false>(Ve, sr, id, s, zd, Ve.pyramid ? za : mn, t.step);
-        if (slot >= 0) mblock = (long long)id * (Ve.cfg.buffer_size + 1) + slot;
-        const float a = fabsf(s);
-        if (a < sr.minabs) Ve.minabs[(uint32_t)id] = a;
-        if (t.step == 0) Ve.first_sdf[(uint32_t)id] = s;
-        stay = (za < sr.maxbound) && (a >= Ve.cfg.threshold);
+        const FineStep r = fine_step(Ve.cfg, sr.m, sr.init_now, sr.maxbound, s);
+        mblock = fine_mblock(Ve, id, fine_commit(Ve, sr, id, t.step, s, zd, r).slot);
+        stay = r.stay;
       }
       if (!TAIL && t.ordered) slot_append<TILE>(stay, id, Ve, base);
       else wave_append<false>(stay, id, live_sel(Ve, t.step + 1), &Ve.C->cnt_live[t.step + 1], TAIL ? t.count2 : nullptr);
@@ -1424,6 +1408,32 @@ __device__ __forceinline__ void tile16_run(const MarchArgs& A, const DecoderDev&
   }
 }
 
+
+// ---- the cluster plan of a launch of 16-ray tiles, from device-side counts: every workgroup of a k_march16 launch / k_step role / k_tail step
+// derives the same one. need = the launch's tiles, the extra tiles for f(origin) on the launch that carries them included.
+// Cluster size: with at most 32 / 64 / 128 tiles -- so that the grid stays within 256 workgroups -- 8 / 4 / 2 compute units share each tile.
+// Measured step time (C3 tail, profiles/r02_steps_c3.md): 52 us (8), 64 us (4), 94 us (2), 107 us (single workgroup).
+__device__ __forceinline__ int cluster_size(const Xchg& xc, int64_t need) {
+  if (!xc.buf) return 1;
+  return (need <= 32 && xc.max_cl >= 8) ? 8 : (need <= 64 && xc.max_cl >= 4) ? 4 : (need <= 128 && xc.min_cl <= 2) ? 2 : 1;
+}
+// Sticky: ALL live rays of full-resolution step `step` fit one launch of 8-CU cluster tiles and a step follows -- the tiles then keep their
+// rays to the end of the march (sticky_tile16). The caller adds what only it knows (that nothing went to the 32- / 64-ray roles; that there are rays).
+__device__ __forceinline__ bool sticky_fits(const Xchg& xc, int step, int fine_steps, int64_t need) {
+  return xc.buf && xc.sticky && xc.max_cl >= 8 && step + 1 < fine_steps && need <= 32;
+}
+// Workgroup bidx of the launch (role, tail step) -> tile and member of its cluster of cl: members = workgroups with equal index mod 8 (same
+// XCD: every role of a launch starts at a multiple of 8); cl = 1: tile bidx.
+// (Measured alternative: member m of every cluster on XCD m, so that an XCD streams only its 1/cl slice of the weights from a
+// warm L2 -- the compute phase did not change, it is not bound by weight latency, and the exchange across XCDs cost 1 us more.)
+__device__ __forceinline__ void cluster_member(int bidx, int cl, bool spread, int& tile, int& member) {
+  tile = bidx; member = 0;
+  if (cl <= 1) return;
+  const int gq = bidx / (8 * cl), r = bidx % (8 * cl);
+  tile = gq * 8 + (r & 7);
+  member = r >> 3;
+  if (spread) { tile = gq * 8 + r / cl; member = r % cl; }     // tests: members on consecutive workgroups = different XCDs
+}
 
 // The same march step on 16-ray tiles (v_mfma_f32_16x16x4_f32), for the live-ray tail: see distr_mlp.hpp::Smem16.
 // MODE_FINE (recursive marchers), MODE_COARSE (pyramid levels of small images) and MODE_EVAL.
@@ -1466,29 +1476,11 @@ __device__ __forceinline__ void march_tile16(const MarchArgs& A, const DecoderDe
   // tiles then keep their rays to the end of the march (sticky_tile16) and the origin tiles ride on THIS launch (the last
   // step's launch would otherwise be a whole cluster-tile latency for them alone). A small remainder next to whole 64-ray
   // rounds must NOT go sticky: its rays would finish their march inside a launch whose other rays move on step by step.
-  bool sticky_launch = false;
-  if (MODE == MODE_FINE && A.xc.buf && A.xc.sticky && A.xc.max_cl >= 8 && gran == 16 && A.step + 1 < V0.fine_steps && ntiles + B <= 32) {
-    sticky_launch = true;
-    norigin = B;
-  }
-  // Cluster size from the (device-side) number of tiles of this launch: with at most 32 / 64 / 128 tiles -- counting the extra
-  // tiles for f(origin) on the one launch that carries them, so that the grid stays within 256 workgroups -- 8 / 4 / 2 compute units
-  // share each tile. Measured step time (C3 tail, profiles/r02_steps_c3.md): 52 us (8), 64 us (4), 94 us (2), 107 us (single
-  // workgroup).
-  int cl = 1;
-  if (MODE != MODE_EVAL && A.xc.buf) {
-    const int64_t need = ntiles + norigin;
-    cl = (need <= 32 && A.xc.max_cl >= 8) ? 8 : (need <= 64 && A.xc.max_cl >= 4) ? 4 : (need <= 128 && A.xc.min_cl <= 2) ? 2 : 1;
-  }
-  int tile = bidx, member = 0;
-  if (cl > 1) {   // members of a cluster = workgroups with equal index mod 8 (same XCD: every role of a launch starts at a multiple of 8).
-    // (Measured alternative: member m of every cluster on XCD m, so that an XCD streams only its 1/cl slice of the weights from a
-    // warm L2 -- the compute phase did not change, it is not bound by weight latency, and the exchange across XCDs cost 1 us more.)
-    const int gq = bidx / (8 * cl), r = bidx % (8 * cl);
-    tile = gq * 8 + (r & 7);
-    member = r >> 3;
-    if (A.xc.spread) { tile = gq * 8 + r / cl; member = r % cl; }     // tests: members on consecutive workgroups = different XCDs
-  }
+  const bool sticky_launch = MODE == MODE_FINE && gran == 16 && sticky_fits(A.xc, A.step, V0.fine_steps, ntiles + B);
+  if (sticky_launch) norigin = B;
+  const int cl = (MODE != MODE_EVAL) ? cluster_size(A.xc, ntiles + norigin) : 1;
+  int tile, member;
+  cluster_member(bidx, cl, A.xc.spread, tile, member);
   const bool origin = norigin > 0 && tile >= ntiles && tile < ntiles + norigin;
   int vb = 0;
   int64_t base = (int64_t)tile * TILE, count = hi;
@@ -1497,14 +1489,7 @@ __device__ __forceinline__ void march_tile16(const MarchArgs& A, const DecoderDe
   } else {
     const int64_t vbase = lo + (int64_t)tile * TILE;
     if (vbase >= hi) return;
-    if (MODE != MODE_EVAL) {
-      int64_t start;
-      int32_t cnt;
-      vfind(c, incl, B, gran, vbase, vb, start, cnt);
-      base = vbase - start;
-      count = cnt;
-      if (base >= count) return;       // padding behind the view's last ray (all members of a cluster agree)
-    }
+    if (MODE != MODE_EVAL && !vtile_find(c, incl, B, gran, vbase, vb, base, count)) return;
   }
   Tile16 t;
   t.tile = tile; t.member = member; t.cl = cl; t.vb = vb; t.origin = origin; t.sticky = sticky_launch; t.solo = false; t.base = base; t.count = count;
@@ -1568,9 +1553,8 @@ __device__ __forceinline__ TailPlan tail_plan(const MarchArgs& A, const Xchg& xc
   P.ntiles = vtotal(P.incl, B) / 16;
   P.norigin = first ? B : 0;
   const int64_t need = P.ntiles + P.norigin;
-  P.sticky = xc.buf && xc.sticky && xc.max_cl >= 8 && step + 1 < V0.fine_steps && P.ntiles > 0 && need <= 32;
-  P.cl = 1;
-  if (xc.buf) P.cl = (need <= 32 && xc.max_cl >= 8) ? 8 : (need <= 64 && xc.max_cl >= 4) ? 4 : (need <= 128 && xc.min_cl <= 2) ? 2 : 1;
+  P.sticky = P.ntiles > 0 && sticky_fits(xc, step, V0.fine_steps, need);
+  P.cl = cluster_size(xc, need);
   return P;
 }
 
@@ -1619,11 +1603,7 @@ __device__ __forceinline__ void tail_slot(const MarchArgs& A, const DecoderDev& 
   if (t.origin) {
     t.vb = (int)(vt - P.ntiles);
   } else {
-    int64_t start;
-    int32_t cnt;
-    vfind(P.c, P.incl, V0.nviews, 16, vt * 16, t.vb, start, cnt);
-    t.base = vt * 16 - start;
-    t.count = cnt;
+    (void)vtile_find(P.c, P.incl, V0.nviews, 16, vt * 16, t.vb, t.base, t.count);     // (16-ray tiles at granularity 16: no padding tiles)
   }
   // second counter of the rays that stay live: the count word next to the step's barrier word, in the tile's view
   t.count2 = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(&V0.C->tail_sync[2 * k + 1]) + (int64_t)t.vb * V0.vstride);
@@ -1691,18 +1671,13 @@ __global__ void __launch_bounds__(256, 1) k_tail(MarchArgs A, DecoderDev D, Deco
       }
     }
     // This workgroup's jobs of the step, ONE call site for all of them (the tile code is large): first its own tile(s) -- cluster tiles as
-    // in march_tile16 (members = workgroups with equal index mod 8: one XCD), single-workgroup tiles b, b + 256, ... --, then the wait for
+    // in march_tile16 (cluster_member), single-workgroup tiles b, b + 256, ... --, then the wait for
     // the step (sticky step: for every tile to have an owner), and from a wait that took too long a scan over all tiles for abandoned ones.
     enum { OWN = 0, WAIT = 1, SCAN = 2 };
     int mode = OWN;
-    int64_t cur = bidx, scan = 0;
-    int member = 0;
-    if (P.cl > 1) {
-      const int gq = bidx / (8 * P.cl), r = bidx % (8 * P.cl);
-      cur = gq * 8 + (r & 7);
-      member = r >> 3;
-      if (xc.spread) { cur = gq * 8 + r / P.cl; member = r % P.cl; }     // tests: members on consecutive workgroups = different XCDs
-    }
+    int own, member;
+    cluster_member(bidx, P.cl, xc.spread, own, member);
+    int64_t cur = own, scan = 0;
     const long long t_step = (long long)wall_clock64();
     for (;;) {
       if (mode == OWN && cur >= slots) mode = WAIT;
@@ -1764,7 +1739,7 @@ __global__ void __launch_bounds__(256, 1) k_tail(MarchArgs A, DecoderDev D, Deco
   }
 }
 
-// One full-resolution march step of the recursive marchers in ONE launch: the three tile sizes of the split (fine_range)
+// One full-resolution march step of the recursive marchers in ONE launch: the three tile sizes of the split (fine_split)
 // are roles of the same grid -- n32 workgroups for 32-ray tiles, n16 for 16-ray / cluster tiles, n64 for 64-ray tiles
 // (n32 a multiple of 8, so cluster members keep equal index mod 8 = the same XCD). Each role finds its
 // range from the device-side live count and exits if it is empty. The 64-ray role is PERSISTENT: at most one workgroup
@@ -2171,12 +2146,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
     const int32_t incl = vprefix(c, B, TILE);
     const int64_t vbase = (int64_t)tile * TILE;
     if (vbase >= vtotal(incl, B)) return;
-    int64_t start;
-    int32_t cnt;
-    vfind(c, incl, B, TILE, vbase, vb, start, cnt);
-    base = vbase - start;
-    count = cnt;
-    if (base >= count) return;
+    if (!vtile_find(c, incl, B, TILE, vbase, vb, base, count)) return;
   } else {
     // gradient samples: every view keeps its OWN tile decomposition (bwd_range of its own count: same tiles, same tile sizes,
     // same partial rows as a stand-alone backward of that view -> bit-identical gradients); this launch walks the

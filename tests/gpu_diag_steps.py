@@ -1,6 +1,6 @@
 """Per-launch table of the march kernels of ONE forward (not a pytest file): for every march launch of the configured render --
 rays evaluated, kernel microseconds (hipEvent bracket on the launch stream), TFLOP/s and fraction of the f32-MFMA peak,
-work-proportional time at the dense rate, and which tile class the split rule (fine_range) picks.
+work-proportional time at the dense rate, and which tile class the split rule (fine_split) picks.
 
     python tests/gpu_diag_steps.py [--size 512] [--march-step 50] [--view 0] [--out gpurun_out/steps.md]
 """
