@@ -114,17 +114,23 @@ DISTR_GLOBAL void __launch_bounds__(256) k_single_loss_partial(SingleLossArgs A,
 
 // sums[0..3], counts[4..7] -> losses[k] = mean over the term's pixel set, 0 for an empty set (loss_utils.py:82-84 etc.)
 DISTR_GLOBAL void __launch_bounds__(64) k_single_loss_final(const float* __restrict__ partial, int nblk, float* __restrict__ out /*[8]: losses[4], counts[4]*/) {
-  __shared__ float s[8];
+  __shared__ float s[4];
+  __shared__ int n[4];
   const int k = threadIdx.x;
-  if (k < 8) {
+  if (k < 4) {
     float acc = 0.f;
     for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * 8 + k];
     s[k] = acc;
+  } else if (k < 8) {
+    // a block's count is an integer <= 256, exact in float32; their sum is not above 2^24: added as integers, converted once
+    int acc = 0;
+    for (int b = 0; b < nblk; ++b) acc += (int)partial[(size_t)b * 8 + k];
+    n[k - 4] = acc;
   }
   __syncthreads();
   if (k < 4) {
-    const float cnt = s[4 + k];
-    out[k] = cnt > 0.f ? s[k] / cnt : 0.f;
+    const float cnt = (float)n[k];
+    out[k] = n[k] > 0 ? s[k] / cnt : 0.f;
     out[4 + k] = cnt;
   }
 }
@@ -290,19 +296,103 @@ DISTR_GLOBAL void __launch_bounds__(256) k_warp_fwd(WarpArgs A, uint8_t* __restr
 // out[0] = loss_color = mean |c1 - c2| over kept pixels x 3 channels (NaN for an empty kept set, as torch.mean of an
 // empty tensor; 0 when view 1 has no valid pixel, renderer_warp.py:111-113), out[1] = #kept, out[2] = #valid
 DISTR_GLOBAL void __launch_bounds__(64) k_warp_final(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
-  __shared__ float s[3];
+  __shared__ float s;
+  __shared__ int n[2];
   const int k = threadIdx.x;
-  if (k < 3) {
+  if (k == 0) {
     float acc = 0.f;
-    for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * 3 + k];
-    s[k] = acc;
+    for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * 3];
+    s = acc;
+  } else if (k < 3) {
+    // the two counts as integers (a block's is <= 256, exact in float32), converted once: exact above 2^24 pixels too
+    int acc = 0;
+    for (int b = 0; b < nblk; ++b) acc += (int)partial[(size_t)b * 3 + k];
+    n[k - 1] = acc;
   }
   __syncthreads();
   if (k == 0) {
-    out[0] = (s[2] == 0.f) ? 0.f : s[0] / (3.0f * s[1]);
-    out[1] = s[1];
-    out[2] = s[2];
+    const float kept = (float)n[0];
+    out[0] = (n[1] == 0) ? 0.f : s / (3.0f * kept);
+    out[1] = kept;
+    out[2] = (float)n[1];
   }
+}
+
+// A kept pixel's gradient in float64 from the float32 inputs: its 24 camera terms [R1 9 | T1 3 | R2 9 | T2 3] are written to acc, each
+// rounded ONCE, and its g_z1 is returned, rounded once (as k_samp_cam_bwd does). In float32 the terms are differences that cancel -- the
+// ray part g_d / e - (g_d . r) r / (rn e^2), -(gix u + giy v), h = K^-1 (x, y, 1) next to the principal point -- and the weights (tx, ty)
+// carry the absolute rounding of a coordinate near W: invisible in a sum over hundreds of pixels, up to 10^4 roundings of a sum that
+// holds ONE pixel. grid_sample's round trip ix = ((2 u / (W - 1) - 1 + 1) / 2) (W - 1) is u for W > 1 and the constant 0 for W = 1: a
+// one-pixel-wide image has no gradient along its thin axis (the float32 code passed d c2 / d ix on as d / d u there).
+__device__ __forceinline__ float warp_pixel_bwd64(const WarpArgs& A, int i, const float* R1, const float* T1, const float* R2, const float* T2,
+                                                  double scale, float* acc /*[24]*/) {
+  const int W = A.W, H = A.H;
+  const double px = (double)(i % W), py = (double)(i / W), z = (double)A.z1[i], eps = (double)1e-12f;
+  double h[3], r[3], d[3], pt[3], q[3], pr[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) h[a] = (double)A.K_inv[a * 3] * px + (double)A.K_inv[a * 3 + 1] * py + (double)A.K_inv[a * 3 + 2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) r[a] = (double)R1[0 * 3 + a] * h[0] + (double)R1[1 * 3 + a] * h[1] + (double)R1[2 * 3 + a] * h[2];
+  const double rn = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), e = rn + eps;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    d[a] = r[a] / e;
+    pt[a] = d[a] * z - ((double)R1[0 * 3 + a] * T1[0] + (double)R1[1 * 3 + a] * T1[1] + (double)R1[2 * 3 + a] * T1[2]);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) q[a] = (double)R2[a * 3] * pt[0] + (double)R2[a * 3 + 1] * pt[1] + (double)R2[a * 3 + 2] * pt[2] + (double)T2[a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) pr[a] = (double)A.K[a * 3] * q[0] + (double)A.K[a * 3 + 1] * q[1] + (double)A.K[a * 3 + 2] * q[2];
+  const double u = pr[0] / pr[2], v = pr[1] / pr[2];
+  const double ix = ((2.0 * u / (double)max(W - 1, 1) - 1.0 + 1.0) / 2.0) * (double)(W - 1);
+  const double iy = ((2.0 * v / (double)max(H - 1, 1) - 1.0 + 1.0) / 2.0) * (double)(H - 1);
+  if (!((ix > -2.0) && (ix < (double)W + 1.0) && (iy > -2.0) && (iy < (double)H + 1.0))) return 0.f;   // every corner outside (or NaN)
+  const double fx = floor(ix), fy = floor(iy), tx = ix - fx, ty = iy - fy;
+  const int x0 = (int)fx, y0 = (int)fy;
+  double val[2][2][3];
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const int x = x0 + dx, y = y0 + dy;
+      const bool in = inb(x, y, W, H);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) val[dy][dx][ch] = in ? (double)A.img2[(size_t)(y * W + x) * 3 + ch] : 0.0;
+    }
+  // d loss / d c2 = -sign(c1 - c2) scale; d c2 / d (ix, iy) of the bilinear sample (zero-padded corners)
+  double gix = 0.0, giy = 0.0;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const double c2 = (val[0][0][ch] * (1.0 - tx) + val[0][1][ch] * tx) * (1.0 - ty) + (val[1][0][ch] * (1.0 - tx) + val[1][1][ch] * tx) * ty;
+    const double df = (double)A.img1[(size_t)i * 3 + ch] - c2;
+    const double gc = (df > 0.0 ? -1.0 : (df < 0.0 ? 1.0 : 0.0)) * scale;
+    gix += gc * ((val[0][1][ch] - val[0][0][ch]) * (1.0 - ty) + (val[1][1][ch] - val[1][0][ch]) * ty);
+    giy += gc * ((val[1][0][ch] - val[0][0][ch]) * (1.0 - tx) + (val[1][1][ch] - val[0][1][ch]) * tx);
+  }
+  if (W == 1) gix = 0.0;
+  if (H == 1) giy = 0.0;
+  const double gpr[3] = {gix / pr[2], giy / pr[2], -(gix * u + giy * v) / pr[2]};
+  double gq[3], gpt[3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) gq[b] = (double)A.K[0 * 3 + b] * gpr[0] + (double)A.K[1 * 3 + b] * gpr[1] + (double)A.K[2 * 3 + b] * gpr[2];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) gpt[b] = (double)R2[0 * 3 + b] * gq[0] + (double)R2[1 * 3 + b] * gq[1] + (double)R2[2 * 3 + b] * gq[2];
+  // pt = d(R1) z + c1(R1, T1), c1_j = -sum_k R1[k][j] T1[k]: R1 through the normalised ray and through c1
+  const double dot = (gpt[0] * r[0] + gpt[1] * r[1] + gpt[2] * r[2]) * z;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double gr = gpt[c] * z / e - (rn > 0.0 ? dot * r[c] / (rn * e * e) : 0.0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[j * 3 + c] = (float)(h[j] * gr - gpt[c] * (double)T1[j]);                  // R1
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    acc[9 + a] = (float)(-((double)R1[a * 3] * gpt[0] + (double)R1[a * 3 + 1] * gpt[1] + (double)R1[a * 3 + 2] * gpt[2]));   // T1
+#pragma unroll
+    for (int b = 0; b < 3; ++b) acc[12 + a * 3 + b] = (float)(gq[a] * pt[b]);                                  // R2
+    acc[21 + a] = (float)gq[a];                                                                                // T2
+  }
+  return (float)(gpt[0] * d[0] + gpt[1] * d[1] + gpt[2] * d[2]);
 }
 
 // backward: g_loss (device scalar) -> g_z1[P] and per-block partials of the camera gradients [R1 9 | T1 3 | R2 9 | T2 3]
@@ -310,7 +400,7 @@ DISTR_GLOBAL void __launch_bounds__(256) k_warp_bwd(WarpArgs A, const float* __r
                                                   const float* __restrict__ g_loss, float* __restrict__ g_z1,
                                                   float* __restrict__ partial /*[nblk][24]*/) {
   __shared__ float lds[96];
-  const int P = A.H * A.W, W = A.W, H = A.H;
+  const int P = A.H * A.W;
   const int i = blockIdx.x * 256 + threadIdx.x;
   float acc[24];
 #pragma unroll
@@ -319,57 +409,8 @@ DISTR_GLOBAL void __launch_bounds__(256) k_warp_bwd(WarpArgs A, const float* __r
   if (i < P) {
     float R1[9], c1[3], R2[9], T2[3], T1[3];
     load_cam_pair(A, R1, c1, R2, T2, T1);
-    const WarpPix w = warp_pixel(A, i, R1, c1, R2, T2);
-    if (w.keep && w.b.ok) {
-      const float scale = g_loss[0] / (3.0f * fwd[1]);
-      // d loss / d c2[ch] = -sign(c1 - c2) * scale
-      float gc[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float df = A.img1[(size_t)i * 3 + ch] - w.c2[ch];
-        gc[ch] = (df > 0.f ? -1.f : (df < 0.f ? 1.f : 0.f)) * scale;
-      }
-      // d c2 / d (ix, iy) of the bilinear sample (zero-padded corners)
-      float val[2][2][3];
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-          const int x = w.b.x0 + dx, y = w.b.y0 + dy;
-          const bool in = inb(x, y, W, H);
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) val[dy][dx][ch] = in ? A.img2[(size_t)(y * W + x) * 3 + ch] : 0.f;
-        }
-      float gix = 0.f, giy = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        gix += gc[ch] * ((val[0][1][ch] - val[0][0][ch]) * (1.0f - w.b.ty) + (val[1][1][ch] - val[1][0][ch]) * w.b.ty);
-        giy += gc[ch] * ((val[1][0][ch] - val[0][0][ch]) * (1.0f - w.b.tx) + (val[1][1][ch] - val[0][1][ch]) * w.b.tx);
-      }
-      // (ix, iy) = (u, v) up to rounding; u = pr0 / pr2, v = pr1 / pr2
-      const float gpr[3] = {gix / w.pr[2], giy / w.pr[2], -(gix * w.u + giy * w.v) / w.pr[2]};
-      float gq[3], gpt[3];
-#pragma unroll
-      for (int b = 0; b < 3; ++b) gq[b] = A.K[0 * 3 + b] * gpr[0] + A.K[1 * 3 + b] * gpr[1] + A.K[2 * 3 + b] * gpr[2];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) acc[12 + a * 3 + b] += gq[a] * w.pt[b];      // R2
-        acc[21 + a] += gq[a];                                                    // T2
-      }
-#pragma unroll
-      for (int b = 0; b < 3; ++b) gpt[b] = R2[0 * 3 + b] * gq[0] + R2[1 * 3 + b] * gq[1] + R2[2 * 3 + b] * gq[2];
-      gz = gpt[0] * w.g.d[0] + gpt[1] * w.g.d[1] + gpt[2] * w.g.d[2];
-      // pt = d(R1) * z + c1(R1, T1)
-      const float gd[3] = {gpt[0] * w.z, gpt[1] * w.z, gpt[2] * w.z};
-      ray_backward_acc(w.g, gd, acc);                                            // R1 through the normalised ray
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc[k * 3 + j] += -gpt[j] * T1[k];           // c1_j = -sum_k R1[k][j] T1[k]
-        acc[9 + k] += -(R1[k * 3] * gpt[0] + R1[k * 3 + 1] * gpt[1] + R1[k * 3 + 2] * gpt[2]);
-      }
-    }
+    const WarpPix w = warp_pixel(A, i, R1, c1, R2, T2);   // the forward's float32 pixel: its keep flag is the kept set
+    if (w.keep) gz = warp_pixel_bwd64(A, i, R1, T1, R2, T2, (double)g_loss[0] / (3.0 * (double)fwd[1]), acc);
     if (g_z1) g_z1[i] = gz;
   }
   // 24 sums in 3 rounds of 8 (LDS budget)

@@ -1017,7 +1017,8 @@ def test_fused_warp_loss_matches_oracle_and_edge_cases(engine):
 def test_random_warp_losses_match_oracle(engine, seed):
     """Seeded random view pairs of a synthetic sphere (ragged sizes, camera pairs from near-identical to 60 degrees apart, sphere size and offset,
     depth-test threshold, off-centre intrinsics): distr_warp_loss_* against the torch restatement of renderer_warp.py:18-101 that G8 pins to the
-    reference -- kept set (<= 2 flips at the depth test), loss, sampled colours, gradients to the view-1 depth and the four camera tensors."""
+    reference -- kept set (<= 2 flips at the depth test), loss, sampled colours; then, with the ambiguous pixels cleared from mask1 on both sides, kept set (no
+    flip), loss, gradients to the view-1 depth and the four camera tensors on every seed."""
     import torch
     from oracle import loss_oracle
     from oracle.gen_synth import sphere_view, procedural_images
@@ -1046,28 +1047,40 @@ def test_random_warp_losses_match_oracle(engine, seed):
         assert keep.sum() == 0 and (np.isnan(loss) or loss == 0.0)
         return
     assert abs(loss - float(ol)) <= 1e-5 + 2e-3 * flips, (seed, loss, float(ol))
-    if flips == 0:
-        ol.backward()
-        # |a - b| has a kink where a colour channel of the two views agrees (near-identical cameras over a smooth image): the sign of a 1e-6
-        # difference is not a statement about either side -- those pixels are left out of the per-pixel gradient, and the camera sums are
-        # compared only when there is no such pixel
-        amb = ((np.abs(oc1.numpy() - oc2.numpy()) < 1e-4).any(axis=-1) & okeep.numpy().reshape(H, W)).reshape(-1)
-        # ... and the bilinear sample has a kink where the projected point sits on a pixel-grid line of view 2 (seed 319: x = 38.99999)
-        with torch.no_grad():
-            Kinv = torch.from_numpy(np.linalg.inv(np.asarray(K, np.float64)).astype(np.float32))
-            yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing='ij')
-            rays = torch.from_numpy(R1).t() @ (Kinv @ torch.stack([xx.reshape(-1), yy.reshape(-1), torch.ones(H * W)], 0))
-            rays = rays / (torch.norm(rays, p=2, dim=0, keepdim=True) + 1e-12)
-            pts = rays * torch.from_numpy(np.asarray(z1, np.float32)).reshape(-1)[None, :] + (-(torch.from_numpy(R1).t() @ torch.from_numpy(T1)))[:, None]
-            proj = torch.from_numpy(np.asarray(K, np.float32)) @ (torch.from_numpy(R2) @ pts + torch.from_numpy(T2)[:, None])
-            xy = (proj[:2] / proj[2]).numpy()
-        fr = np.abs(xy - np.round(xy))
-        amb |= (fr < 2e-3).any(axis=0) & okeep.numpy().reshape(-1)
-        gz, ref_gz = grads[0].reshape(-1), tz.grad.numpy().reshape(-1)
-        assert np.abs(gz - ref_gz)[~amb].max() <= 5e-4 * max(np.abs(ref_gz).max(), 1e-12), seed
-        if not amb.any():
-            for a, v in zip(grads[1:], (tR1, tT1, tR2, tT2)):
-                assert np.abs(a.reshape(-1) - v.grad.numpy().reshape(-1)).max() <= 5e-4 * max(np.abs(v.grad.numpy()).max(), 1e-12), seed
+    # |a - b| has a kink where a colour channel of the two views agrees (near-identical cameras over a smooth image): the sign of a 1e-6
+    # difference is not a statement about either side. An exact tie is: both sides give gradient 0 there (the checkerboard channel of
+    # procedural_images ties on a quarter to a third of the kept pixels), so only 0 < |c1 - c2| < 1e-4 is ambiguous
+    dc = np.abs(oc1.numpy() - oc2.numpy())
+    amb = (((dc > 0) & (dc < 1e-4)).any(axis=-1) & okeep.numpy().reshape(H, W)).reshape(-1)
+    # ... and the bilinear sample has a kink where the projected point sits on a pixel-grid line of view 2 (seed 319: x = 38.99999)
+    with torch.no_grad():
+        Kinv = torch.from_numpy(np.linalg.inv(np.asarray(K, np.float64)).astype(np.float32))
+        yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing='ij')
+        rays = torch.from_numpy(R1).t() @ (Kinv @ torch.stack([xx.reshape(-1), yy.reshape(-1), torch.ones(H * W)], 0))
+        rays = rays / (torch.norm(rays, p=2, dim=0, keepdim=True) + 1e-12)
+        pts = rays * torch.from_numpy(np.asarray(z1, np.float32)).reshape(-1)[None, :] + (-(torch.from_numpy(R1).t() @ torch.from_numpy(T1)))[:, None]
+        proj = torch.from_numpy(np.asarray(K, np.float32)) @ (torch.from_numpy(R2) @ pts + torch.from_numpy(T2)[:, None])
+        xy = (proj[:2] / proj[2]).numpy()
+    fr = np.abs(xy - np.round(xy))
+    amb |= (fr < 2e-3).any(axis=0) & okeep.numpy().reshape(-1)
+    amb |= keep.astype(bool) != okeep.numpy()             # a pixel the two sides decide differently at the depth test (<= 2, above)
+    # the ambiguous pixels leave mask1 on BOTH sides and the pair is run again: every output is then compared on every seed, the four
+    # camera sums included. At most 3 % of the valid pixels may go (1.0 .. 1.6 % of the kept pixels on seeds 0 .. 11)
+    assert amb.sum() <= 0.03 * int(g['mask1'].astype(bool).sum()), (seed, int(amb.sum()))
+    g2 = dict(g, mask1=np.where(amb, 0, g['mask1'].reshape(-1)).astype(np.uint8).reshape(g['mask1'].shape))
+    loss, keep, c1, c2, grads = _warp_hip(engine, g2, 1.0)
+    tz, tR1, tT1, tR2, tT2 = t('zdepth1'), t('R1'), t('T1'), t('R2'), t('T2')
+    ol, okeep, oc1, oc2 = loss_oracle.warp_loss(K, H, W, tz, torch.from_numpy(g2['mask1']), torch.from_numpy(z2), torch.from_numpy(img1),
+                                                torch.from_numpy(img2), tR1, tT1, tR2, tT2, thres)
+    assert int((keep.astype(bool) != okeep.numpy()).sum()) == 0, seed
+    if okeep.sum() == 0:
+        return
+    assert abs(loss - float(ol)) <= 1e-5, (seed, loss, float(ol))
+    ol.backward()
+    gz, ref_gz = grads[0].reshape(-1), tz.grad.numpy().reshape(-1)
+    assert np.abs(gz - ref_gz).max() <= 5e-4 * max(np.abs(ref_gz).max(), 1e-12), seed
+    for a, v in zip(grads[1:], (tR1, tT1, tR2, tT2)):
+        assert np.abs(a.reshape(-1) - v.grad.numpy().reshape(-1)).max() <= 5e-4 * max(np.abs(v.grad.numpy()).max(), 1e-12), seed
 
 
 class _Cam(object):
