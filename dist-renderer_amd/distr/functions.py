@@ -707,10 +707,11 @@ def _train_weight_struct(weights, C_len):
     return tw
 
 
-def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None):
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None):
     """Layer-wise decode_sdf of one segmented list of at most 64 segments (distr_train_forward): weights = [W0..W8, b0..b8] f32 device
     tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
     A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed.
+    ws, out (tests): a uint8 device tensor to use as the workspace and an f32 (sum counts, 1) tensor for sdf, instead of fresh ones.
     dropout: None, or (layer_mask, threshold, scale, seed, segment_base) -- train_dropout_params(...) + (seed, global index of segment 0)
     (distr_train_forward_dropout); the saved activations are then those behind the dropout, and train_backward follows."""
     counts = [int(c) for c in counts]
@@ -734,9 +735,13 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
         raise binding.DistrError('decode_sdf_train: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
                                  'more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient follows the batch)'
                                  % (x.shape[0], need, train_max_bytes()))
-    ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
     stride = 0 if lat.shape[0] == 1 else C_len
-    out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.shape[0]:
+        raise ValueError('train_forward: ws is a contiguous uint8 tensor, out a contiguous f32 tensor of %d values' % x.shape[0])
     p = binding.ptr
     td = _train_dropout_struct(dropout)
     if td is None:
@@ -748,15 +753,21 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist, dropout)
 
 
-def train_backward(saved, g_sdf):
+def train_backward(saved, g_sdf, out=None):
     """Backward of train_forward (distr_train_backward): g_sdf (sum counts,) -> ([g_W0..g_W8, g_b0..g_b8], g_latent (S, C): one row per
-    segment, also for a shared code)."""
+    segment, also for a shared code). out (tests): (the eighteen gradient tensors, g_latent) to write into instead of fresh ones."""
     ctx, dev = saved.ctx, saved.ws.device
     gs = _f32c(g_sdf, dev).reshape(-1)
     if gs.numel() != sum(saved.counts):
         raise ValueError('g_sdf has %d entries for %d points' % (gs.numel(), sum(saved.counts)))
-    grads = [torch.empty_like(w) for w in saved.weights]
-    g_lat = torch.empty(len(saved.counts), saved.latent_size, dtype=torch.float32, device=dev)
+    if out is None:
+        grads = [torch.empty_like(w) for w in saved.weights]
+        g_lat = torch.empty(len(saved.counts), saved.latent_size, dtype=torch.float32, device=dev)
+    else:
+        grads, g_lat = out
+        if [(g.shape, g.dtype, g.is_contiguous()) for g in grads] != [(w.shape, torch.float32, True) for w in saved.weights] \
+                or (g_lat.shape, g_lat.dtype, g_lat.is_contiguous()) != ((len(saved.counts), saved.latent_size), torch.float32, True):
+            raise ValueError('train_backward: out is (eighteen contiguous f32 tensors of the weights\' shapes, g_latent (S, C))')
     tg = binding.TrainGrads()
     for l in range(9):
         tg.g_W[l] = grads[l].data_ptr()

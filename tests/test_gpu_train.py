@@ -4,7 +4,8 @@ References: decode_sdf_batch (the fused tiles) for the values, and for the gradi
 run WITH THE GATES THE GPU RUN SAVED, so that both differentiate the same piecewise-linear function and no ReLU-side carve-out is needed
 (tests/test_train_host.py pins the restatement to the float64 torch Decoder). Bars: 2e-6 on sdf (G11's), 1e-4 of a tensor's largest entry
 on gradients (the project's bar for a different f32 summation order), per row for the code gradient so that a wrong small row cannot
-hide. Shapes are the smallest at which each mechanism can go wrong: segments [1, 64, 65, 0, 130, 63] (block -> segment map, padded rows,
+hide, and also per block of a tensor (train_restatement.gradient_blocks: the latent, xyz and activation columns of g_W0 / g_W4 come from
+different kernels). The reduction order itself is pinned byte for byte by tests/test_gpu_train_edges.py. Shapes are the smallest at which each mechanism can go wrong: segments [1, 64, 65, 0, 130, 63] (block -> segment map, padded rows,
 an empty segment), a shared code, one list of 2 L + 1 rows (three K slabs, the last with a single real row), 65 segments (two chunks).
 """
 import ctypes as C
@@ -63,6 +64,14 @@ def _assert_gradients(got_W, got_b, got_rows, ref_W, ref_b, ref_rows, sizes, tag
             rel = (a.double() - b).abs().max().item() / top
             worst = max(worst, rel)
             assert rel <= 1e-4, (tag, name, rel)
+    # the same bar per block: the latent, xyz and activation columns of g_W0 / g_W4 come from different kernels, and a small block
+    # must not hide behind a large one (tests/train_restatement.py::gradient_blocks)
+    import train_restatement as tr
+    blocks = tr.blockwise_residuals([t.cpu() for t in list(got_W) + list(got_b)], list(ref_W) + list(ref_b), got_W[0].shape[1] - 3)
+    for name, rel, top in blocks:
+        assert rel <= 1e-4, (tag, 'block', name, rel, top)
+    worst_block = max(blocks, key=lambda t: t[1])
+    print('%s: worst block %s, %.3e of its largest entry' % (tag, worst_block[0], worst_block[1]))
     for s, a, b in _segments(sizes):
         if a == b:
             assert not got_rows[s].any(), (tag, 'the empty segment has a code gradient')

@@ -46,6 +46,29 @@ def gradients(Ws, bs, codes, pts, counts, w, clamp=None, gates=None):
     return y.detach(), [z.detach() for z in pre], [zero(t) for t in W64], [zero(t) for t in b64], zero(c64)
 
 
+def gradient_blocks(Cn):
+    """The parts of the eighteen gradients that different kernels write, as (name, index into [g_W0..g_W8, g_b0..g_b8], column slice):
+    in g_W0 and g_W4 the latent columns and the xyz columns come from the column-sum kernels, the activation columns from the GEMM.
+    A residual is judged against the largest entry of its own block, so that a small block cannot hide behind a large one."""
+    n3 = 509 - Cn
+    blocks = [('g_W0 latent', 0, slice(0, Cn)), ('g_W0 xyz', 0, slice(Cn, Cn + 3)),
+              ('g_W4 activations', 4, slice(0, n3)), ('g_W4 latent', 4, slice(n3, 509)), ('g_W4 xyz', 4, slice(509, 512))]
+    blocks += [('g_W%d' % l, l, slice(None)) for l in (1, 2, 3, 5, 6, 7, 8)]
+    return blocks + [('g_b%d' % l, 9 + l, slice(None)) for l in range(9)]
+
+
+def blockwise_residuals(got, ref, Cn):
+    """got, ref: [g_W0..g_W8, g_b0..g_b8] (tensors or arrays). [(name, max |got - ref| / max |ref| of the block, max |ref|)]; a block whose
+    reference is all zero reports 0 when got is all zero there and inf otherwise."""
+    out = []
+    for name, i, cols in gradient_blocks(Cn):
+        a, b = np.asarray(got[i], dtype=np.float64)[..., cols], np.asarray(ref[i], dtype=np.float64)[..., cols]
+        top = np.abs(b).max()
+        err = np.abs(a - b).max()
+        out.append((name, (err / top) if top > 0 else (0.0 if err == 0 else np.inf), top))
+    return out
+
+
 def clamped_l1(sdf, target, clamp):
     return (torch.clamp(sdf, -clamp, clamp) - torch.clamp(target, -clamp, clamp)).abs().mean()
 
