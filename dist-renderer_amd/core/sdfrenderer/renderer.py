@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from distr import binding, functions
+from distr import binding, decoder_pack, functions
 
 
 def default_arith():
@@ -27,7 +27,8 @@ class SDFRenderer(object):
     # reference: renderer.py:13
     def __init__(self, decoder, intrinsic, img_hw=None, transform_matrix=None, march_step=50, buffer_size=5,
                  ray_marching_ratio=1.5, use_depth2normal=False, max_sample_dist=0.2, radius=1.0, threshold=5e-5,
-                 scale_list=[4, 2, 1], march_step_list=[3, 3, -1], use_gpu=True, is_eval=True, arith=None, normal_decoder_grad=False):
+                 scale_list=[4, 2, 1], march_step_list=[3, 3, -1], use_gpu=True, is_eval=True, arith=None, decoder_grad=False,
+                 normal_decoder_grad=False):
         # arith (not in the reference): 'f32' = exact f32 decoder evaluations (default); 'bf16x6' / 'f16x3' = the opt-in split-bf16 /
         # split-f16 march tiles (values within ~1e-6, 1.5x / 2x the step rate, no cluster tiles: for large dense renders; f16x3 only for
         # decoders inside the f16 range, see distr_render_stats.f16_overflows); None = default_arith(); also settable later (self.arith)
@@ -35,6 +36,11 @@ class SDFRenderer(object):
         # (normalize_normal=False) through the decoder's second path (decode_sdf_gradient with create_graph=True, decoder_utils.py:76-92),
         # the term the backward omits by default (DESIGN.md sections 5 and 8d); also settable later (self.normal_decoder_grad)
         self.normal_decoder_grad = bool(normal_decoder_grad)
+        # decoder_grad (not in the reference, where autograd simply does it): render / render_depth / render_depth_batch also back-propagate
+        # to the decoder's parameters that require grad -- fine-tuning the prior on image losses (zdepth, depth, min_sdf, normals from depth).
+        # The backward then exports its sample list and runs the layer-wise train path on it: ONE HOST SYNC per backward, not capturable
+        # into a graph; off (the default) nothing changes. Also settable later (self.decoder_grad)
+        self.decoder_grad = bool(decoder_grad)
         if arith is None:
             arith = default_arith()
         if arith not in binding.ARITH:
@@ -105,6 +111,20 @@ class SDFRenderer(object):
         """Packed decoder of this renderer's module; follows later parameter updates of the live module (load_state_dict,
         fine-tuning steps, .to()) like the reference, which evaluates the module itself on every call."""
         return functions.get_engine(self.decoder, self.device)
+
+    def _decoder_weights(self):
+        """W0..W8, b0..b8 of the module on its autograd graph (weight norm folded there) when this call back-propagates to the decoder:
+        decoder_grad set, grad enabled and a decoder parameter that requires grad; None otherwise."""
+        if not self.decoder_grad or not torch.is_grad_enabled() or not any(p.requires_grad for p in self.decoder.parameters()):
+            return None
+        if self.normal_decoder_grad:
+            raise NotImplementedError('decoder_grad together with normal_decoder_grad: the second path of the normals has no weight gradient '
+                                      'here (DESIGN.md section 8h)')
+        if self.arith != 'f32':
+            raise NotImplementedError("decoder_grad: arith='f32' only (this renderer: %r)" % (self.arith,))
+        functions._check_eval(self.decoder)
+        Ws, bs = decoder_pack.effective_weights_torch(self.decoder)
+        return Ws + bs
 
     # ---- small accessors (renderer.py:61-68)
     def get_intrinsic(self):
@@ -198,7 +218,9 @@ class SDFRenderer(object):
             no_grad_depth, no_grad_mask, no_grad_camera = True, True, True
         cfg = self._cfg(clamp_dist, self._check_marcher(ray_marching_type), use_transform, want_normal=False,
                         no_grad_depth=no_grad_depth, no_grad_mask=no_grad_mask, no_grad_camera=no_grad_camera)
-        zdepth, mask, min_sdf, _, _ = functions.render_call(self._engine, cfg, latent, R, T)
+        # (decoder_grad: with all three no_grad flags nothing of this render is on the graph, the decoder included)
+        weights = None if (no_grad_depth and no_grad_mask and no_grad_camera) else self._decoder_weights()
+        zdepth, mask, min_sdf, _, _ = functions.render_call(self._engine, cfg, latent, R, T, weights=weights)
         self._last = (cfg, zdepth)
         if no_grad_depth:
             zdepth = zdepth.detach()
@@ -226,7 +248,7 @@ class SDFRenderer(object):
                         no_grad_depth=all(ngd), no_grad_mask=all(ngm), no_grad_camera=all(ngc))
         flags = [(0 if ngd[v] else binding.VIEW_GRAD_DEPTH) | (0 if ngm[v] else binding.VIEW_GRAD_MASK) |
                  (0 if ngc[v] else binding.VIEW_GRAD_CAMERA) for v in range(B)]
-        zdepth, mask, min_sdf, _, _ = functions.render_batch_call(self._engine, cfg, latent, Rs, Ts, flags)
+        zdepth, mask, min_sdf, _, _ = functions.render_batch_call(self._engine, cfg, latent, Rs, Ts, flags, weights=self._decoder_weights())
         # (a view rendered with no_grad_depth ignores the upstream gradient of its Zdepth row in the backward kernel: the
         # per-view flag does what the reference's .detach() does, renderer.py:876-877)
         # min_sdf of a view with BOTH no_grad_mask and no_grad_camera is detached by render_depth (renderer.py:388-389 + 863: with the
@@ -276,8 +298,10 @@ class SDFRenderer(object):
         if profile:
             self._engine.ctx.profile_enable(True)
         # (no_grad_normal detaches the normals inside render_normal, renderer.py:908-909: the decoder-path term goes with them)
+        weights = None if (no_grad_depth and no_grad_mask and no_grad_camera) else self._decoder_weights()
         zdepth, mask, min_sdf, depth, normal = functions.render_call(self._engine, cfg, latent, R, T,
-                                                                     normal_decoder_grad=self.normal_decoder_grad and not no_grad_normal)
+                                                                     normal_decoder_grad=self.normal_decoder_grad and not no_grad_normal,
+                                                                     weights=weights, normals_detached=no_grad_normal)
         if profile:
             n, ms = self._engine.ctx.profile_read()
             self._engine.ctx.profile_enable(False)

@@ -282,10 +282,10 @@ int check_cfg(distr_ctx* ctx, const distr_render_cfg* c) {
                 c->buffer_size, coarse_rows + fine, c->march_step);
   if (!(c->radius > 0.f) || !(c->threshold >= 0.f)) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad radius/threshold");
   if (c->arith != DISTR_ARITH_F32 && c->arith != DISTR_ARITH_BF16X6 && c->arith != DISTR_ARITH_F16X3) return fail(ctx, DISTR_ERR_INVALID_ARG, "unknown arith %d", c->arith);
-  if (c->arith != DISTR_ARITH_F32 && ctx->has_decoder && ctx->D.nlat != LAT)
+  if (c->arith != DISTR_ARITH_F32 && ctx && ctx->has_decoder && ctx->D.nlat != LAT)
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith %s: the split arithmetics are built for code length %d only (this decoder: %d); use f32",
                 c->arith == DISTR_ARITH_BF16X6 ? "bf16x6" : "f16x3", LAT, ctx->D.nlat);
-  if (c->arith == DISTR_ARITH_F16X3 && ctx->has_decoder && !ctx->h3_ok)
+  if (c->arith == DISTR_ARITH_F16X3 && ctx && ctx->has_decoder && !ctx->h3_ok)
     return fail(ctx, DISTR_ERR_UNSUPPORTED, "arith f16x3: %s; use bf16x6 or f32 for this decoder", ctx->h3_why.c_str());
   if (c->rows != 0) {
     if (c->rows < 0 || c->row0 < 0 || c->row0 + c->rows > c->H) return fail(ctx, DISTR_ERR_INVALID_ARG, "row band [%d,+%d) outside the %d-row image", c->row0, c->rows, c->H);
@@ -491,6 +491,24 @@ size_t bwd_bytes(const distr_render_cfg& c) {
   const size_t b = ((smax * sizeof(Sample) + 255) & ~(size_t)255) + tiles * PSTRIDE * sizeof(float) + nchunks * PSTRIDE * sizeof(float) +
                    nblk * (2 * sizeof(int32_t) + 16 * sizeof(float)) + 2048;
   return (b + 255) & ~(size_t)255;
+}
+
+// The backward workspace of view 0 of a batch, carved (view b: bstride = bwd_bytes further): the one layout of render_backward_impl,
+// which fills it, and distr_render_samples_export_batch, which reads the sample list back out of it. P: pixels of the rendered band.
+struct BwdCarve { BwdWs W; size_t smax; int nblk; unsigned nchunks; };
+BwdCarve carve_bwd(const distr_render_cfg& c, int P, void* ws_bwd) {
+  BwdCarve b;
+  b.smax = (size_t)P * c.buffer_size + 1;
+  Carver cv(ws_bwd);
+  b.W.bstride = (int64_t)bwd_bytes(c);
+  b.W.samples = cv.take<Sample>(b.smax);
+  const unsigned prows = (unsigned)((b.smax + 31) / 32) + 256;     // partial rows (sized for 32-sample tiles: bwd_bytes)
+  b.W.partial = cv.take<float>((size_t)prows * PSTRIDE);
+  b.nblk = (P + 255) / 256;
+  b.nchunks = (prows + BWD_CHUNK - 1) / BWD_CHUNK;
+  b.W.chunk_part = cv.take<float>((size_t)b.nchunks * PSTRIDE);
+  b.W.BB.cnt = cv.take<int32_t>(b.nblk); b.W.BB.off = cv.take<int32_t>(b.nblk); b.W.BB.acc = cv.take<float>((size_t)b.nblk * 16);
+  return b;
 }
 
 inline dim3 grid1(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
@@ -1301,19 +1319,13 @@ int render_backward_impl(distr_ctx* ctx, const distr_render_cfg* cfg, int nviews
   const DecoderDev& D = ctx->D;
   const int P = V.P;
   const unsigned NV = (unsigned)nviews;
-  const size_t smax = (size_t)P * cfg->buffer_size + 1;
   constexpr int TILE = 64;
-  Carver cv(ws_bwd);
-  BwdWs W;
-  W.bstride = (int64_t)bsingle;
-  W.samples = cv.take<Sample>(smax);
+  const BwdCarve bc = carve_bwd(*cfg, P, ws_bwd);
+  const BwdWs& W = bc.W;
+  const size_t smax = bc.smax;
   const unsigned tiles = (unsigned)((smax + TILE - 1) / TILE);
-  const unsigned prows = (unsigned)((smax + 31) / 32) + 256;     // partial rows (sized for 32-sample tiles: bwd_bytes)
-  W.partial = cv.take<float>((size_t)prows * PSTRIDE);
-  const int nblk = (P + 255) / 256;
-  const unsigned nchunks = (prows + BWD_CHUNK - 1) / BWD_CHUNK;
-  W.chunk_part = cv.take<float>((size_t)nchunks * PSTRIDE);
-  W.BB.cnt = cv.take<int32_t>(nblk); W.BB.off = cv.take<int32_t>(nblk); W.BB.acc = cv.take<float>((size_t)nblk * 16);
+  const int nblk = bc.nblk;
+  const unsigned nchunks = bc.nchunks;
   hipLaunchKernelGGL(k_bwd_prep<false>, dim3(nblk, NV), dim3(256), 0, s, V, g_zdepth, g_min_sdf, g_depth, g_normal, W);
   LAUNCH_CHECK("k_bwd_prep<count>");
   hipLaunchKernelGGL(k_bwd_scan, dim3(NV), dim3(256), 0, s, V, W, nblk);
@@ -1402,6 +1414,36 @@ int distr_render_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int
   EntryGuard guard_(ctx);
   return render_backward_impl(ctx, cfg, nviews, ws, ws_bytes, g_zdepth, g_min_sdf, g_depth, g_normal, g_latent, g_R, g_T, ws_bwd,
                               ws_bwd_bytes, stream);
+}
+
+// ---- the backward's gradient-sample list, written out (include/distr_render_train.h)
+int64_t distr_render_max_samples(const distr_render_cfg* cfg) {
+  if (check_cfg(nullptr, cfg)) return 0;
+  return (int64_t)band_rows(*cfg) * cfg->W * cfg->buffer_size + 1;
+}
+
+int distr_render_samples_export_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const void* ws_fwd, size_t ws_fwd_bytes,
+                                      const void* ws_bwd, size_t ws_bwd_bytes, float* xyz, float* coef, int32_t* src, int64_t cap,
+                                      int32_t* counts_dev, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
+  if (!cfg->save_for_backward) return fail(ctx, DISTR_ERR_INVALID_ARG, "sample export: the forward was run with save_for_backward=0");
+  if (!ws_fwd || !ws_bwd) return fail(ctx, DISTR_ERR_INVALID_ARG, "null workspace");
+  if (!xyz || !coef || !counts_dev) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  View V;
+  const size_t single = make_view(*cfg, const_cast<void*>(ws_fwd), V, ctx->save_masks, nviews);
+  const BwdCarve bc = carve_bwd(*cfg, V.P, const_cast<void*>(ws_bwd));
+  if (cap < (int64_t)bc.smax) return fail(ctx, DISTR_ERR_INVALID_ARG, "sample export: cap %lld is below the %zu rows a view's list can hold", (long long)cap, bc.smax);
+  if (ws_fwd_bytes < single * nviews) return fail(ctx, DISTR_ERR_WORKSPACE, "forward workspace too small: %zu < %zu", ws_fwd_bytes, single * nviews);
+  if (ws_bwd_bytes < (size_t)bc.W.bstride * nviews) return fail(ctx, DISTR_ERR_WORKSPACE, "backward workspace too small: %zu < %zu", ws_bwd_bytes, (size_t)bc.W.bstride * nviews);
+  // (a list never holds more than smax <= cap rows: the grid covers those, whatever stride the caller chose)
+  hipLaunchKernelGGL(k_samples_export, dim3((unsigned)((bc.smax + 255) / 256), (unsigned)nviews), dim3(256), 0, (hipStream_t)stream, V, bc.W, xyz, coef,
+                     src, cap, counts_dev);
+  LAUNCH_CHECK("k_samples_export");
+  return DISTR_OK;
 }
 
 int distr_render_normal(distr_ctx* ctx, const distr_render_cfg* cfg, const float* latent, const float* R, const float* T,

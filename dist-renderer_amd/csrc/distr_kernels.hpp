@@ -284,6 +284,19 @@ __device__ __forceinline__ CamRegs load_cam(const Consts* C) {
   return k;
 }
 
+// The point of a gradient sample from its source and depth: the centre of its pixel (or coarse ray) -> ray -> camera position + ray * zb,
+// through M. k_bwd (which differentiates the decoder there) and k_samples_export (which writes the list out) share it. src < 0 (the pad
+// sample): p is left as it is -- the callers preset the origin.
+__device__ __forceinline__ void sample_point(const View& V, int32_t src, float zb, float* p) {
+  if (src < 0) return;
+  const int lvl = src_level(src), ray = src_ray(src);
+  const CamRegs cam = load_cam(V.C);
+  float cx, cy;
+  level_center(level_sel(V, lvl), ray, cx, cy);
+  const RayGeo g = make_ray(V.cfg.K_inv, cam.R, cx, cy);
+  make_point(V.cfg.M, cam.c, g.d, zb, p);
+}
+
 // XC = true: write-through stores (sc1: nothing stays dirty in this XCD's L2) and L1-bypassing loads -- the fence-free hand-off form of
 // MI355X_MICROARCH.md ("sc1 stores AND sc1 loads"). Measured for the per-ray march state inside the persistent tail launch (k_tail) and NOT
 // used there: every step got slower than with plain accesses + one release / acquire fence per tile (137 x 137 / 100 steps: 7.94 against
@@ -2216,14 +2229,7 @@ __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_bwd(Bw
         } else {
           if (MODE == BWD_POINTGRAD) { sm.src = pix_list[r]; sm.zb = zdepth[sm.src]; sm.coef = 1.0f; }
           else sm = samples[r];
-          if (sm.src >= 0) {
-            const int lvl = src_level(sm.src), ray = src_ray(sm.src);
-            const CamRegs cam = load_cam(V.C);
-            float cx, cy;
-            level_center(level_sel(V, lvl), ray, cx, cy);
-            const RayGeo g = make_ray(V.cfg.K_inv, cam.R, cx, cy);
-            make_point(V.cfg.M, cam.c, g.d, sm.zb, p);
-          }
+          sample_point(V, sm.src, sm.zb, p);
         }
       }
       S.xyz[tid] = p[0]; S.xyz[TILE + tid] = p[1]; S.xyz[2 * TILE + tid] = p[2];
@@ -2570,6 +2576,26 @@ DISTR_GLOBAL void __launch_bounds__(256) k_bwd_scan(View V0, BwdWs W0, int nblk)
     samples[V.C->cnt_samples] = sm;
     V.C->cnt_samples = V.C->cnt_samples + 1;
   }
+}
+
+// The list k_bwd walked, written out (distr_render_samples_export_batch): grid (blocks of 256 list positions, nviews). Row r < count of
+// view v: its point (sample_point, as k_bwd<BWD_FULL> builds it), coefficient and encoded source, at [v][r] of arrays of `cap` rows per
+// view; rows at or beyond the count are not touched. counts[v] = the view's count. Reads both workspaces, changes neither.
+DISTR_GLOBAL void __launch_bounds__(256) k_samples_export(View V0, BwdWs W0, float* __restrict__ xyz, float* __restrict__ coef,
+                                                          int32_t* __restrict__ src, int64_t cap, int32_t* __restrict__ counts) {
+  const View V = view_at(V0, blockIdx.y);
+  const Sample* samples = bws_at(W0, blockIdx.y).samples;
+  const int32_t count = V.C->cnt_samples;
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[blockIdx.y] = count;
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= count || r >= cap) return;
+  const Sample sm = samples[r];
+  float p[3] = {0.f, 0.f, 0.f};
+  sample_point(V, sm.src, sm.zb, p);
+  const int64_t o = (int64_t)blockIdx.y * cap + r;
+  xyz[o * 3] = p[0]; xyz[o * 3 + 1] = p[1]; xyz[o * 3 + 2] = p[2];
+  coef[o] = sm.coef;
+  if (src) src[o] = sm.src;
 }
 
 // column sums of the tile partials over one chunk of tiles -> chunk_part[chunk][col] (fixed order, no atomics)

@@ -46,6 +46,8 @@ TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset',
                  'distr_train_dropout_keep']
 # the ordered live list seen from outside (include/distr_live_order.h, included by distr.h): block enumeration, k-step counts, list read-back
 LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list']
+# the render backward's gradient-sample list, written out (include/distr_render_train.h, included by distr.h): weight gradients through render
+RENDER_TRAIN_EXPORTS = ['distr_render_max_samples', 'distr_render_samples_export_batch']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -166,7 +168,8 @@ class RenderStats(_Sized):
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_split.hpp', 'distr_losses.hpp',
            'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp', 'distr_philox.hpp')
-HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h', 'distr_live_order.h')                    # include/: the C ABI
+HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h', 'distr_live_order.h',
+           'distr_render_train.h')                    # include/: the C ABI
 INST_GROUPS = 10           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -427,6 +430,9 @@ def lib():
             L.distr_train_forward_dropout.argtypes = L.distr_train_forward.argtypes + [td]
             L.distr_train_backward_dropout.argtypes = L.distr_train_backward.argtypes + [td]
             L.distr_train_dropout_keep.argtypes = [C.c_uint64, C.c_uint32, i32, i64, i64, i32]
+            L.distr_render_max_samples.argtypes = [C.POINTER(RenderCfg)]
+            L.distr_render_max_samples.restype = i64
+            L.distr_render_samples_export_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, vp, C.c_size_t, vp, C.c_size_t, fp, fp, vp, i64, vp, vp]
             _lib = L
     return _lib
 

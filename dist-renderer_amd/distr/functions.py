@@ -253,10 +253,16 @@ class RenderBatchFunction(torch.autograd.Function):
     per step for all views: the views' latency-bound tails overlap). `view_flags`: per-view DISTR_VIEW_GRAD_* (the no_grad_* options of
     each view). `normal_decoder_grad`: the backward also returns the term of a normal-map loss that reaches code and camera through the
     decoder (distr_render_normal_grad_backward_batch), added to the gradients of the main backward; without it every
-    byte is what it was before the option existed."""
+    byte is what it was before the option existed. `weights` (optional, trailing): W0..W8, b0..b8 of the decoder the engine was packed
+    from (decoder_pack.effective_weights_torch) -- the backward then also returns their eighteen gradients (render_weight_grads,
+    DESIGN.md section 8h): it exports the backward's sample list, reads the B counts on the host (ONE HOST SYNC per backward: such a
+    backward cannot be captured into a graph) and runs the layer-wise train path on the list. The gradients of codes and cameras are
+    those of the fused backward either way; without weights every byte is what it was before the option existed."""
 
     @staticmethod
-    def forward(ctx, latent, R, T, engine, cfg, view_flags, normal_decoder_grad=False):
+    def forward(ctx, latent, R, T, engine, cfg, view_flags, normal_decoder_grad=False, *weights):
+        if weights and len(weights) != 18:
+            raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
         dev = engine.device
         H, W = cfg.band_rows, cfg.W
         P = H * W
@@ -285,6 +291,9 @@ class RenderBatchFunction(torch.autograd.Function):
             p(depth) if cfg.want_normal else None, p(normal) if cfg.want_normal else None, p(ws), ws.numel(), engine.ctx.stream()))
         _check_f16_range(engine, cfg, ws, B, fwd_bytes, needs_grad=any(ctx.needs_input_grad[:3]))
         ctx.engine, ctx.cfg, ctx.ws, ctx.bwd_bytes, ctx.B, ctx.shared = engine, cfg, ws, bwd_bytes, B, shared
+        ctx.nweights = len(weights)
+        if weights:
+            ctx.save_for_backward(lat, *weights)       # (the codes as the forward used them: the train path decodes with them again)
         ctx.generation = engine.generation
         ctx.shapes = (latent.shape, R.shape, T.shape)
         ctx.in_meta = tuple((t.device, t.dtype) for t in (latent, R, T))
@@ -314,10 +323,15 @@ class RenderBatchFunction(torch.autograd.Function):
             # the decoder-path term of the normal-map loss: outputs of its own, added here (the main backward's reduction order stays)
             n_lat, n_R, n_T = normal_grad_term(engine, cfg, ws, gn, B, ctx.flags)
             g_lat, g_R, g_T = g_lat + n_lat, g_R + n_R, g_T + n_T
+        g_weights = ()
+        if ctx.nweights:
+            lat, weights = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+            grads, _ = render_weight_grads(engine, cfg, ws, ws_b, B, weights, lat, want_latent=False)
+            g_weights = tuple(g.reshape(w.shape).to(device=w.device, dtype=w.dtype) for g, w in zip(grads, weights))
         ls, rs, ts = ctx.shapes
         if ctx.shared and B > 1:
             g_lat = g_lat.sum(0)                   # one shape code rendered from B cameras: the views' gradients add up (fixed order)
-        return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None, None, None)
+        return tuple(g.reshape(sh).to(device=d, dtype=dt) for g, sh, (d, dt) in zip((g_lat, g_R, g_T), (ls, rs, ts), ctx.in_meta)) + (None, None, None, None) + g_weights
 
 
 def normal_grad_term(engine, cfg, ws, g_normal, B, view_flags=None):
@@ -343,10 +357,32 @@ def normal_grad_applies(cfg):
     return bool(cfg.want_normal) and not cfg.use_depth2normal and not cfg.normalize_normal
 
 
-def render_batch_call(engine, cfg, latent, R, T, view_flags=None, normal_decoder_grad=False):
+def check_render_weights(cfg, weights, normal_decoder_grad=False, normals_detached=False):
+    """What weight gradients through render are defined for; NotImplementedError naming the reason otherwise.
+    normals_detached: the caller keeps the decoder out of the autograd normals (render(no_grad_normal=True), renderer.py:908-909)."""
+    if len(weights) != 18:
+        raise ValueError('weights: W0..W8, b0..b8 (decoder_pack.effective_weights_torch), 18 tensors, got %d' % len(weights))
+    if cfg.arith != binding.ARITH['f32']:
+        raise NotImplementedError("decoder_grad: arith='f32' only (the layer-wise train path is f32; the split arithmetics' sample lists "
+                                  "belong to other ReLU patterns)")
+    if cfg.rows != 0:
+        raise NotImplementedError('decoder_grad: row bands are not implemented (render the whole image)')
+    if cfg.want_normal and not cfg.use_depth2normal and not normals_detached:
+        raise NotImplementedError('decoder_grad: the weight gradient of autograd normals (d(grad_x f)/dW, not zero for a ReLU decoder) is not '
+                                  'implemented; normals from depth (use_depth2normal=True) are supported, and so is no_grad_normal=True')
+    if normal_decoder_grad:
+        raise NotImplementedError('decoder_grad together with normal_decoder_grad: the second path of the normals has no weight gradient here')
+
+
+def render_batch_call(engine, cfg, latent, R, T, view_flags=None, weights=None, normals_detached=False, normal_decoder_grad=False):
     """Batched render_call: R (B,3,3), T (B,3), latent (1,C) (shared) or (B,C). normal_decoder_grad: see RenderBatchFunction; where the
-    term is zero or absent (normal_grad_applies) the option does nothing."""
-    need_bwd = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in (latent, R, T))
+    term is zero or absent (normal_grad_applies) the option does nothing. weights: None, or W0..W8, b0..b8 of the engine's decoder on
+    the autograd graph (decoder_pack.effective_weights_torch): the backward also returns their gradients (one host sync per backward,
+    see RenderBatchFunction; check_render_weights names what is refused, normals_detached is its argument)."""
+    weights = list(weights) if weights is not None else []
+    if weights:
+        check_render_weights(cfg, weights, normal_decoder_grad, normals_detached)
+    need_bwd = torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in [latent, R, T] + weights)
     cfg = cfg.clone()
     cfg.save_for_backward = 1 if need_bwd else 0
     if normal_decoder_grad and normal_grad_applies(cfg):
@@ -354,14 +390,15 @@ def render_batch_call(engine, cfg, latent, R, T, view_flags=None, normal_decoder
             raise NotImplementedError('normal_decoder_grad: row bands are not implemented (render the whole image)')
         if cfg.arith != binding.ARITH['f32']:
             raise NotImplementedError("normal_decoder_grad: arith='f32' only")
-    return RenderBatchFunction.apply(latent, R, T, engine, cfg, view_flags, bool(normal_decoder_grad))
+    return RenderBatchFunction.apply(latent, R, T, engine, cfg, view_flags, bool(normal_decoder_grad), *weights)
 
 
-def render_call(engine, cfg, latent, R, T, normal_decoder_grad=False):
+def render_call(engine, cfg, latent, R, T, normal_decoder_grad=False, weights=None, normals_detached=False):
     """One view: latent (1,C), R (3,3), T (3) -> (zdepth (P), mask (P) uint8, min_sdf (P), depth (H,W), normal (H,W,3))."""
     _single_view(engine, latent, R, T)
     H, W = cfg.band_rows, cfg.W
-    z, mask, q, depth, normal = render_batch_call(engine, cfg, latent, R, T, normal_decoder_grad=normal_decoder_grad)
+    z, mask, q, depth, normal = render_batch_call(engine, cfg, latent, R, T, normal_decoder_grad=normal_decoder_grad, weights=weights,
+                                                  normals_detached=normals_detached)
     if cfg.want_normal:
         depth, normal = depth.reshape(H, W), normal.reshape(H, W, 3)
     return z.reshape(-1), mask.reshape(-1), q.reshape(-1), depth, normal
@@ -827,6 +864,110 @@ class DecodeSdfTrainFunction(torch.autograd.Function):
 
 def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None, dropout=None):
     return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, dropout, *weights)
+
+
+# ---- weight gradients through render: the backward's sample list on the layer-wise path (include/distr_render_train.h)
+def render_samples(engine, cfg, ws, ws_b, B, want_src=False):
+    """distr_render_samples_export_batch on the forward workspace `ws` and the backward workspace `ws_b` as distr_render_backward_batch
+    of B views of `cfg` left them (tests and tools; render_weight_grads): -> (xyz (B, cap, 3), coef (B, cap), src (B, cap) int32 or None,
+    counts_dev (B,) int32 on the device), cap = distr_render_max_samples(cfg). View v's list is its first counts_dev[v] rows; the rows
+    behind them are not written (uninitialised memory)."""
+    dev = engine.device
+    cap = int(engine.ctx.L.distr_render_max_samples(C.byref(cfg)))
+    if cap <= 0:
+        raise ValueError('render_samples: a cfg the render calls refuse')
+    xyz = torch.empty(B, cap, 3, dtype=torch.float32, device=dev)
+    coef = torch.empty(B, cap, dtype=torch.float32, device=dev)
+    src = torch.empty(B, cap, dtype=torch.int32, device=dev) if want_src else None
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    p = binding.ptr
+    engine.ctx.check(engine.ctx.L.distr_render_samples_export_batch(
+        engine.ctx.h, C.byref(cfg), B, p(ws), ws.numel(), p(ws_b), ws_b.numel(), p(xyz), p(coef), p(src), cap, p(counts), engine.ctx.stream()))
+    return xyz, coef, src, counts
+
+
+def train_plan_bytes(counts):
+    """Workspace bytes of one train_forward call on segments of `counts` points: mirror of distr_train_workspace_bytes (pure Python, a
+    function of the counts alone -- the code length does not enter). About 20 KB per 64-padded row and the slabs of the weight gradients."""
+    rows = train_segment_rows(counts)[-1]
+    blocks, nseg, hid = rows // TRAIN_ROW_TILE, len(counts), 512
+    nslab = train_slab_plan(rows)[1]
+    up = lambda n: (n + 255) & ~255
+    b = up(4 * rows) + up(4 * blocks) + up(4 * nseg * 2 * hid) + up(16 * rows) + 8 * up(4 * rows * hid) + 3 * up(4 * rows) + 2 * up(4 * rows * hid)
+    b += up(4 * blocks * 4 * hid) + 3 * up(4 * nseg * 4 * hid) + up(4 * nslab * hid * hid) + up(4 * blocks)
+    return b + 256
+
+
+def render_train_chunks(counts, max_bytes):
+    """The plan of the train calls over the sample lists of B views: counts[v] rows per view -> a list of pieces, each a list of segments
+    (view, first row, rows). Every piece fits max_bytes (train_plan_bytes of its segments' rows) and has at most 64 segments; a view's
+    list is cut only at multiples of 64 rows from its start (whole tiles of the train path: a cut moves no row to another tile); views
+    without rows get no segment; pieces and segments follow the view order. A function of the counts and the limit alone: the same
+    inputs give the same plan, and so the same bytes. ValueError when not even 64 rows fit the limit."""
+    counts = [int(c) for c in counts]
+    if min(counts + [0]) < 0:
+        raise ValueError('counts must be >= 0, got %r' % (counts,))
+    max_bytes = int(max_bytes)
+    pieces, cur = [], []
+    for v, c in enumerate(counts):
+        at = 0
+        while at < c:
+            have = [n for _, _, n in cur]
+            left = c - at
+            fits = lambda n: train_plan_bytes(have + [n]) <= max_bytes
+            if len(cur) < binding.MAX_SEGMENTS and fits(min(left, TRAIN_ROW_TILE)):
+                if fits(left):
+                    n = left
+                else:               # the most whole tiles that fit (bytes grow with the rows)
+                    lo, hi = 1, -(-left // TRAIN_ROW_TILE)          # lo tiles fit, hi tiles do not
+                    while hi - lo > 1:
+                        mid = (lo + hi) // 2
+                        lo, hi = (mid, hi) if fits(mid * TRAIN_ROW_TILE) else (lo, mid)
+                    n = lo * TRAIN_ROW_TILE
+                cur.append((v, at, n))
+                at += n
+            elif cur:
+                pieces.append(cur)
+                cur = []
+            else:
+                raise ValueError('render_train_chunks: %d bytes do not hold one tile of 64 samples (%d bytes)'
+                                 % (max_bytes, train_plan_bytes([TRAIN_ROW_TILE])))
+    if cur:
+        pieces.append(cur)
+    return pieces
+
+
+def render_weight_grads(engine, cfg, ws, ws_b, B, weights, codes, max_bytes=None, want_latent=True):
+    """Weight gradients of one render backward: dL/dW_l, dL/db_l = sum over the backward's sample list of coef * d f / d(W_l, b_l)
+    (DESIGN.md section 8h). ws / ws_b: the workspaces as distr_render_backward_batch of B views left them; weights: W0..W8, b0..b8 as the
+    engine packed them; codes (1, C) shared or (B, C). Exports the list, READS THE B COUNTS ON THE HOST (one sync), cuts the views' rows
+    into train calls (render_train_chunks under DISTR_TRAIN_MAX_BYTES or max_bytes), runs train_forward / train_backward per piece and
+    adds the pieces' gradients in piece order. -> ([g_W0..g_W8, g_b0..g_b8], g_latent (B, C): the layer-wise code gradient of every
+    view, the sum of its segments' rows in order -- a cross-check of the fused g_latent, which is the one autograd returns; None
+    without want_latent)."""
+    xyz, coef, _, counts_dev = render_samples(engine, cfg, ws, ws_b, B)
+    counts = [int(c) for c in counts_dev.cpu().tolist()]
+    weights = [_f32c(w, engine.device) for w in weights]
+    lat = _f32c(codes, engine.device).reshape(-1, engine.latent_size)
+    total = [torch.zeros_like(w) for w in weights]
+    g_lat = torch.zeros(B, engine.latent_size, dtype=torch.float32, device=engine.device) if want_latent else None
+    first = True
+    for piece in render_train_chunks(counts, train_max_bytes() if max_bytes is None else max_bytes):
+        pts = torch.cat([xyz[v, a:a + n] for v, a, n in piece])
+        cf = torch.cat([coef[v, a:a + n] for v, a, n in piece])
+        seg_codes = lat if lat.shape[0] == 1 else lat[[v for v, _, _ in piece]]
+        _, saved = train_forward(weights, seg_codes, pts, [n for _, _, n in piece], clamp_dist=None)
+        grads, rows = train_backward(saved, cf)
+        del saved
+        if first:
+            total, first = grads, False
+        else:
+            for a, b in zip(total, grads):
+                a += b
+        if want_latent:
+            for (v, _, _), row in zip(piece, rows):
+                g_lat[v] += row
+    return total, g_lat
 
 
 def depth_samples_count(engine, cfg, depth):

@@ -379,5 +379,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_train.h"
 /* the ordered live list of the full-resolution march seen from outside: block enumeration, k-step counts, list read-back */
 #include "distr_live_order.h"
+/* the render backward's gradient-sample list, written out: weight gradients through render on the layer-wise path */
+#include "distr_render_train.h"
 
 #endif /* DISTR_H_ */
