@@ -222,3 +222,33 @@ def decode_color_batch(decoder, color_codes, shape_codes, points, counts=None, n
     else:
         out = functions.color_eval_multi(eng, color_codes, shape_codes, flat, counts)
     return out.reshape(shape + (3,))
+
+
+def decode_color_train(decoder, color_codes, shape_codes, points, counts=None, dropout_seed=None):
+    """decode_color_batch that is differentiable w.r.t. `decoder.parameters()` AND both codes (not in the reference, which trains its
+    texture network through the torch Decoder): the colour decoder on the layer-wise path of DESIGN.md section 8i -- the GEMMs of
+    decode_sdf_train on the network (L, lin3 rows, outputs) = (256 + cs, 253, 3), tanh and no clamp. Arguments, shapes and ValueErrors
+    as decode_color_batch: points (S, N, 3) -> (S, N, 3), or the flat list (sum N, 3) with `counts` -> (sum N, 3); color_codes (S, cs)
+    and shape_codes (S, 256), or (1, .) shared. points with requires_grad are refused (points are data here: decode_color_batch gives
+    gradients to them). Without `dropout_seed` the decoder must be in eval mode; with an int seed a decoder in training mode gets the
+    counter-based mask of section 8g, segment = the index into the code rows; in eval mode the seed changes nothing. latent_dropout in
+    training mode stays refused. A workspace above DISTR_TRAIN_MAX_BYTES (24 KB per point) is refused, not chunked. Weight norm is
+    folded on the autograd graph. The colour engine is not involved: after an optimiser step decode_color* and SDFRenderer_color
+    re-pack the weights by themselves."""
+    from distr import decoder_pack
+    module = decoder.module if hasattr(decoder, 'module') else decoder
+    dropout = None
+    if dropout_seed is None:
+        functions._check_eval(module)
+    else:
+        params = functions.train_dropout_params(module, dropout_seed)
+        dropout = None if params is None else params + (int(dropout_seed), 0)
+    Ws, bs = decoder_pack.effective_weights_torch_color(decoder)
+    if points.requires_grad:
+        raise ValueError('decode_color_train: points.requires_grad is set, but points are data on the layer-wise path (no point gradients); '
+                         'pass points.detach(), or use decode_color_batch for gradients to the points')
+    x, counts, shape = _color_batch_layout(color_codes, shape_codes, points, counts)
+    if x.device.type != 'cuda':
+        raise RuntimeError('decode_color_train: tensors must be on the GPU (no CPU path in this build)')
+    out = functions.decode_color_train_call(Ws + bs, color_codes, shape_codes, x, counts, dropout)
+    return out.reshape(shape + (3,))

@@ -2650,7 +2650,8 @@ int distr_color_relight(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nfr
 namespace {
 
 struct TrainPlan {
-  int C, nseg;
+  int C, nseg;               // C: the code length L of the described net (section 8i)
+  int n3, ld4, nout;         // lin3's rows, W4's row stride n3 + L + 3 (columns [lin3 outputs | code | xyz]), lin8's rows (1 or 3)
   int64_t n;                 // points
   int rows, blocks;          // padded rows, 64-row blocks
   int64_t slab_len; int nslab;
@@ -2659,7 +2660,7 @@ struct TrainPlan {
   // workspace
   int32_t *rowpt, *blkseg, *blkpt0;
   float *c0c4, *xyz4, *X[9] /* 1..8 */, *z, *th, *dz, *D[2], *colpart, *colseg[3] /* lin0, lin4, the others */, *slabs;
-  int out_w[9], in_w[9];     // GEMM widths: rows of W_l, and the columns of W_l that multiply the saved activation (lin4: 509 - C)
+  int out_w[9], in_w[9];     // GEMM widths: rows of W_l, and the columns of W_l that multiply the saved activation (lin4: n3)
 };
 
 void train_slab_plan(int64_t rows, int64_t* len, int* count) {
@@ -2670,12 +2671,17 @@ void train_slab_plan(int64_t rows, int64_t* len, int* count) {
   *count = (int)((rows + L - 1) / L);
 }
 
-int train_plan(distr_ctx* ctx, int32_t C, int32_t nseg, const int64_t* counts, TrainPlan& p) {
+constexpr int TRAIN_MAX_L = 65536;      // code length of a described net: keeps every index of W0 / W4 far inside an int
+
+// L, n3, nout: the described net (distr_train_net); the SDF decoder of code length C is (C, 509 - C, 1)
+int train_plan(distr_ctx* ctx, int32_t L, int32_t n3, int32_t nout, int32_t nseg, const int64_t* counts, TrainPlan& p) {
   memset(&p, 0, sizeof(p));
   PointList pl;
   if (int rc = seg_list(ctx, nseg, counts, pl)) return rc;
-  if (C < 1 || C > HID - 4) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_size %d: 1..%d", C, HID - 4);
-  p.C = C; p.nseg = nseg; p.n = pl.n;
+  if (nout != 1 && nout != 3) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: out_dim %d: 1 or 3", nout);
+  if (n3 < 1 || n3 > HID - 3) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: lin3_rows %d: 1..%d", n3, HID - 3);
+  if (L < 1 || L > TRAIN_MAX_L) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: latent_size %d: 1..%d", L, TRAIN_MAX_L);
+  p.C = L; p.n3 = n3; p.ld4 = n3 + L + 3; p.nout = nout; p.nseg = nseg; p.n = pl.n;
   int64_t rows = 0;
   for (int s = 0; s < nseg; ++s) {
     p.sg.n[s] = (int32_t)counts[s];
@@ -2686,8 +2692,14 @@ int train_plan(distr_ctx* ctx, int32_t C, int32_t nseg, const int64_t* counts, T
   p.rows = (int)rows; p.blocks = (int)(rows / train::TROW);
   train_slab_plan(rows, &p.slab_len, &p.nslab);
   for (int l = 0; l < 9; ++l) { p.out_w[l] = HID; p.in_w[l] = HID; }
-  p.out_w[3] = HID - 3 - C; p.in_w[4] = HID - 3 - C; p.out_w[8] = 1; p.in_w[0] = 3;
+  p.out_w[3] = n3; p.in_w[4] = n3; p.out_w[8] = nout; p.in_w[0] = 3;
   return DISTR_OK;
+}
+
+// the SDF decoder of the calls that take distr_train_weights
+int train_plan_sdf(distr_ctx* ctx, int32_t C, int32_t nseg, const int64_t* counts, TrainPlan& p) {
+  if (C < 1 || C > HID - 4) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_size %d: 1..%d", C, HID - 4);
+  return train_plan(ctx, C, HID - 3 - C, 1, nseg, counts, p);
 }
 
 size_t train_carve(void* base, TrainPlan& p) {
@@ -2697,7 +2709,7 @@ size_t train_carve(void* base, TrainPlan& p) {
   p.c0c4 = c.take<float>((size_t)p.nseg * 2 * HID);
   p.xyz4 = c.take<float>(R * 4);
   for (int l = 1; l <= 8; ++l) p.X[l] = c.take<float>(R * HID);
-  p.z = c.take<float>(R); p.th = c.take<float>(R); p.dz = c.take<float>(R);
+  p.z = c.take<float>(R * p.nout); p.th = c.take<float>(R * p.nout); p.dz = c.take<float>(R * p.nout);
   p.D[0] = c.take<float>(R * HID); p.D[1] = c.take<float>(R * HID);
   p.colpart = c.take<float>((size_t)p.blocks * 4 * HID);
   for (int i = 0; i < 3; ++i) p.colseg[i] = c.take<float>((size_t)p.nseg * 4 * HID);
@@ -2748,14 +2760,31 @@ int train_weights_ok(distr_ctx* ctx, const distr_train_weights* w) {
   return DISTR_OK;
 }
 
+int train_net_ok(distr_ctx* ctx, const distr_train_net* w) {
+  if (!w || w->struct_size != sizeof(distr_train_net)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: struct_size (use DISTR_INIT)");
+  for (int l = 0; l < 9; ++l)
+    if (!w->W[l] || !w->b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: null pointer for lin%d", l);
+  return DISTR_OK;
+}
+
+// distr_train_weights as the description of its SDF decoder (checked by train_weights_ok / train_plan_sdf before it is used)
+distr_train_net train_net_of(const distr_train_weights* w) {
+  distr_train_net n;
+  memset(&n, 0, sizeof(n));
+  n.struct_size = sizeof(n); n.latent_size = w->latent_size; n.lin3_rows = HID - 3 - w->latent_size; n.out_dim = 1;
+  for (int l = 0; l < 9; ++l) { n.W[l] = w->W[l]; n.b[l] = w->b[l]; }
+  return n;
+}
+
 // g_W of one layer's activation columns: Delta^T X over the K slabs, then the slabs in order
-int train_weight_grad(distr_ctx* ctx, const TrainPlan& p, const float* delta, int ldd, int M, const float* X, int N, float* g_W, hipStream_t s) {
+// (ldo: the row stride of g_W -- ld4 for lin4, whose activation columns are the first n3 of its rows, 512 elsewhere)
+int train_weight_grad(distr_ctx* ctx, const TrainPlan& p, const float* delta, int ldd, int M, const float* X, int N, float* g_W, int ldo, hipStream_t s) {
   train::GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = delta; g.lda = ldd; g.B = X; g.ldb = HID; g.Cout = p.slabs; g.ldc = N; g.M = M; g.N = N; g.K = p.rows;
   g.slab_len = (int)p.slab_len; g.slab_stride = (size_t)M * N;
   if (int rc = train_gemm<false, false, train::EPI_PART>(ctx, "k_train_gemm<weights>", g, p.nslab, s)) return rc;
-  hipLaunchKernelGGL(train::k_train_slab_sum, grid1((int64_t)M * N), dim3(256), 0, s, (const float*)p.slabs, p.nslab, M, N, g_W, HID);
+  hipLaunchKernelGGL(train::k_train_slab_sum, grid1((int64_t)M * N), dim3(256), 0, s, (const float*)p.slabs, p.nslab, M, N, g_W, ldo);
   LAUNCH_CHECK("k_train_slab_sum");
   return DISTR_OK;
 }
@@ -2773,25 +2802,139 @@ int train_bias_grad(distr_ctx* ctx, const TrainPlan& p, const float* delta, int 
   return DISTR_OK;
 }
 
+int train_grads_ok(distr_ctx* ctx, const distr_train_grads* gr) {
+  if (!gr || gr->struct_size != sizeof(distr_train_grads)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: struct_size (use DISTR_INIT)");
+  for (int l = 0; l < 9; ++l)
+    if (!gr->g_W[l] || !gr->g_b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: null pointer for lin%d", l);
+  return DISTR_OK;
+}
+
+// the forward on a checked description and its plan (the caller holds the EntryGuard)
+int train_forward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, int32_t nseg, const float* latent, int64_t latent_stride, const float* xyz,
+                      float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
+  train::DropArgs da;
+  uint32_t drop_mask;
+  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
+  const int C = p.C;
+  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
+  if (!latent || !ws || (p.n > 0 && (!xyz || !sdf))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < train_carve(nullptr, p)) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
+  train_carve(ws, p);
+  if (p.rows == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg, p.blkpt0);
+  LAUNCH_CHECK("k_train_rows");
+  da.blkseg = p.blkseg; da.blkpt0 = p.blkpt0;
+  hipLaunchKernelGGL(train::k_train_consts, dim3(4, (unsigned)p.nseg), dim3(256), 0, s, p.c0c4, w->W[0], w->b[0], w->W[4], w->b[4], C, p.ld4, p.n3, latent, latent_stride);
+  LAUNCH_CHECK("k_train_consts");
+  if (drop_mask & 1u) {
+    da.layer = 0;
+    hipLaunchKernelGGL(train::k_train_lin0_drop, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4,
+                       w->W[0], C, p.X[1], p.xyz4, da);
+  } else
+    hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
+                       p.X[1], p.xyz4);
+  LAUNCH_CHECK("k_train_lin0");
+  for (int l = 1; l <= 8; ++l) {
+    train::GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = p.X[l]; g.lda = HID; g.B = w->W[l]; g.ldb = l == 4 ? p.ld4 : HID; g.M = p.rows; g.N = p.out_w[l]; g.K = p.in_w[l];
+    g.Cout = l < 8 ? p.X[l + 1] : p.z; g.ldc = l < 8 ? HID : p.nout; g.relu = l < 8;
+    if (l == 4) {      // the accumulator starts from c4[segment]; xyz follows the lin3 outputs (and the code) in k order
+      g.ctab = p.c0c4 + HID; g.ctab_stride = 2 * HID; g.blkseg = p.blkseg;
+      g.tailW = w->W[4] + (p.ld4 - 3); g.tail_ld = p.ld4; g.xyz4 = p.xyz4;
+    } else g.bias = w->b[l];
+    da.layer = (uint32_t)l;
+    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s, (l < 8 && (drop_mask >> l & 1u)) ? &da : nullptr)) return rc;
+  }
+  hipLaunchKernelGGL(train::k_train_out, grid1((int64_t)p.rows * p.nout), dim3(256), 0, s, (const float*)p.z, (const int32_t*)p.rowpt, p.rows, p.nout, clamp, p.th, sdf);
+  LAUNCH_CHECK("k_train_out");
+  return DISTR_OK;
+}
+
+int train_backward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, int32_t nseg, const float* latent, int64_t latent_stride, const float* g_sdf,
+                       float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream, train::DropArgs& da, uint32_t drop_mask) {
+  const int C = p.C;
+  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
+  if (!latent || !ws || (p.n > 0 && !g_sdf)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  train_carve(ws, p);
+  hipStream_t s = (hipStream_t)stream;
+  if (p.rows == 0) {       // an empty list: every gradient is zero
+    for (int l = 0; l < 9; ++l) {
+      const size_t in = l == 0 ? (size_t)C + 3 : l == 4 ? (size_t)p.ld4 : HID;
+      HIP_TRY(hipMemsetAsync(gr->g_W[l], 0, (size_t)p.out_w[l] * in * sizeof(float), s));
+      HIP_TRY(hipMemsetAsync(gr->g_b[l], 0, (size_t)p.out_w[l] * sizeof(float), s));
+    }
+    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * C * sizeof(float), s));
+    return DISTR_OK;
+  }
+  hipLaunchKernelGGL(train::k_train_dz, grid1((int64_t)p.rows * p.nout), dim3(256), 0, s, g_sdf, (const float*)p.th, (const int32_t*)p.rowpt, p.rows, p.nout, clamp, p.dz);
+  LAUNCH_CHECK("k_train_dz");
+  // lin8: its delta is dz, nout columns
+  if (int rc = train_weight_grad(ctx, p, p.dz, p.nout, p.nout, p.X[8], HID, gr->g_W[8], HID, s)) return rc;
+  if (int rc = train_bias_grad(ctx, p, p.dz, p.nout, p.nout, false, p.colseg[2], gr->g_b[8], nullptr, 0, 0, 0, latent, latent_stride, s)) return rc;
+  const float* delta = p.dz;
+  int ldd = p.nout, cur = 0;
+  for (int l = 8; l >= 1; --l) {
+    // delta of lin(l-1) = (delta of lin_l) W_l, gated by the saved relu output X_l; lin4: its lin3 columns only
+    train::GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = l == 4 ? p.ld4 : HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
+    g.Cout = p.D[cur]; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
+    // X_l went through lin(l-1)'s dropout: a dropped unit is an exact zero there, a kept one carries the factor scale
+    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (drop_mask >> (l - 1) & 1u) ? &da : nullptr)) return rc;
+    delta = p.D[cur]; ldd = HID; cur ^= 1;
+    const int m = l - 1;       // delta now belongs to lin m
+    if (m >= 1) {
+      if (int rc = train_weight_grad(ctx, p, delta, HID, p.out_w[m], p.X[m], p.in_w[m], gr->g_W[m], m == 4 ? p.ld4 : HID, s)) return rc;
+      if (int rc = train_bias_grad(ctx, p, delta, HID, p.out_w[m], m == 4, p.colseg[m == 4 ? 1 : 2], gr->g_b[m], m == 4 ? gr->g_W[4] : nullptr, p.ld4, p.n3,
+                                   p.ld4 - 3, latent, latent_stride, s))
+        return rc;
+    } else {
+      if (int rc = train_bias_grad(ctx, p, delta, HID, HID, true, p.colseg[0], gr->g_b[0], gr->g_W[0], C + 3, 0, C, latent, latent_stride, s)) return rc;
+    }
+  }
+  if (g_latent) {
+    hipLaunchKernelGGL(train::k_train_glatent, dim3((unsigned)((C + 255) / 256), (unsigned)p.nseg), dim3(256), 0, s, (const float*)p.colseg[0], (const float*)p.colseg[1], w->W[0],
+                       w->W[4], C, p.ld4, p.n3, g_latent);
+    LAUNCH_CHECK("k_train_glatent");
+  }
+  return DISTR_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t distr_train_workspace_bytes(int32_t latent_size, int32_t nseg, const int64_t* counts_host) {
   TrainPlan p;
-  return train_plan(nullptr, latent_size, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
+  return train_plan_sdf(nullptr, latent_size, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
 }
 
 size_t distr_train_activation_offset(int32_t latent_size, int32_t nseg, const int64_t* counts_host, int32_t layer) {
   TrainPlan p;
-  if (layer < 1 || layer > 8 || train_plan(nullptr, latent_size, nseg, counts_host, p) != DISTR_OK) return 0;
+  if (layer < 1 || layer > 8 || train_plan_sdf(nullptr, latent_size, nseg, counts_host, p) != DISTR_OK) return 0;
+  train_carve(nullptr, p);
+  return (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt);
+}
+
+size_t distr_train_net_workspace_bytes(const distr_train_net* net, int32_t nseg, const int64_t* counts_host) {
+  TrainPlan p;
+  if (!net || net->struct_size != sizeof(distr_train_net)) return 0;
+  return train_plan(nullptr, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
+}
+
+size_t distr_train_net_activation_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts_host, int32_t layer) {
+  TrainPlan p;
+  if (!net || net->struct_size != sizeof(distr_train_net) || layer < 1 || layer > 8) return 0;
+  if (train_plan(nullptr, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p) != DISTR_OK) return 0;
   train_carve(nullptr, p);
   return (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt);
 }
 
 int64_t distr_train_segment_row(int32_t nseg, const int64_t* counts_host, int32_t seg) {
   TrainPlan p;
-  if (seg < 0 || seg > nseg || train_plan(nullptr, 1, nseg, counts_host, p) != DISTR_OK) return -1;
+  if (seg < 0 || seg > nseg || train_plan_sdf(nullptr, 1, nseg, counts_host, p) != DISTR_OK) return -1;
   return p.seg_row[seg];
 }
 
@@ -2818,45 +2961,20 @@ int distr_train_forward_dropout(distr_ctx* ctx, const distr_train_weights* w, in
   EntryGuard guard_(ctx);
   if (int rc = train_weights_ok(ctx, w)) return rc;
   TrainPlan p;
-  if (int rc = train_plan(ctx, w->latent_size, nseg, counts_host, p)) return rc;
-  train::DropArgs da;
-  uint32_t drop_mask;
-  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
-  const int C = p.C;
-  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
-  if (!latent || !ws || (p.n > 0 && (!xyz || !sdf))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  if (ws_bytes < train_carve(nullptr, p)) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
-  train_carve(ws, p);
-  if (p.rows == 0) return DISTR_OK;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg, p.blkpt0);
-  LAUNCH_CHECK("k_train_rows");
-  da.blkseg = p.blkseg; da.blkpt0 = p.blkpt0;
-  hipLaunchKernelGGL(train::k_train_consts, dim3(4, (unsigned)p.nseg), dim3(256), 0, s, p.c0c4, w->W[0], w->b[0], w->W[4], w->b[4], C, latent, latent_stride);
-  LAUNCH_CHECK("k_train_consts");
-  if (drop_mask & 1u) {
-    da.layer = 0;
-    hipLaunchKernelGGL(train::k_train_lin0_drop, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4,
-                       w->W[0], C, p.X[1], p.xyz4, da);
-  } else
-    hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
-                       p.X[1], p.xyz4);
-  LAUNCH_CHECK("k_train_lin0");
-  for (int l = 1; l <= 8; ++l) {
-    train::GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = p.X[l]; g.lda = HID; g.B = w->W[l]; g.ldb = HID; g.M = p.rows; g.N = p.out_w[l]; g.K = p.in_w[l];
-    g.Cout = l < 8 ? p.X[l + 1] : p.z; g.ldc = l < 8 ? HID : 1; g.relu = l < 8;
-    if (l == 4) {      // the accumulator starts from c4[segment]; xyz follows the lin3 outputs in k order
-      g.ctab = p.c0c4 + HID; g.ctab_stride = 2 * HID; g.blkseg = p.blkseg;
-      g.tailW = w->W[4] + (HID - 3); g.tail_ld = HID; g.xyz4 = p.xyz4;
-    } else g.bias = w->b[l];
-    da.layer = (uint32_t)l;
-    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s, (l < 8 && (drop_mask >> l & 1u)) ? &da : nullptr)) return rc;
-  }
-  hipLaunchKernelGGL(train::k_train_out, grid1(p.rows), dim3(256), 0, s, (const float*)p.z, (const int32_t*)p.rowpt, p.rows, clamp, p.th, sdf);
-  LAUNCH_CHECK("k_train_out");
-  return DISTR_OK;
+  if (int rc = train_plan_sdf(ctx, w->latent_size, nseg, counts_host, p)) return rc;
+  const distr_train_net net = train_net_of(w);
+  return train_forward_net(ctx, &net, p, nseg, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, stream, drop);
+}
+
+int distr_train_net_forward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                            const float* xyz, float clamp, float* out, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = train_net_ok(ctx, net)) return rc;
+  TrainPlan p;
+  if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p)) return rc;
+  if (p.nout != 1 && clamp >= 0.f) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: clamp_dist %g with out_dim %d: a clamp belongs to out_dim 1 (pass a negative value)", (double)clamp, p.nout);
+  return train_forward_net(ctx, net, p, nseg, latent, latent_stride, xyz, clamp, out, ws, ws_bytes, stream, drop);
 }
 
 int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
@@ -2873,57 +2991,27 @@ int distr_train_backward_dropout(distr_ctx* ctx, const distr_train_weights* w, i
   train::DropArgs da;
   uint32_t drop_mask;
   if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
-  if (!gr || gr->struct_size != sizeof(distr_train_grads)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: struct_size (use DISTR_INIT)");
-  for (int l = 0; l < 9; ++l)
-    if (!gr->g_W[l] || !gr->g_b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grads: null pointer for lin%d", l);
+  if (int rc = train_grads_ok(ctx, gr)) return rc;
   TrainPlan p;
-  if (int rc = train_plan(ctx, w->latent_size, nseg, counts_host, p)) return rc;
-  const int C = p.C;
-  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
-  if (!latent || !ws || (p.n > 0 && !g_sdf)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  train_carve(ws, p);
-  hipStream_t s = (hipStream_t)stream;
-  if (p.rows == 0) {       // an empty list: every gradient is zero
-    for (int l = 0; l < 9; ++l) {
-      const size_t in = l == 0 ? (size_t)C + 3 : HID;
-      HIP_TRY(hipMemsetAsync(gr->g_W[l], 0, (size_t)p.out_w[l] * in * sizeof(float), s));
-      HIP_TRY(hipMemsetAsync(gr->g_b[l], 0, (size_t)p.out_w[l] * sizeof(float), s));
-    }
-    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * C * sizeof(float), s));
-    return DISTR_OK;
-  }
-  hipLaunchKernelGGL(train::k_train_dz, grid1(p.rows), dim3(256), 0, s, g_sdf, (const float*)p.th, (const int32_t*)p.rowpt, p.rows, clamp, p.dz);
-  LAUNCH_CHECK("k_train_dz");
-  // lin8: its delta is the column dz
-  if (int rc = train_weight_grad(ctx, p, p.dz, 1, 1, p.X[8], HID, gr->g_W[8], s)) return rc;
-  if (int rc = train_bias_grad(ctx, p, p.dz, 1, 1, false, p.colseg[2], gr->g_b[8], nullptr, 0, 0, 0, latent, latent_stride, s)) return rc;
-  const float* delta = p.dz;
-  int ldd = 1, cur = 0;
-  for (int l = 8; l >= 1; --l) {
-    // delta of lin(l-1) = (delta of lin_l) W_l, gated by the saved relu output X_l; lin4: its lin3 columns only
-    train::GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
-    g.Cout = p.D[cur]; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
-    // X_l went through lin(l-1)'s dropout: a dropped unit is an exact zero there, a kept one carries the factor scale
-    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (drop_mask >> (l - 1) & 1u) ? &da : nullptr)) return rc;
-    delta = p.D[cur]; ldd = HID; cur ^= 1;
-    const int m = l - 1;       // delta now belongs to lin m
-    if (m >= 1) {
-      if (int rc = train_weight_grad(ctx, p, delta, HID, p.out_w[m], p.X[m], p.in_w[m], gr->g_W[m], s)) return rc;
-      if (int rc = train_bias_grad(ctx, p, delta, HID, p.out_w[m], m == 4, p.colseg[m == 4 ? 1 : 2], gr->g_b[m], m == 4 ? gr->g_W[4] : nullptr, HID, HID - 3 - C,
-                                   HID - 3, latent, latent_stride, s))
-        return rc;
-    } else {
-      if (int rc = train_bias_grad(ctx, p, delta, HID, HID, true, p.colseg[0], gr->g_b[0], gr->g_W[0], C + 3, 0, C, latent, latent_stride, s)) return rc;
-    }
-  }
-  if (g_latent) {
-    hipLaunchKernelGGL(train::k_train_glatent, dim3((unsigned)((C + 255) / 256), (unsigned)p.nseg), dim3(256), 0, s, (const float*)p.colseg[0], (const float*)p.colseg[1], w->W[0],
-                       w->W[4], C, g_latent);
-    LAUNCH_CHECK("k_train_glatent");
-  }
-  return DISTR_OK;
+  if (int rc = train_plan_sdf(ctx, w->latent_size, nseg, counts_host, p)) return rc;
+  const distr_train_net net = train_net_of(w);
+  return train_backward_net(ctx, &net, p, nseg, latent, latent_stride, g_sdf, clamp, ws, gr, g_latent, stream, da, drop_mask);
+}
+
+int distr_train_net_backward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                             const float* g_out, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
+                             const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (int rc = train_net_ok(ctx, net)) return rc;
+  train::DropArgs da;
+  uint32_t drop_mask;
+  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
+  if (int rc = train_grads_ok(ctx, gr)) return rc;
+  TrainPlan p;
+  if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p)) return rc;
+  if (p.nout != 1 && clamp >= 0.f) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: clamp_dist %g with out_dim %d: a clamp belongs to out_dim 1 (pass a negative value)", (double)clamp, p.nout);
+  return train_backward_net(ctx, net, p, nseg, latent, latent_stride, g_out, clamp, ws, gr, g_latent, stream, da, drop_mask);
 }
 
 }  // extern "C"

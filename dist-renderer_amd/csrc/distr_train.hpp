@@ -6,7 +6,9 @@
 //   rows      every segment padded to a multiple of 64 rows (TROW): a 64-row block never holds two segments. A padded row has xyz = 0
 //             and an upstream gradient of 0 -> its deltas are exactly 0 and it adds exactly nothing to any sum.
 //   forward   k_train_rows (row -> point table), k_train_consts (c0 / c4 per segment), k_train_lin0, k_train_gemm<FWD> x 8 (lin1..lin8;
-//             lin8 as a GEMM with one output column), k_train_out (tanh, clamp, scatter to the caller's order)
+//             lin8 as a GEMM with one or three output columns), k_train_out (tanh, clamp, scatter to the caller's order)
+//   network   the host describes it (section 8i): code length L, lin3's rows n3, W4's row stride ld4 = n3 + L + 3 with the columns
+//             [lin3 outputs | code | xyz], nout = 1 or 3 output channels. The SDF decoder is L = C, n3 = 509 - C, ld4 = 512, nout = 1.
 //   backward  k_train_dz, then per layer 8..1: k_train_gemm<DW> over K slabs + k_train_slab_sum (g_W), k_train_colsum +
 //             k_train_colsum_seg + k_train_bias (g_b and, for lin0 / lin4, the xyz and latent columns of g_W), k_train_gemm<DX> (the
 //             delta of the layer below, gated by the saved activation); k_train_glatent last.
@@ -60,14 +62,15 @@ struct DropArgs {
   const int32_t* blkseg; const int32_t* blkpt0;
 };
 
-// c0[s] = b0 + W0[:, :C] code_s, c4[s] = b4 + W4[:, 509-C : 509] code_s, one k-ordered fmaf chain each (the arithmetic of
-// k_latent_consts, on row-major weights). grid (4, segments), 256 threads; c0c4[s][1024]
+// c0[s] = b0 + W0[:, :C] code_s, c4[s] = b4 + W4[:, col4 : col4 + C] code_s, one k-ordered fmaf chain each (the arithmetic of
+// k_latent_consts, on row-major weights). C = the code length L of the net, ld4 = W4's row stride, col4 = its first code column (the
+// SDF decoder: 512 and 509 - C). grid (4, segments), 256 threads; c0c4[s][1024]
 DISTR_GLOBAL void __launch_bounds__(256) k_train_consts(float* __restrict__ c0c4, const float* __restrict__ W0, const float* __restrict__ b0,
-                                                      const float* __restrict__ W4, const float* __restrict__ b4, int C,
+                                                      const float* __restrict__ W4, const float* __restrict__ b4, int C, int ld4, int col4,
                                                       const float* __restrict__ latent, int64_t lat_stride) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   const int o = gid & (HID - 1);
-  const float* w = (gid < HID) ? W0 + (size_t)o * (C + 3) : W4 + (size_t)o * HID + (HID - 3 - C);
+  const float* w = (gid < HID) ? W0 + (size_t)o * (C + 3) : W4 + (size_t)o * ld4 + col4;
   float acc = (gid < HID) ? b0[o] : b4[o];
   latent += (int64_t)blockIdx.y * lat_stride;
   for (int k = 0; k < C; ++k) acc = __builtin_fmaf(w[k], latent[k], acc);
@@ -326,29 +329,32 @@ DISTR_GLOBAL void __launch_bounds__(256, 2) k_train_gemm_drop(GemmArgs g, DropAr
   gemm_tile<A_K, B_K, EPI, true>(g, d);
 }
 
-// sdf = tanh(z), clamped, into the caller's order; th[row] = tanh(z) (unclamped) for the backward
-DISTR_GLOBAL void __launch_bounds__(256) k_train_out(const float* __restrict__ z, const int32_t* __restrict__ rowpt, int rows, float clamp,
+// out = tanh(z), clamped, into the caller's order as out[pt][ch]; th[row][ch] = tanh(z) (unclamped) for the backward. One thread per
+// (row, channel) of the nout channels (the host passes clamp < 0 for nout == 3).
+DISTR_GLOBAL void __launch_bounds__(256) k_train_out(const float* __restrict__ z, const int32_t* __restrict__ rowpt, int rows, int nout, float clamp,
                                                    float* __restrict__ th, float* __restrict__ sdf) {
-  const int row = blockIdx.x * 256 + threadIdx.x;
-  if (row >= rows) return;
-  const float s = tanh_spec(z[row]);
-  th[row] = s;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)rows * nout) return;
+  const int row = (int)(i / nout), ch = (int)(i - (int64_t)row * nout);
+  const float s = tanh_spec(z[i]);
+  th[i] = s;
   const int pt = rowpt[row];
-  if (pt >= 0) sdf[pt] = clamp >= 0.f ? fminf(fmaxf(s, -clamp), clamp) : s;
+  if (pt >= 0) sdf[(size_t)pt * nout + ch] = clamp >= 0.f ? fminf(fmaxf(s, -clamp), clamp) : s;
 }
 
-// delta at the output: dz[row] = g_sdf (1 - tanh^2), 0 where the clamp cut and for a padded row
+// delta at the output: dz[row][ch] = g_out[pt][ch] (1 - tanh^2), 0 where the clamp cut and for a padded row
 DISTR_GLOBAL void __launch_bounds__(256) k_train_dz(const float* __restrict__ g_sdf, const float* __restrict__ th, const int32_t* __restrict__ rowpt,
-                                                  int rows, float clamp, float* __restrict__ dz) {
-  const int row = blockIdx.x * 256 + threadIdx.x;
-  if (row >= rows) return;
+                                                  int rows, int nout, float clamp, float* __restrict__ dz) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)rows * nout) return;
+  const int row = (int)(i / nout), ch = (int)(i - (int64_t)row * nout);
   const int pt = rowpt[row];
   float d = 0.f;
   if (pt >= 0) {
-    const float s = th[row];
-    if (!(clamp >= 0.f && fabsf(s) > clamp)) d = g_sdf[pt] * (1.f - s * s);
+    const float s = th[i];
+    if (!(clamp >= 0.f && fabsf(s) > clamp)) d = g_sdf[(size_t)pt * nout + ch] * (1.f - s * s);
   }
-  dz[row] = d;
+  dz[i] = d;
 }
 
 // g_W = the slab partials in slab order. out[m * ldo + n] for m < M, n < N; part[slab][M * N]
@@ -431,17 +437,17 @@ DISTR_GLOBAL void __launch_bounds__(256) k_train_bias(const float* __restrict__ 
   }
 }
 
-// g_latent[s][c] = sum_o W0[o][c] seg0[s][0][o] + sum_o W4[o][509 - C + c] seg4[s][0][o], o in order, lin0's chain then lin4's.
-// grid (ceil(C / 256), segments)
+// g_latent[s][c] = sum_o W0[o][c] seg0[s][0][o] + sum_o W4[o][col4 + c] seg4[s][0][o], o in order, lin0's chain then lin4's. W0's row
+// stride is C + 3, W4's is ld4 (the SDF decoder: ld4 = 512, col4 = 509 - C). grid (ceil(C / 256), segments)
 DISTR_GLOBAL void __launch_bounds__(256) k_train_glatent(const float* __restrict__ seg0, const float* __restrict__ seg4, const float* __restrict__ W0,
-                                                       const float* __restrict__ W4, int C, float* __restrict__ g_latent) {
+                                                       const float* __restrict__ W4, int C, int ld4, int col4, float* __restrict__ g_latent) {
   const int c = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
   if (c >= C) return;
   const float* s0 = seg0 + (size_t)s * 4 * HID;
   const float* s4 = seg4 + (size_t)s * 4 * HID;
   float a = 0.f;
   for (int o = 0; o < HID; ++o) a = __builtin_fmaf(W0[(size_t)o * (C + 3) + c], s0[o], a);
-  for (int o = 0; o < HID; ++o) a = __builtin_fmaf(W4[(size_t)o * HID + (HID - 3 - C) + c], s4[o], a);
+  for (int o = 0; o < HID; ++o) a = __builtin_fmaf(W4[(size_t)o * ld4 + col4 + c], s4[o], a);
   g_latent[(size_t)s * C + c] = a;
 }
 

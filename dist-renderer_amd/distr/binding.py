@@ -43,7 +43,9 @@ COLOR_BATCH_EXPORTS = ['distr_color_multi_workspace_bytes', 'distr_color_backwar
 # the layer-wise decoder path (include/distr_train.h, included by distr.h): decode_sdf with gradients to the decoder's weights
 TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset', 'distr_train_segment_row', 'distr_train_slab_plan',
                  'distr_train_forward', 'distr_train_backward', 'distr_train_forward_dropout', 'distr_train_backward_dropout',
-                 'distr_train_dropout_keep']
+                 'distr_train_dropout_keep',
+                 # the same path on a described network: the colour decoder
+                 'distr_train_net_workspace_bytes', 'distr_train_net_activation_offset', 'distr_train_net_forward', 'distr_train_net_backward']
 # the ordered live list seen from outside (include/distr_live_order.h, included by distr.h): block enumeration, k-step counts, list read-back
 LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list']
 # the render backward's gradient-sample list, written out (include/distr_render_train.h, included by distr.h): weight gradients through render
@@ -147,6 +149,12 @@ def make_warp_cfg(img_hw, intrinsic, thres_depth):
 class TrainWeights(_Sized):
     """distr_train_weights: the nine layers of the decoder as device pointers, row-major (out, in)."""
     _fields_ = [('struct_size', C.c_uint32), ('latent_size', C.c_int32), ('W', C.c_void_p * 9), ('b', C.c_void_p * 9)]
+
+
+class TrainNet(_Sized):
+    """distr_train_net: a described network of the layer-wise path -- code length L, lin3's rows, lin8's rows (1 or 3), the nine layers."""
+    _fields_ = [('struct_size', C.c_uint32), ('latent_size', C.c_int32), ('lin3_rows', C.c_int32), ('out_dim', C.c_int32), ('W', C.c_void_p * 9),
+                ('b', C.c_void_p * 9)]
 
 
 class TrainGrads(_Sized):
@@ -430,6 +438,13 @@ def lib():
             L.distr_train_forward_dropout.argtypes = L.distr_train_forward.argtypes + [td]
             L.distr_train_backward_dropout.argtypes = L.distr_train_backward.argtypes + [td]
             L.distr_train_dropout_keep.argtypes = [C.c_uint64, C.c_uint32, i32, i64, i64, i32]
+            tn = C.POINTER(TrainNet)
+            L.distr_train_net_workspace_bytes.argtypes = [tn, i32, i64p]
+            L.distr_train_net_workspace_bytes.restype = C.c_size_t
+            L.distr_train_net_activation_offset.argtypes = [tn, i32, i64p, i32]
+            L.distr_train_net_activation_offset.restype = C.c_size_t
+            L.distr_train_net_forward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp, td]
+            L.distr_train_net_backward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, C.c_float, vp, tg, fp, vp, td]
             L.distr_render_max_samples.argtypes = [C.POINTER(RenderCfg)]
             L.distr_render_max_samples.restype = i64
             L.distr_render_samples_export_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, vp, C.c_size_t, vp, C.c_size_t, fp, fp, vp, i64, vp, vp]

@@ -135,7 +135,40 @@ def effective_weights_torch(decoder):
     hands out its own parameters; weight norm, old style (`weight_g` / `weight_v`) or parametrized (`parametrizations.weight.original0 /
     original1`), is folded as effective_weights folds it, W = v * (g / ||v||_row) with the same f32 operations in the same order, so the
     train path and the packed engine see the same weights, and autograd carries g_W on to g and v. Checked as check_module_flags and validate check a decoder that is packed (flags, the nine shapes, finite values)."""
-    import torch
+    Ws, bs = _folded_weights_torch(decoder)
+    C = int(Ws[0].shape[1]) - 3 if Ws[0].dim() == 2 else -1
+    if C < 1 or C > MAX_LATENT:
+        raise UnsupportedDecoder('lin0 has shape %s: code length %d is outside 1..%d (lin3 of a latent_in=[4] decoder has 509 - C rows)'
+                                 % (tuple(Ws[0].shape), C, MAX_LATENT))
+    shapes = fixture.layer_shapes(C)
+    for l, (W, b) in enumerate(zip(Ws, bs)):
+        if tuple(W.shape) != shapes[l] or tuple(b.shape) != (shapes[l][0],):
+            raise UnsupportedDecoder('lin%d has shape %s, kernels are specialised for %s (DeepSDF 8x512, latent %d, latent_in=[4], '
+                                     'last_dim=1)' % (l, tuple(W.shape), shapes[l], C))
+    _check_finite_torch(Ws, bs)
+    return Ws, bs
+
+
+def effective_weights_torch_color(decoder):
+    """effective_weights_torch for the colour decoder (load_decoder(color_size=cs)): ([W_l], [b_l]) on the autograd graph of the module's
+    parameters, for decode_color_train. The same flag checks and the same weight-norm fold; the nine shapes are
+    those validate_color asks for (fixture.color_layer_shapes(cs), cs >= 1: lin0 (512, 256 + cs + 3), lin3 (253, 512), lin4 (512, 512 +
+    cs), lin8 (3, 512)); every value is finite."""
+    Ws, bs = _folded_weights_torch(decoder)
+    cs = (int(Ws[0].shape[1]) - 3 - fixture.LATENT_SIZE) if Ws[0].dim() == 2 else -1
+    if cs <= 0:
+        raise UnsupportedDecoder('colour decoder must take latent = 256 + color_size (> 256), got lin0 of shape %s' % (tuple(Ws[0].shape),))
+    want = fixture.color_layer_shapes(cs)
+    for l, (W, b) in enumerate(zip(Ws, bs)):
+        if tuple(W.shape) != want[l] or tuple(b.shape) != (want[l][0],):
+            raise UnsupportedDecoder('colour lin%d has shape %s, expected %s (DeepSDF 8x512 with latent 256+%d, latent_in=[4], '
+                                     'last_dim=3)' % (l, tuple(W.shape), want[l], cs))
+    _check_finite_torch(Ws, bs)
+    return Ws, bs
+
+
+def _folded_weights_torch(decoder):
+    """The nine (W_l, b_l) of a module on its autograd graph, weight norm folded; flags and the layer count checked."""
     check_module_flags(decoder)
     d = decoder.module if hasattr(decoder, 'module') else decoder
     params = dict(d.named_parameters())
@@ -156,21 +189,16 @@ def effective_weights_torch(decoder):
         l += 1
     if len(Ws) != fixture.NUM_LINEAR:
         raise UnsupportedDecoder('expected %d linear layers, got %d' % (fixture.NUM_LINEAR, len(Ws)))
-    C = int(Ws[0].shape[1]) - 3 if Ws[0].dim() == 2 else -1
-    if C < 1 or C > MAX_LATENT:
-        raise UnsupportedDecoder('lin0 has shape %s: code length %d is outside 1..%d (lin3 of a latent_in=[4] decoder has 509 - C rows)'
-                                 % (tuple(Ws[0].shape), C, MAX_LATENT))
-    shapes = fixture.layer_shapes(C)
-    for l, (W, b) in enumerate(zip(Ws, bs)):
-        if tuple(W.shape) != shapes[l] or tuple(b.shape) != (shapes[l][0],):
-            raise UnsupportedDecoder('lin%d has shape %s, kernels are specialised for %s (DeepSDF 8x512, latent %d, latent_in=[4], '
-                                     'last_dim=1)' % (l, tuple(W.shape), shapes[l], C))
+    return Ws, bs
+
+
+def _check_finite_torch(Ws, bs):
+    import torch
     with torch.no_grad():       # one reduction and one host read for all eighteen tensors
         finite = torch.stack([torch.isfinite(t).all() for t in Ws + bs])
         if not bool(finite.all()):
             bad = [i for i, ok in enumerate(finite.tolist()) if not ok][0]
             raise UnsupportedDecoder('lin%d has non-finite weights or biases' % (bad % fixture.NUM_LINEAR))
-    return Ws, bs
 
 
 def validate_color(Ws, bs):

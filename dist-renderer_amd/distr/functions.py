@@ -713,10 +713,12 @@ def _train_dropout_struct(dropout, chunk_base=0):
 class TrainSaved(object):
     """What train_forward keeps for train_backward: the workspace with the saved layer inputs, and the call it belongs to."""
 
-    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp, dropout=None):
+    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp, dropout=None, net=None):
         self.ctx, self.ws, self.latent_size, self.counts = ctx, ws, C_len, list(counts)
         self.weights, self.lat, self.stride, self.clamp, self.dropout = weights, lat, stride, clamp, dropout
         self.seg_rows = train_segment_rows(counts)
+        self.net = net                                   # None: the SDF decoder of code length C_len; else (L, lin3_rows, out_dim)
+        self.lin3_rows, self.out_dim = (509 - C_len, 1) if net is None else (int(net[1]), int(net[2]))
 
     def _cnt(self):
         return (C.c_int64 * len(self.counts))(*self.counts)
@@ -726,14 +728,18 @@ class TrainSaved(object):
         return self.seg_rows[s], self.seg_rows[s] + self.counts[s]
 
     def activations(self, layer):
-        """(rows, width) f32 view of X_layer (1..8), the saved input of lin_layer = relu of lin_(layer-1); width 512, 509 - C for layer 4."""
-        off = self.ctx.L.distr_train_activation_offset(self.latent_size, len(self.counts), self._cnt(), int(layer))
+        """(rows, width) f32 view of X_layer (1..8), the saved input of lin_layer = relu of lin_(layer-1); width 512, lin3_rows (the SDF
+        decoder: 509 - C) for layer 4."""
+        if self.net is None:
+            off = self.ctx.L.distr_train_activation_offset(self.latent_size, len(self.counts), self._cnt(), int(layer))
+        else:
+            off = self.ctx.L.distr_train_net_activation_offset(C.byref(_train_net_struct(self.weights, self.net)), len(self.counts), self._cnt(), int(layer))
         if not off:
             raise ValueError('layer %r: 1..8' % (layer,))
         R = self.seg_rows[-1]
         base = (-self.ws.data_ptr()) % 256
         x = self.ws[base + off: base + off + R * 512 * 4].view(torch.float32).reshape(R, 512)
-        return x[:, :509 - self.latent_size] if layer == 4 else x
+        return x[:, :self.lin3_rows] if layer == 4 else x
 
 
 def _train_weight_struct(weights, C_len):
@@ -744,13 +750,32 @@ def _train_weight_struct(weights, C_len):
     return tw
 
 
-def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None):
+def _train_net_struct(weights, net):
+    """net = (L, lin3_rows, out_dim) -> distr_train_net on the eighteen tensors"""
+    tn = binding.TrainNet(latent_size=int(net[0]), lin3_rows=int(net[1]), out_dim=int(net[2]))
+    for l in range(9):
+        tn.W[l] = weights[l].data_ptr()
+        tn.b[l] = weights[9 + l].data_ptr()
+    return tn
+
+
+def train_net_shapes(net):
+    """The eighteen shapes [W0..W8, b0..b8] a net description (L, lin3_rows, out_dim) implies (include/distr_train.h)."""
+    L, n3, nout = (int(v) for v in net)
+    W = [(512, L + 3), (512, 512), (512, 512), (n3, 512), (512, n3 + L + 3), (512, 512), (512, 512), (512, 512), (nout, 512)]
+    return W + [(o,) for o, _ in W]
+
+
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None, net=None):
     """Layer-wise decode_sdf of one segmented list of at most 64 segments (distr_train_forward): weights = [W0..W8, b0..b8] f32 device
     tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
     A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed.
     ws, out (tests): a uint8 device tensor to use as the workspace and an f32 (sum counts, 1) tensor for sdf, instead of fresh ones.
     dropout: None, or (layer_mask, threshold, scale, seed, segment_base) -- train_dropout_params(...) + (seed, global index of segment 0)
-    (distr_train_forward_dropout); the saved activations are then those behind the dropout, and train_backward follows."""
+    (distr_train_forward_dropout); the saved activations are then those behind the dropout, and train_backward follows.
+    net: None = the SDF decoder, its code length derived from W0; or (L, lin3_rows, out_dim), a described network (distr_train_net_*,
+    DESIGN.md section 8i; the colour decoder is (256 + cs, 253, 3)): the weights have train_net_shapes(net), latents are (S, L) or
+    (1, L), the output is (sum counts, out_dim), and a clamp belongs to out_dim 1."""
     counts = [int(c) for c in counts]
     dev = points.device
     if dev.type != 'cuda':
@@ -760,6 +785,15 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     ctx = _train_context(dev.index if dev.index is not None else torch.cuda.current_device())
     weights = [_f32c(t, dev) for t in weights]
     C_len = weights[0].shape[1] - 3
+    nout = 1
+    if net is not None:
+        net = tuple(int(v) for v in net)
+        if len(net) != 3:
+            raise ValueError('net %r: (L, lin3_rows, out_dim)' % (net,))
+        if len(weights) != 18 or [tuple(t.shape) for t in weights] != train_net_shapes(net):
+            raise ValueError('net (L, lin3_rows, out_dim) = %r takes W0..W8, b0..b8 of shapes %r, got %r'
+                             % (net, train_net_shapes(net), [tuple(t.shape) for t in weights]))
+        C_len, nout = net[0], net[2]
     lat = _f32c(latents, dev).reshape(-1, C_len)
     if lat.shape[0] not in (1, len(counts)):
         raise ValueError('latents have shape %s; %d segments take (%d, %d) or (1, %d)' % (tuple(latents.shape), len(counts), len(counts), C_len, C_len))
@@ -767,27 +801,36 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     if x.shape[0] != sum(counts):
         raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), x.shape[0]))
     cnt = (C.c_int64 * len(counts))(*counts)
-    need = ctx.L.distr_train_workspace_bytes(C_len, len(counts), cnt)
+    if net is None:
+        need = ctx.L.distr_train_workspace_bytes(C_len, len(counts), cnt)
+    else:
+        need = ctx.L.distr_train_net_workspace_bytes(C.byref(_train_net_struct(weights, net)), len(counts), cnt)
+        if not need:
+            raise ValueError('net (L, lin3_rows, out_dim) = %r: L >= 1, lin3_rows in 1..509, out_dim 1 or 3' % (net,))
     if need > train_max_bytes():
-        raise binding.DistrError('decode_sdf_train: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
+        raise binding.DistrError('%s: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
                                  'more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient follows the batch)'
-                                 % (x.shape[0], need, train_max_bytes()))
+                                 % ('decode_sdf_train' if net is None else 'decode_color_train' if nout == 3 else 'train_forward', x.shape[0], need,
+                                    train_max_bytes()))
     if ws is None:
         ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
     stride = 0 if lat.shape[0] == 1 else C_len
     if out is None:
-        out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
-    if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.shape[0]:
-        raise ValueError('train_forward: ws is a contiguous uint8 tensor, out a contiguous f32 tensor of %d values' % x.shape[0])
+        out = torch.empty(x.shape[0], nout, dtype=torch.float32, device=dev)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.shape[0] * nout:
+        raise ValueError('train_forward: ws is a contiguous uint8 tensor, out a contiguous f32 tensor of %d values' % (x.shape[0] * nout))
     p = binding.ptr
     td = _train_dropout_struct(dropout)
-    if td is None:
+    if net is not None:
+        ctx.check(ctx.L.distr_train_net_forward(ctx.h, C.byref(_train_net_struct(weights, net)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
+                                                p(out), p(ws), ws.numel(), ctx.stream(), None if td is None else C.byref(td)))
+    elif td is None:
         ctx.check(ctx.L.distr_train_forward(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
                                             p(out), p(ws), ws.numel(), ctx.stream()))
     else:
         ctx.check(ctx.L.distr_train_forward_dropout(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x),
                                                     _clamp_arg(clamp_dist), p(out), p(ws), ws.numel(), ctx.stream(), C.byref(td)))
-    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist, dropout)
+    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist, dropout, net)
 
 
 def train_backward(saved, g_sdf, out=None):
@@ -795,8 +838,8 @@ def train_backward(saved, g_sdf, out=None):
     segment, also for a shared code). out (tests): (the eighteen gradient tensors, g_latent) to write into instead of fresh ones."""
     ctx, dev = saved.ctx, saved.ws.device
     gs = _f32c(g_sdf, dev).reshape(-1)
-    if gs.numel() != sum(saved.counts):
-        raise ValueError('g_sdf has %d entries for %d points' % (gs.numel(), sum(saved.counts)))
+    if gs.numel() != sum(saved.counts) * saved.out_dim:
+        raise ValueError('g_sdf has %d entries for %d points of %d channel(s)' % (gs.numel(), sum(saved.counts), saved.out_dim))
     if out is None:
         grads = [torch.empty_like(w) for w in saved.weights]
         g_lat = torch.empty(len(saved.counts), saved.latent_size, dtype=torch.float32, device=dev)
@@ -811,7 +854,11 @@ def train_backward(saved, g_sdf, out=None):
         tg.g_b[l] = grads[9 + l].data_ptr()
     p = binding.ptr
     td = _train_dropout_struct(saved.dropout)
-    if td is None:
+    if saved.net is not None:
+        ctx.check(ctx.L.distr_train_net_backward(ctx.h, C.byref(_train_net_struct(saved.weights, saved.net)), len(saved.counts), saved._cnt(), p(saved.lat),
+                                                 saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream(),
+                                                 None if td is None else C.byref(td)))
+    elif td is None:
         ctx.check(ctx.L.distr_train_backward(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(), p(saved.lat),
                                              saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream()))
     else:
@@ -866,6 +913,66 @@ def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None, dropo
     return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, dropout, *weights)
 
 
+class _CodeLayout(object):
+    """What color_code_rows needs of an engine, without one: the code length of the colour net and the device."""
+
+    def __init__(self, latent_size, device):
+        self.latent_size, self.device = latent_size, device
+
+
+def color_train_net(weights):
+    """(L, lin3_rows, out_dim) = (256 + cs, 253, 3) of the colour decoder whose W0 is weights[0]."""
+    return int(weights[0].shape[1]) - 3, 253, 3
+
+
+class DecodeColorTrainFunction(torch.autograd.Function):
+    """decode_color on the layer-wise path with autograd to both codes AND the eighteen weight tensors:
+    (color_codes (S, cs) or (1, cs), shape_codes (S, 256) or (1, 256), flat points (sum counts, 3), counts, dropout, W0..W8, b0..b8) ->
+    (sum counts, 3). The code rows are [shape | colour] as color_code_rows builds them. More than 64 segments run in chunks of 64; the
+    weight gradients of the chunks are added in chunk order. The code gradient rows are split into the two codes; the rows of a shared
+    code are summed in segment order. Points are data. dropout as DecodeSdfTrainFunction: the segment is the index into the code rows."""
+
+    @staticmethod
+    def forward(ctx, color_codes, shape_codes, points, counts, dropout, *weights):
+        if len(weights) != 18:
+            raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
+        counts = [int(c) for c in counts]
+        plan = segment_plan(counts)
+        net = color_train_net(weights)
+        lat = color_code_rows(_CodeLayout(net[0], points.device), color_codes.detach(), shape_codes.detach(), len(counts))
+        x = points.detach().reshape(-1, 3)
+        outs, ctx.saved_chunks = [], []
+        for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
+            n = sum(counts[s0:s0 + ns])
+            drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
+            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], None, dropout=drop, net=net)
+            outs.append(out)
+            ctx.saved_chunks.append((saved, p0, n, s0, ns))
+        ctx.code_like = (color_codes.detach(), shape_codes.detach())
+        ctx.need = (color_codes.requires_grad, shape_codes.requires_grad)
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.reshape(-1, 3)
+        total, rows = None, []
+        for saved, p0, n, s0, ns in ctx.saved_chunks:
+            grads, g_lat = train_backward(saved, g[p0:p0 + n])
+            rows.append(g_lat)
+            if total is None:
+                total = grads
+            else:
+                for a, b in zip(total, grads):
+                    a += b
+        g_rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+        g_c, g_s = _split_code_grad(g_rows, *ctx.code_like)
+        return ((g_c if ctx.need[0] else None), (g_s if ctx.need[1] else None), None, None, None) + tuple(total)
+
+
+def decode_color_train_call(weights, color_codes, shape_codes, points, counts, dropout=None):
+    return DecodeColorTrainFunction.apply(color_codes, shape_codes, points, counts, dropout, *weights)
+
+
 # ---- weight gradients through render: the backward's sample list on the layer-wise path (include/distr_render_train.h, DESIGN.md 8h)
 def render_samples(engine, cfg, ws, ws_b, B, want_src=False):
     """distr_render_samples_export_batch on the forward workspace `ws` and the backward workspace `ws_b` as distr_render_backward_batch
@@ -886,14 +993,16 @@ def render_samples(engine, cfg, ws, ws_b, B, want_src=False):
     return xyz, coef, src, counts
 
 
-def train_plan_bytes(counts):
-    """Workspace bytes of one train_forward call on segments of `counts` points: mirror of distr_train_workspace_bytes (pure Python, a
-    function of the counts alone -- the code length does not enter). About 20 KB per 64-padded row and the slabs of the weight gradients."""
+def train_plan_bytes(counts, out_dim=1):
+    """Workspace bytes of one train_forward call on segments of `counts` points: mirror of distr_train_workspace_bytes and, with
+    out_dim = 3, of distr_train_net_workspace_bytes (pure Python, a function of the counts and out_dim alone -- the code length and
+    lin3's rows do not enter). About 20 KB per 64-padded row and the slabs of the weight gradients; the three per-row arrays z, tanh, dz
+    have out_dim floats per row."""
     rows = train_segment_rows(counts)[-1]
     blocks, nseg, hid = rows // TRAIN_ROW_TILE, len(counts), 512
     nslab = train_slab_plan(rows)[1]
     up = lambda n: (n + 255) & ~255
-    b = up(4 * rows) + up(4 * blocks) + up(4 * nseg * 2 * hid) + up(16 * rows) + 8 * up(4 * rows * hid) + 3 * up(4 * rows) + 2 * up(4 * rows * hid)
+    b = up(4 * rows) + up(4 * blocks) + up(4 * nseg * 2 * hid) + up(16 * rows) + 8 * up(4 * rows * hid) + 3 * up(4 * rows * int(out_dim)) + 2 * up(4 * rows * hid)
     b += up(4 * blocks * 4 * hid) + 3 * up(4 * nseg * 4 * hid) + up(4 * nslab * hid * hid) + up(4 * blocks)
     return b + 256
 

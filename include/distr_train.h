@@ -101,6 +101,39 @@ int distr_train_backward_dropout(distr_ctx* ctx, const distr_train_weights* weig
 /* host code, no GPU: the definition above (1 = kept), for tests and callers */
 int distr_train_dropout_keep(uint64_t seed, uint32_t threshold, int32_t layer, int64_t segment, int64_t point, int32_t unit);
 
+/* ---- the same path for a network that is DESCRIBED instead of derived from C: the colour decoder.
+ * The 8x512 chain with latent_in=[4] and
+ *   lin0 (512, L + 3)                       columns [code (L) | xyz (3)]
+ *   lin3 (lin3_rows, 512)
+ *   lin4 (512, ld4 = lin3_rows + L + 3)     columns [lin3's outputs (lin3_rows) | code (L) | xyz (3)]
+ *   lin8 (out_dim, 512)                     followed by tanh
+ * The SDF decoder is L = C, lin3_rows = 509 - C, out_dim = 1 (ld4 = 512): the calls above are exactly these calls on that description.
+ * The colour decoder of load_decoder(color_size=cs) is L = 256 + cs, lin3_rows = 253, out_dim = 3; its code rows are [shape | colour].
+ * out[sum counts][out_dim] and g_out[sum counts][out_dim] in the caller's point order, g_latent[nseg][L]; distr_train_grads in the
+ * shapes the description implies. clamp_dist is honoured for out_dim == 1 and must be negative for out_dim == 3. X_4 holds lin3_rows
+ * columns. For out_dim == 1 the workspace is carved as above (the size and the offsets do not depend on L or lin3_rows); for out_dim ==
+ * 3 the three per-row arrays behind X_8 have three floats per row. Sum orders, padding, segments, latent_dev / latent_stride (0 or >=
+ * L), streams and the dropout struct (may be NULL) as above. Refused (DISTR_ERR_INVALID_ARG): a wrong struct_size, out_dim other than
+ * 1 or 3, lin3_rows outside 1..509, L outside 1..65536, a null pointer, a clamp_dist >= 0 with out_dim == 3; DISTR_ERR_WORKSPACE for
+ * a workspace that is too small. The two size functions return 0 for a description the calls refuse (pointers are not looked at). */
+typedef struct distr_train_net {
+  uint32_t struct_size;
+  int32_t  latent_size;   /* L: code length folded into c0 / c4 (SDF: C; colour: 256 + cs) */
+  int32_t  lin3_rows;     /* outputs of lin3 = activation columns of lin4 (SDF: 509 - C; colour: 253) */
+  int32_t  out_dim;       /* rows of lin8: 1 or 3 */
+  const float* W[9];
+  const float* b[9];
+} distr_train_net;
+
+size_t distr_train_net_workspace_bytes(const distr_train_net* net, int32_t nseg, const int64_t* counts_host);
+size_t distr_train_net_activation_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts_host, int32_t layer);
+int distr_train_net_forward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent_dev,
+                            int64_t latent_stride, const float* xyz_dev, float clamp_dist, float* out_dev, void* ws_dev, size_t ws_bytes,
+                            void* stream, const distr_train_dropout* drop);
+int distr_train_net_backward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent_dev,
+                             int64_t latent_stride, const float* g_out, float clamp_dist, void* ws_dev, const distr_train_grads* grads,
+                             float* g_latent, void* stream, const distr_train_dropout* drop);
+
 #ifdef __cplusplus
 }
 #endif
