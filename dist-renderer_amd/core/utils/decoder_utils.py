@@ -115,15 +115,39 @@ def decode_sdf_batch(decoder, latent_vectors, points, counts=None, clamp_dist=0.
     return out.reshape(shape + (1,))
 
 
+def _refuse_point_grads(name, points):
+    if points.requires_grad:
+        raise ValueError('%s: points.requires_grad is set, but points are data on the layer-wise path (no point gradients); '
+                         'pass points.detach(), or use %s for gradients to the points' % (name, name.replace('_train', '_batch')))
+
+
 def _train_layout(Cn, latent_vectors, points, counts):
     """Shape logic of decode_sdf_train: decode_sdf_batch's (_batch_layout), and points that ask for a gradient are refused. Runs
     without a GPU."""
     if latent_vectors is None:
         raise NotImplementedError('latent_vectors=None (a code in every input row, decoder_utils.py:58-59) is not supported')
-    if points.requires_grad:
-        raise ValueError('decode_sdf_train: points.requires_grad is set, but points are data on the layer-wise path (no point gradients); '
-                         'pass points.detach(), or use decode_sdf_batch for gradients to the points')
+    _refuse_point_grads('decode_sdf_train', points)
     return _batch_layout(Cn, latent_vectors, points, counts)
+
+
+def _train_prologue(name, decoder, points, dropout_seed, weights_of, layout):
+    """What decode_sdf_train and decode_color_train (`name`) do before their node, in this order: the decoder's checks (eval mode, or
+    with a seed the dropout tuple of functions.train_forward), its weights on the autograd graph (weights_of(decoder) -> (Ws, bs)),
+    the refusal of points that ask for a gradient, the shapes (layout(Ws) -> (flat points, counts, output shape)), the device.
+    -> (W0..W8 + b0..b8, flat points, counts, output shape, dropout)"""
+    module = decoder.module if hasattr(decoder, 'module') else decoder
+    dropout = None
+    if dropout_seed is None:
+        functions._check_eval(module)
+    else:
+        params = functions.train_dropout_params(module, dropout_seed)
+        dropout = None if params is None else params + (int(dropout_seed), 0)
+    Ws, bs = weights_of(decoder)
+    _refuse_point_grads(name, points)
+    x, counts, shape = layout(Ws)
+    if x.device.type != 'cuda':
+        raise RuntimeError('%s: tensors must be on the GPU (no CPU path in this build)' % name)
+    return Ws + bs, x, counts, shape, dropout
 
 
 def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.1, dropout_seed=None):
@@ -139,18 +163,9 @@ def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.
     the gradients arrive at weight_g / weight_v. The fused engine is not involved: after an optimiser step the renderers and
     decode_sdf re-pack the weights by themselves."""
     from distr import decoder_pack
-    module = decoder.module if hasattr(decoder, 'module') else decoder
-    dropout = None
-    if dropout_seed is None:
-        functions._check_eval(module)
-    else:
-        params = functions.train_dropout_params(module, dropout_seed)
-        dropout = None if params is None else params + (int(dropout_seed), 0)
-    Ws, bs = decoder_pack.effective_weights_torch(decoder)
-    x, counts, shape = _train_layout(Ws[0].shape[1] - 3, latent_vectors, points, counts)
-    if x.device.type != 'cuda':
-        raise RuntimeError('decode_sdf_train: tensors must be on the GPU (no CPU path in this build)')
-    out = functions.decode_sdf_train_call(Ws + bs, latent_vectors, x, counts, clamp_dist, dropout)
+    weights, x, counts, shape, dropout = _train_prologue('decode_sdf_train', decoder, points, dropout_seed, decoder_pack.effective_weights_torch,
+                                                         lambda Ws: _train_layout(Ws[0].shape[1] - 3, latent_vectors, points, counts))
+    out = functions.decode_sdf_train_call(weights, latent_vectors, x, counts, clamp_dist, dropout)
     return out.reshape(shape + (1,))
 
 
@@ -236,19 +251,7 @@ def decode_color_train(decoder, color_codes, shape_codes, points, counts=None, d
     folded on the autograd graph. The colour engine is not involved: after an optimiser step decode_color* and SDFRenderer_color
     re-pack the weights by themselves."""
     from distr import decoder_pack
-    module = decoder.module if hasattr(decoder, 'module') else decoder
-    dropout = None
-    if dropout_seed is None:
-        functions._check_eval(module)
-    else:
-        params = functions.train_dropout_params(module, dropout_seed)
-        dropout = None if params is None else params + (int(dropout_seed), 0)
-    Ws, bs = decoder_pack.effective_weights_torch_color(decoder)
-    if points.requires_grad:
-        raise ValueError('decode_color_train: points.requires_grad is set, but points are data on the layer-wise path (no point gradients); '
-                         'pass points.detach(), or use decode_color_batch for gradients to the points')
-    x, counts, shape = _color_batch_layout(color_codes, shape_codes, points, counts)
-    if x.device.type != 'cuda':
-        raise RuntimeError('decode_color_train: tensors must be on the GPU (no CPU path in this build)')
-    out = functions.decode_color_train_call(Ws + bs, color_codes, shape_codes, x, counts, dropout)
+    weights, x, counts, shape, dropout = _train_prologue('decode_color_train', decoder, points, dropout_seed, decoder_pack.effective_weights_torch_color,
+                                                         lambda Ws: _color_batch_layout(color_codes, shape_codes, points, counts))
+    out = functions.decode_color_train_call(weights, color_codes, shape_codes, x, counts, dropout)
     return out.reshape(shape + (3,))

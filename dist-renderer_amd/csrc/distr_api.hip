@@ -2661,6 +2661,9 @@ struct TrainPlan {
   int32_t *rowpt, *blkseg, *blkpt0;
   float *c0c4, *xyz4, *X[9] /* 1..8 */, *z, *th, *dz, *D[2], *colpart, *colseg[3] /* lin0, lin4, the others */, *slabs;
   int out_w[9], in_w[9];     // GEMM widths: rows of W_l, and the columns of W_l that multiply the saved activation (lin4: n3)
+  size_t bytes;              // what the carve takes
+  train::DropArgs da;        // the call's dropout as the kernels take it (train_call)
+  uint32_t drop_mask;
 };
 
 void train_slab_plan(int64_t rows, int64_t* len, int* count) {
@@ -2696,12 +2699,6 @@ int train_plan(distr_ctx* ctx, int32_t L, int32_t n3, int32_t nout, int32_t nseg
   return DISTR_OK;
 }
 
-// the SDF decoder of the calls that take distr_train_weights
-int train_plan_sdf(distr_ctx* ctx, int32_t C, int32_t nseg, const int64_t* counts, TrainPlan& p) {
-  if (C < 1 || C > HID - 4) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_size %d: 1..%d", C, HID - 4);
-  return train_plan(ctx, C, HID - 3 - C, 1, nseg, counts, p);
-}
-
 size_t train_carve(void* base, TrainPlan& p) {
   WsCarve c(base);
   const size_t R = (size_t)p.rows;
@@ -2716,6 +2713,15 @@ size_t train_carve(void* base, TrainPlan& p) {
   p.slabs = c.take<float>((size_t)p.nslab * HID * HID);
   p.blkpt0 = c.take<int32_t>((size_t)p.blocks);      // (last: the offsets of everything above are those of the path without dropout)
   return c.bytes();
+}
+
+// plan and carve of a description (its pointers are not looked at): every size, offset and train call goes through here.
+// base == nullptr: sizes and offsets only.
+int train_layout(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts, void* base, TrainPlan& p) {
+  if (!net || net->struct_size != sizeof(distr_train_net)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: struct_size (use DISTR_INIT)");
+  if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts, p)) return rc;
+  p.bytes = train_carve(base, p);
+  return DISTR_OK;
 }
 
 inline int vec_ok(const void* p, int ld) { return ((uintptr_t)p % 16 == 0 && ld % 4 == 0) ? 1 : 0; }
@@ -2753,27 +2759,28 @@ int train_drop_args(distr_ctx* ctx, const distr_train_dropout* d, int32_t nseg, 
   return DISTR_OK;
 }
 
-int train_weights_ok(distr_ctx* ctx, const distr_train_weights* w) {
-  if (!w || w->struct_size != sizeof(distr_train_weights)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_weights: struct_size (use DISTR_INIT)");
+// the nine W / b pairs of a description; name: the struct the caller passed, for the message
+int train_pointers_ok(distr_ctx* ctx, const distr_train_net* net, const char* name) {
   for (int l = 0; l < 9; ++l)
-    if (!w->W[l] || !w->b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_weights: null pointer for lin%d", l);
+    if (!net->W[l] || !net->b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "%s: null pointer for lin%d", name, l);
   return DISTR_OK;
 }
 
-int train_net_ok(distr_ctx* ctx, const distr_train_net* w) {
-  if (!w || w->struct_size != sizeof(distr_train_net)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: struct_size (use DISTR_INIT)");
-  for (int l = 0; l < 9; ++l)
-    if (!w->W[l] || !w->b[l]) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: null pointer for lin%d", l);
-  return DISTR_OK;
-}
-
-// distr_train_weights as the description of its SDF decoder (checked by train_weights_ok / train_plan_sdf before it is used)
-distr_train_net train_net_of(const distr_train_weights* w) {
-  distr_train_net n;
+// the SDF decoder of code length C as a description: (C, 509 - C, 1), no pointers yet; false for a C outside 1..508
+bool train_sdf_net(int32_t C, distr_train_net& n) {
   memset(&n, 0, sizeof(n));
-  n.struct_size = sizeof(n); n.latent_size = w->latent_size; n.lin3_rows = HID - 3 - w->latent_size; n.out_dim = 1;
+  n.struct_size = sizeof(n); n.latent_size = C; n.lin3_rows = HID - 3 - C; n.out_dim = 1;
+  return C >= 1 && C <= HID - 4;
+}
+
+// distr_train_weights -> the description of its SDF decoder (the pointers are checked by the entry)
+int train_net_of(distr_ctx* ctx, const distr_train_weights* w, distr_train_net& n) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);      // (a refusal writes the context's message)
+  if (!w || w->struct_size != sizeof(distr_train_weights)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_weights: struct_size (use DISTR_INIT)");
+  if (!train_sdf_net(w->latent_size, n)) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_size %d: 1..%d", w->latent_size, HID - 4);
   for (int l = 0; l < 9; ++l) { n.W[l] = w->W[l]; n.b[l] = w->b[l]; }
-  return n;
+  return DISTR_OK;
 }
 
 // g_W of one layer's activation columns: Delta^T X over the K slabs, then the slabs in order
@@ -2809,28 +2816,38 @@ int train_grads_ok(distr_ctx* ctx, const distr_train_grads* gr) {
   return DISTR_OK;
 }
 
-// the forward on a checked description and its plan (the caller holds the EntryGuard)
-int train_forward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, int32_t nseg, const float* latent, int64_t latent_stride, const float* xyz,
-                      float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
-  train::DropArgs da;
-  uint32_t drop_mask;
-  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
+// THE check of a train call's arguments, forward and backward alike (the caller holds the EntryGuard). name: the struct the caller
+// passed its weights in. gr: the backward's gradients (backward = true). io: the per-point array, xyz or the upstream gradient.
+// Leaves the plan carved on the caller's workspace, with the dropout as the kernels take it.
+int train_call(distr_ctx* ctx, const distr_train_net* net, const char* name, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride,
+               const float* io, float clamp, void* ws, const distr_train_dropout* drop, bool backward, const distr_train_grads* gr, TrainPlan& p) {
+  if (int rc = train_layout(ctx, net, nseg, counts, ws, p)) return rc;
+  if (int rc = train_pointers_ok(ctx, net, name)) return rc;
+  if (int rc = train_drop_args(ctx, drop, nseg, p.da, p.drop_mask)) return rc;
+  if (backward)
+    if (int rc = train_grads_ok(ctx, gr)) return rc;
+  if (p.nout != 1 && clamp >= 0.f)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: clamp_dist %g with out_dim %d: a clamp belongs to out_dim 1 (pass a negative value)", (double)clamp, p.nout);
+  if (latent_stride != 0 && latent_stride < p.C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, p.C);
+  if (!latent || !ws || (p.n > 0 && !io)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  return DISTR_OK;
+}
+
+// the forward's launch sequence on a checked call
+int train_forward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, const float* latent, int64_t latent_stride, const float* xyz, float clamp,
+                         float* sdf, void* stream) {
   const int C = p.C;
-  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
-  if (!latent || !ws || (p.n > 0 && (!xyz || !sdf))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  if (ws_bytes < train_carve(nullptr, p)) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
-  train_carve(ws, p);
   if (p.rows == 0) return DISTR_OK;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(train::k_train_rows, grid1(p.rows), dim3(256), 0, s, p.sg, p.nseg, p.rows, p.rowpt, p.blkseg, p.blkpt0);
   LAUNCH_CHECK("k_train_rows");
-  da.blkseg = p.blkseg; da.blkpt0 = p.blkpt0;
+  p.da.blkseg = p.blkseg; p.da.blkpt0 = p.blkpt0;
   hipLaunchKernelGGL(train::k_train_consts, dim3(4, (unsigned)p.nseg), dim3(256), 0, s, p.c0c4, w->W[0], w->b[0], w->W[4], w->b[4], C, p.ld4, p.n3, latent, latent_stride);
   LAUNCH_CHECK("k_train_consts");
-  if (drop_mask & 1u) {
-    da.layer = 0;
+  if (p.drop_mask & 1u) {
+    p.da.layer = 0;
     hipLaunchKernelGGL(train::k_train_lin0_drop, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4,
-                       w->W[0], C, p.X[1], p.xyz4, da);
+                       w->W[0], C, p.X[1], p.xyz4, p.da);
   } else
     hipLaunchKernelGGL(train::k_train_lin0, dim3((unsigned)p.blocks), dim3(256), 0, s, xyz, (const int32_t*)p.rowpt, (const int32_t*)p.blkseg, (const float*)p.c0c4, w->W[0], C,
                        p.X[1], p.xyz4);
@@ -2844,20 +2861,18 @@ int train_forward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, in
       g.ctab = p.c0c4 + HID; g.ctab_stride = 2 * HID; g.blkseg = p.blkseg;
       g.tailW = w->W[4] + (p.ld4 - 3); g.tail_ld = p.ld4; g.xyz4 = p.xyz4;
     } else g.bias = w->b[l];
-    da.layer = (uint32_t)l;
-    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s, (l < 8 && (drop_mask >> l & 1u)) ? &da : nullptr)) return rc;
+    p.da.layer = (uint32_t)l;
+    if (int rc = train_gemm<true, true, train::EPI_FWD>(ctx, "k_train_gemm<forward>", g, 1, s, (l < 8 && (p.drop_mask >> l & 1u)) ? &p.da : nullptr)) return rc;
   }
   hipLaunchKernelGGL(train::k_train_out, grid1((int64_t)p.rows * p.nout), dim3(256), 0, s, (const float*)p.z, (const int32_t*)p.rowpt, p.rows, p.nout, clamp, p.th, sdf);
   LAUNCH_CHECK("k_train_out");
   return DISTR_OK;
 }
 
-int train_backward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, int32_t nseg, const float* latent, int64_t latent_stride, const float* g_sdf,
-                       float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream, train::DropArgs& da, uint32_t drop_mask) {
-  const int C = p.C;
-  if (latent_stride != 0 && latent_stride < C) return fail(ctx, DISTR_ERR_INVALID_ARG, "latent_stride %lld: 0 (shared code) or >= %d", (long long)latent_stride, C);
-  if (!latent || !ws || (p.n > 0 && !g_sdf)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
-  train_carve(ws, p);
+// the backward's launch sequence on a checked call
+int train_backward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, const float* latent, int64_t latent_stride, const float* g_sdf, float clamp,
+                          const distr_train_grads* gr, float* g_latent, void* stream) {
+  const int C = p.C, nseg = p.nseg;
   hipStream_t s = (hipStream_t)stream;
   if (p.rows == 0) {       // an empty list: every gradient is zero
     for (int l = 0; l < 9; ++l) {
@@ -2882,7 +2897,7 @@ int train_backward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, i
     g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = l == 4 ? p.ld4 : HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
     g.Cout = p.D[cur]; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
     // X_l went through lin(l-1)'s dropout: a dropped unit is an exact zero there, a kept one carries the factor scale
-    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (drop_mask >> (l - 1) & 1u) ? &da : nullptr)) return rc;
+    if (int rc = train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (p.drop_mask >> (l - 1) & 1u) ? &p.da : nullptr)) return rc;
     delta = p.D[cur]; ldd = HID; cur ^= 1;
     const int m = l - 1;       // delta now belongs to lin m
     if (m >= 1) {
@@ -2902,39 +2917,61 @@ int train_backward_net(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, i
   return DISTR_OK;
 }
 
+
+// THE way into the forward: every public forward is this call on a description
+int train_forward_entry(distr_ctx* ctx, const distr_train_net* net, const char* name, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride,
+                        const float* xyz, float clamp, float* out, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  TrainPlan p;
+  if (int rc = train_call(ctx, net, name, nseg, counts, latent, latent_stride, xyz, clamp, ws, drop, false, nullptr, p)) return rc;
+  if (p.n > 0 && !out) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < p.bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
+  return train_forward_launch(ctx, net, p, latent, latent_stride, xyz, clamp, out, stream);
+}
+
+// THE way into the backward
+int train_backward_entry(distr_ctx* ctx, const distr_train_net* net, const char* name, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride,
+                         const float* g_out, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream, const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  TrainPlan p;
+  if (int rc = train_call(ctx, net, name, nseg, counts, latent, latent_stride, g_out, clamp, ws, drop, true, gr, p)) return rc;
+  return train_backward_launch(ctx, net, p, latent, latent_stride, g_out, clamp, gr, g_latent, stream);
+}
+
+// workspace bytes (layer 0) or the byte offset of X_layer (1..8) behind the aligned base; 0 for what the calls refuse
+size_t train_bytes_or_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts, int32_t layer) {
+  TrainPlan p;
+  if (layer < 0 || layer > 8 || train_layout(nullptr, net, nseg, counts, nullptr, p) != DISTR_OK) return 0;
+  return layer ? (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt) : p.bytes;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t distr_train_workspace_bytes(int32_t latent_size, int32_t nseg, const int64_t* counts_host) {
-  TrainPlan p;
-  return train_plan_sdf(nullptr, latent_size, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
+  distr_train_net net;
+  return train_sdf_net(latent_size, net) ? train_bytes_or_offset(&net, nseg, counts_host, 0) : 0;
 }
 
 size_t distr_train_activation_offset(int32_t latent_size, int32_t nseg, const int64_t* counts_host, int32_t layer) {
-  TrainPlan p;
-  if (layer < 1 || layer > 8 || train_plan_sdf(nullptr, latent_size, nseg, counts_host, p) != DISTR_OK) return 0;
-  train_carve(nullptr, p);
-  return (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt);
+  distr_train_net net;
+  return layer >= 1 && train_sdf_net(latent_size, net) ? train_bytes_or_offset(&net, nseg, counts_host, layer) : 0;
 }
 
 size_t distr_train_net_workspace_bytes(const distr_train_net* net, int32_t nseg, const int64_t* counts_host) {
-  TrainPlan p;
-  if (!net || net->struct_size != sizeof(distr_train_net)) return 0;
-  return train_plan(nullptr, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p) == DISTR_OK ? train_carve(nullptr, p) : 0;
+  return train_bytes_or_offset(net, nseg, counts_host, 0);
 }
 
 size_t distr_train_net_activation_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts_host, int32_t layer) {
-  TrainPlan p;
-  if (!net || net->struct_size != sizeof(distr_train_net) || layer < 1 || layer > 8) return 0;
-  if (train_plan(nullptr, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p) != DISTR_OK) return 0;
-  train_carve(nullptr, p);
-  return (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt);
+  return layer >= 1 ? train_bytes_or_offset(net, nseg, counts_host, layer) : 0;
 }
 
 int64_t distr_train_segment_row(int32_t nseg, const int64_t* counts_host, int32_t seg) {
   TrainPlan p;
-  if (seg < 0 || seg > nseg || train_plan_sdf(nullptr, 1, nseg, counts_host, p) != DISTR_OK) return -1;
+  if (seg < 0 || seg > nseg || train_plan(nullptr, 1, 1, 1, nseg, counts_host, p) != DISTR_OK) return -1;
   return p.seg_row[seg];
 }
 
@@ -2957,24 +2994,14 @@ int distr_train_forward(distr_ctx* ctx, const distr_train_weights* w, int32_t ns
 
 int distr_train_forward_dropout(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                                 const float* xyz, float clamp, float* sdf, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (int rc = train_weights_ok(ctx, w)) return rc;
-  TrainPlan p;
-  if (int rc = train_plan_sdf(ctx, w->latent_size, nseg, counts_host, p)) return rc;
-  const distr_train_net net = train_net_of(w);
-  return train_forward_net(ctx, &net, p, nseg, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, stream, drop);
+  distr_train_net net;
+  if (int rc = train_net_of(ctx, w, net)) return rc;
+  return train_forward_entry(ctx, &net, "distr_train_weights", nseg, counts_host, latent, latent_stride, xyz, clamp, sdf, ws, ws_bytes, stream, drop);
 }
 
 int distr_train_net_forward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                             const float* xyz, float clamp, float* out, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (int rc = train_net_ok(ctx, net)) return rc;
-  TrainPlan p;
-  if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p)) return rc;
-  if (p.nout != 1 && clamp >= 0.f) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: clamp_dist %g with out_dim %d: a clamp belongs to out_dim 1 (pass a negative value)", (double)clamp, p.nout);
-  return train_forward_net(ctx, net, p, nseg, latent, latent_stride, xyz, clamp, out, ws, ws_bytes, stream, drop);
+  return train_forward_entry(ctx, net, "distr_train_net", nseg, counts_host, latent, latent_stride, xyz, clamp, out, ws, ws_bytes, stream, drop);
 }
 
 int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
@@ -2985,33 +3012,15 @@ int distr_train_backward(distr_ctx* ctx, const distr_train_weights* w, int32_t n
 int distr_train_backward_dropout(distr_ctx* ctx, const distr_train_weights* w, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                                  const float* g_sdf, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
                                  const distr_train_dropout* drop) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (int rc = train_weights_ok(ctx, w)) return rc;
-  train::DropArgs da;
-  uint32_t drop_mask;
-  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
-  if (int rc = train_grads_ok(ctx, gr)) return rc;
-  TrainPlan p;
-  if (int rc = train_plan_sdf(ctx, w->latent_size, nseg, counts_host, p)) return rc;
-  const distr_train_net net = train_net_of(w);
-  return train_backward_net(ctx, &net, p, nseg, latent, latent_stride, g_sdf, clamp, ws, gr, g_latent, stream, da, drop_mask);
+  distr_train_net net;
+  if (int rc = train_net_of(ctx, w, net)) return rc;
+  return train_backward_entry(ctx, &net, "distr_train_weights", nseg, counts_host, latent, latent_stride, g_sdf, clamp, ws, gr, g_latent, stream, drop);
 }
 
 int distr_train_net_backward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
                              const float* g_out, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
                              const distr_train_dropout* drop) {
-  if (!ctx) return DISTR_ERR_INVALID_ARG;
-  EntryGuard guard_(ctx);
-  if (int rc = train_net_ok(ctx, net)) return rc;
-  train::DropArgs da;
-  uint32_t drop_mask;
-  if (int rc = train_drop_args(ctx, drop, nseg, da, drop_mask)) return rc;
-  if (int rc = train_grads_ok(ctx, gr)) return rc;
-  TrainPlan p;
-  if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts_host, p)) return rc;
-  if (p.nout != 1 && clamp >= 0.f) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: clamp_dist %g with out_dim %d: a clamp belongs to out_dim 1 (pass a negative value)", (double)clamp, p.nout);
-  return train_backward_net(ctx, net, p, nseg, latent, latent_stride, g_out, clamp, ws, gr, g_latent, stream, da, drop_mask);
+  return train_backward_entry(ctx, net, "distr_train_net", nseg, counts_host, latent, latent_stride, g_out, clamp, ws, gr, g_latent, stream, drop);
 }
 
 }  // extern "C"

@@ -713,15 +713,15 @@ def _train_dropout_struct(dropout, chunk_base=0):
 class TrainSaved(object):
     """What train_forward keeps for train_backward: the workspace with the saved layer inputs, and the call it belongs to."""
 
-    def __init__(self, ctx, ws, C_len, counts, weights, lat, stride, clamp, dropout=None, net=None):
-        self.ctx, self.ws, self.latent_size, self.counts = ctx, ws, C_len, list(counts)
+    def __init__(self, ctx, ws, net, counts, weights, lat, stride, clamp, dropout=None):
+        self.ctx, self.ws, self.net, self.counts = ctx, ws, net, list(counts)       # net: (L, lin3_rows, out_dim), the SDF decoder's too
         self.weights, self.lat, self.stride, self.clamp, self.dropout = weights, lat, stride, clamp, dropout
+        self.latent_size, self.lin3_rows, self.out_dim = net
         self.seg_rows = train_segment_rows(counts)
-        self.net = net                                   # None: the SDF decoder of code length C_len; else (L, lin3_rows, out_dim)
-        self.lin3_rows, self.out_dim = (509 - C_len, 1) if net is None else (int(net[1]), int(net[2]))
 
-    def _cnt(self):
-        return (C.c_int64 * len(self.counts))(*self.counts)
+    def call_args(self):
+        """(distr_train_net*, nseg, counts_host) as every distr_train_net_* function takes them first"""
+        return C.byref(_train_net_struct(self.weights, self.net)), len(self.counts), (C.c_int64 * len(self.counts))(*self.counts)
 
     def rows(self, s):
         """(first row, last row + 1) of segment s's points in the workspace (its padded rows follow)."""
@@ -730,24 +730,13 @@ class TrainSaved(object):
     def activations(self, layer):
         """(rows, width) f32 view of X_layer (1..8), the saved input of lin_layer = relu of lin_(layer-1); width 512, lin3_rows (the SDF
         decoder: 509 - C) for layer 4."""
-        if self.net is None:
-            off = self.ctx.L.distr_train_activation_offset(self.latent_size, len(self.counts), self._cnt(), int(layer))
-        else:
-            off = self.ctx.L.distr_train_net_activation_offset(C.byref(_train_net_struct(self.weights, self.net)), len(self.counts), self._cnt(), int(layer))
+        off = self.ctx.L.distr_train_net_activation_offset(*(self.call_args() + (int(layer),)))
         if not off:
             raise ValueError('layer %r: 1..8' % (layer,))
         R = self.seg_rows[-1]
         base = (-self.ws.data_ptr()) % 256
         x = self.ws[base + off: base + off + R * 512 * 4].view(torch.float32).reshape(R, 512)
         return x[:, :self.lin3_rows] if layer == 4 else x
-
-
-def _train_weight_struct(weights, C_len):
-    tw = binding.TrainWeights(latent_size=int(C_len))
-    for l in range(9):
-        tw.W[l] = weights[l].data_ptr()
-        tw.b[l] = weights[9 + l].data_ptr()
-    return tw
 
 
 def _train_net_struct(weights, net):
@@ -766,16 +755,17 @@ def train_net_shapes(net):
     return W + [(o,) for o, _ in W]
 
 
-def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None, net=None):
-    """Layer-wise decode_sdf of one segmented list of at most 64 segments (distr_train_forward): weights = [W0..W8, b0..b8] f32 device
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None, net=None, caller='train_forward'):
+    """Layer-wise decode of one segmented list of at most 64 segments (distr_train_net_forward): weights = [W0..W8, b0..b8] f32 device
     tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
-    A workspace above DISTR_TRAIN_MAX_BYTES is refused. ws_bytes (tests): the workspace size to pass instead of the one needed.
-    ws, out (tests): a uint8 device tensor to use as the workspace and an f32 (sum counts, 1) tensor for sdf, instead of fresh ones.
-    dropout: None, or (layer_mask, threshold, scale, seed, segment_base) -- train_dropout_params(...) + (seed, global index of segment 0)
-    (distr_train_forward_dropout); the saved activations are then those behind the dropout, and train_backward follows.
-    net: None = the SDF decoder, its code length derived from W0; or (L, lin3_rows, out_dim), a described network (distr_train_net_*,
-    DESIGN.md section 8i; the colour decoder is (256 + cs, 253, 3)): the weights have train_net_shapes(net), latents are (S, L) or
-    (1, L), the output is (sum counts, out_dim), and a clamp belongs to out_dim 1."""
+    A workspace above DISTR_TRAIN_MAX_BYTES is refused (the message names `caller`). ws_bytes (tests): the workspace size to pass
+    instead of the one needed. ws, out (tests): a uint8 device tensor to use as the workspace and an f32 (sum counts, 1) tensor for
+    sdf, instead of fresh ones.
+    dropout: None, or (layer_mask, threshold, scale, seed, segment_base) -- train_dropout_params(...) + (seed, global index of segment 0);
+    the saved activations are then those behind the dropout, and train_backward follows.
+    net: (L, lin3_rows, out_dim), the described network (the colour decoder is (256 + cs, 253, 3)): the weights
+    have train_net_shapes(net), latents are (S, L) or (1, L), the output is (sum counts, out_dim), and a clamp belongs to out_dim 1.
+    None = the SDF decoder, (C, 509 - C, 1) with the code length C of W0; a C outside 1..508 is refused here."""
     counts = [int(c) for c in counts]
     dev = points.device
     if dev.type != 'cuda':
@@ -784,58 +774,50 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
         raise ValueError('%d segments: one train_forward call takes 1..%d' % (len(counts), binding.MAX_SEGMENTS))
     ctx = _train_context(dev.index if dev.index is not None else torch.cuda.current_device())
     weights = [_f32c(t, dev) for t in weights]
-    C_len = weights[0].shape[1] - 3
-    nout = 1
-    if net is not None:
-        net = tuple(int(v) for v in net)
-        if len(net) != 3:
-            raise ValueError('net %r: (L, lin3_rows, out_dim)' % (net,))
-        if len(weights) != 18 or [tuple(t.shape) for t in weights] != train_net_shapes(net):
-            raise ValueError('net (L, lin3_rows, out_dim) = %r takes W0..W8, b0..b8 of shapes %r, got %r'
-                             % (net, train_net_shapes(net), [tuple(t.shape) for t in weights]))
-        C_len, nout = net[0], net[2]
+    if net is None:
+        C_len = weights[0].shape[1] - 3
+        if not 1 <= C_len <= 508:
+            raise binding.DistrError('train_forward: latent_size %d: 1..508 (the SDF decoder is the network (C, 509 - C, 1))' % C_len)
+        net = (C_len, 509 - C_len, 1)
+    net = tuple(int(v) for v in net)
+    if len(net) != 3:
+        raise ValueError('net %r: (L, lin3_rows, out_dim)' % (net,))
+    if len(weights) != 18 or [tuple(t.shape) for t in weights] != train_net_shapes(net):
+        raise ValueError('net (L, lin3_rows, out_dim) = %r takes W0..W8, b0..b8 of shapes %r, got %r'
+                         % (net, train_net_shapes(net), [tuple(t.shape) for t in weights]))
+    C_len, nout = net[0], net[2]
     lat = _f32c(latents, dev).reshape(-1, C_len)
     if lat.shape[0] not in (1, len(counts)):
         raise ValueError('latents have shape %s; %d segments take (%d, %d) or (1, %d)' % (tuple(latents.shape), len(counts), len(counts), C_len, C_len))
     x = _f32c(points, dev).reshape(-1, 3)
     if x.shape[0] != sum(counts):
         raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), x.shape[0]))
-    cnt = (C.c_int64 * len(counts))(*counts)
-    if net is None:
-        need = ctx.L.distr_train_workspace_bytes(C_len, len(counts), cnt)
-    else:
-        need = ctx.L.distr_train_net_workspace_bytes(C.byref(_train_net_struct(weights, net)), len(counts), cnt)
-        if not need:
-            raise ValueError('net (L, lin3_rows, out_dim) = %r: L >= 1, lin3_rows in 1..509, out_dim 1 or 3' % (net,))
+    stride = 0 if lat.shape[0] == 1 else C_len
+    saved = TrainSaved(ctx, ws, net, counts, weights, lat, stride, clamp_dist, dropout)
+    need = ctx.L.distr_train_net_workspace_bytes(*saved.call_args())
+    if not need:
+        raise ValueError('net (L, lin3_rows, out_dim) = %r: L >= 1, lin3_rows in 1..509, out_dim 1 or 3' % (net,))
     if need > train_max_bytes():
         raise binding.DistrError('%s: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
                                  'more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient follows the batch)'
-                                 % ('decode_sdf_train' if net is None else 'decode_color_train' if nout == 3 else 'train_forward', x.shape[0], need,
-                                    train_max_bytes()))
+                                 % (caller, x.shape[0], need, train_max_bytes()))
     if ws is None:
-        ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
-    stride = 0 if lat.shape[0] == 1 else C_len
+        ws = saved.ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
     if out is None:
         out = torch.empty(x.shape[0], nout, dtype=torch.float32, device=dev)
     if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.shape[0] * nout:
         raise ValueError('train_forward: ws is a contiguous uint8 tensor, out a contiguous f32 tensor of %d values' % (x.shape[0] * nout))
     p = binding.ptr
     td = _train_dropout_struct(dropout)
-    if net is not None:
-        ctx.check(ctx.L.distr_train_net_forward(ctx.h, C.byref(_train_net_struct(weights, net)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
-                                                p(out), p(ws), ws.numel(), ctx.stream(), None if td is None else C.byref(td)))
-    elif td is None:
-        ctx.check(ctx.L.distr_train_forward(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x), _clamp_arg(clamp_dist),
-                                            p(out), p(ws), ws.numel(), ctx.stream()))
-    else:
-        ctx.check(ctx.L.distr_train_forward_dropout(ctx.h, C.byref(_train_weight_struct(weights, C_len)), len(counts), cnt, p(lat), stride, p(x),
-                                                    _clamp_arg(clamp_dist), p(out), p(ws), ws.numel(), ctx.stream(), C.byref(td)))
-    return out, TrainSaved(ctx, ws, C_len, counts, weights, lat, stride, clamp_dist, dropout, net)
+    ctx.check(ctx.L.distr_train_net_forward(*((ctx.h,) + saved.call_args() + (p(lat), stride, p(x), _clamp_arg(clamp_dist), p(out), p(ws), ws.numel(), ctx.stream(),
+                                                                               None if td is None else C.byref(td)))))
+    return out, saved
 
 
 def train_backward(saved, g_sdf, out=None):
-    """Backward of train_forward (distr_train_backward): g_sdf (sum counts,) -> ([g_W0..g_W8, g_b0..g_b8], g_latent (S, C): one row per
-    segment, also for a shared code). out (tests): (the eighteen gradient tensors, g_latent) to write into instead of fresh ones."""
+    """Backward of train_forward (distr_train_net_backward): g_sdf (sum counts, out_dim) -> ([g_W0..g_W8, g_b0..g_b8], g_latent (S, C):
+    one row per segment, also for a shared code). out (tests): (the eighteen gradient tensors, g_latent) to write into instead of fresh
+    ones."""
     ctx, dev = saved.ctx, saved.ws.device
     gs = _f32c(g_sdf, dev).reshape(-1)
     if gs.numel() != sum(saved.counts) * saved.out_dim:
@@ -854,18 +836,50 @@ def train_backward(saved, g_sdf, out=None):
         tg.g_b[l] = grads[9 + l].data_ptr()
     p = binding.ptr
     td = _train_dropout_struct(saved.dropout)
-    if saved.net is not None:
-        ctx.check(ctx.L.distr_train_net_backward(ctx.h, C.byref(_train_net_struct(saved.weights, saved.net)), len(saved.counts), saved._cnt(), p(saved.lat),
-                                                 saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream(),
-                                                 None if td is None else C.byref(td)))
-    elif td is None:
-        ctx.check(ctx.L.distr_train_backward(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(), p(saved.lat),
-                                             saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream()))
-    else:
-        ctx.check(ctx.L.distr_train_backward_dropout(ctx.h, C.byref(_train_weight_struct(saved.weights, saved.latent_size)), len(saved.counts), saved._cnt(),
-                                                     p(saved.lat), saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg), p(g_lat), ctx.stream(),
-                                                     C.byref(td)))
+    ctx.check(ctx.L.distr_train_net_backward(*((ctx.h,) + saved.call_args() + (p(saved.lat), saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg),
+                                                                                p(g_lat), ctx.stream(), None if td is None else C.byref(td)))))
     return grads, g_lat
+
+
+def _add_in_order(total, grads):
+    """THE accumulator of the weight gradients of several train calls: the first call's tensors, then `a += b` in call order."""
+    if total is None:
+        return grads
+    for a, b in zip(total, grads):
+        a += b
+    return total
+
+
+def _eighteen(weights):
+    if len(weights) != 18:
+        raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
+
+
+def _train_chunks_forward(ctx, weights, lat, points, counts, clamp_dist, dropout, net, caller):
+    """The forward both train nodes share: code rows `lat` (S, L) or (1, L), more than 64 segments in chunks of 64 (a chunk's
+    segment_base is the dropout's + its first segment); keeps every chunk's TrainSaved on ctx for _train_chunks_backward."""
+    counts = [int(c) for c in counts]
+    x = points.detach().reshape(-1, 3)
+    outs, ctx.saved_chunks = [], []
+    for s0, ns, p0, row, stride in _multi_chunks(lat, segment_plan(counts)):
+        n = sum(counts[s0:s0 + ns])
+        drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
+        out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist, dropout=drop, net=net, caller=caller)
+        outs.append(out)
+        ctx.saved_chunks.append((saved, p0, n))
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+def _train_chunks_backward(ctx, g):
+    """The backward both train nodes share: the upstream gradient of the output -> (the eighteen weight gradients, the chunks' added in
+    chunk order; the code-gradient rows (S, L))"""
+    g = g.reshape(-1, ctx.saved_chunks[0][0].out_dim)
+    total, rows = None, []
+    for saved, p0, n in ctx.saved_chunks:
+        grads, g_lat = train_backward(saved, g[p0:p0 + n])
+        rows.append(g_lat)
+        total = _add_in_order(total, grads)
+    return total, (rows[0] if len(rows) == 1 else torch.cat(rows))
 
 
 class DecodeSdfTrainFunction(torch.autograd.Function):
@@ -876,35 +890,14 @@ class DecodeSdfTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, codes, points, counts, clamp_dist, dropout, *weights):
-        if len(weights) != 18:
-            raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
-        counts = [int(c) for c in counts]
-        plan = segment_plan(counts)
+        _eighteen(weights)
         lat = codes.detach().reshape(-1, weights[0].shape[1] - 3)
-        x = points.detach().reshape(-1, 3)
-        outs, ctx.saved_chunks = [], []
-        for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
-            n = sum(counts[s0:s0 + ns])
-            drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
-            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist, dropout=drop)
-            outs.append(out)
-            ctx.saved_chunks.append((saved, p0, n, s0, ns))
         ctx.codes_shape, ctx.shared = codes.shape, lat.shape[0] == 1
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        return _train_chunks_forward(ctx, weights, lat, points, counts, clamp_dist, dropout, None, 'decode_sdf_train')
 
     @staticmethod
     def backward(ctx, g):
-        g = g.reshape(-1)
-        total, rows = None, []
-        for saved, p0, n, s0, ns in ctx.saved_chunks:
-            grads, g_lat = train_backward(saved, g[p0:p0 + n])
-            rows.append(g_lat)
-            if total is None:
-                total = grads
-            else:
-                for a, b in zip(total, grads):
-                    a += b
-        g_rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+        total, g_rows = _train_chunks_backward(ctx, g)
         g_codes = (g_rows.sum(0) if ctx.shared and g_rows.shape[0] > 1 else g_rows).reshape(ctx.codes_shape)
         return (g_codes, None, None, None, None) + tuple(total)
 
@@ -934,37 +927,16 @@ class DecodeColorTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, color_codes, shape_codes, points, counts, dropout, *weights):
-        if len(weights) != 18:
-            raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
-        counts = [int(c) for c in counts]
-        plan = segment_plan(counts)
+        _eighteen(weights)
         net = color_train_net(weights)
         lat = color_code_rows(_CodeLayout(net[0], points.device), color_codes.detach(), shape_codes.detach(), len(counts))
-        x = points.detach().reshape(-1, 3)
-        outs, ctx.saved_chunks = [], []
-        for s0, ns, p0, row, stride in _multi_chunks(lat, plan):
-            n = sum(counts[s0:s0 + ns])
-            drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
-            out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], None, dropout=drop, net=net)
-            outs.append(out)
-            ctx.saved_chunks.append((saved, p0, n, s0, ns))
         ctx.code_like = (color_codes.detach(), shape_codes.detach())
         ctx.need = (color_codes.requires_grad, shape_codes.requires_grad)
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        return _train_chunks_forward(ctx, weights, lat, points, counts, None, dropout, net, 'decode_color_train')
 
     @staticmethod
     def backward(ctx, g):
-        g = g.reshape(-1, 3)
-        total, rows = None, []
-        for saved, p0, n, s0, ns in ctx.saved_chunks:
-            grads, g_lat = train_backward(saved, g[p0:p0 + n])
-            rows.append(g_lat)
-            if total is None:
-                total = grads
-            else:
-                for a, b in zip(total, grads):
-                    a += b
-        g_rows = rows[0] if len(rows) == 1 else torch.cat(rows)
+        total, g_rows = _train_chunks_backward(ctx, g)
         g_c, g_s = _split_code_grad(g_rows, *ctx.code_like)
         return ((g_c if ctx.need[0] else None), (g_s if ctx.need[1] else None), None, None, None) + tuple(total)
 
@@ -994,17 +966,16 @@ def render_samples(engine, cfg, ws, ws_b, B, want_src=False):
 
 
 def train_plan_bytes(counts, out_dim=1):
-    """Workspace bytes of one train_forward call on segments of `counts` points: mirror of distr_train_workspace_bytes and, with
-    out_dim = 3, of distr_train_net_workspace_bytes (pure Python, a function of the counts and out_dim alone -- the code length and
-    lin3's rows do not enter). About 20 KB per 64-padded row and the slabs of the weight gradients; the three per-row arrays z, tanh, dz
-    have out_dim floats per row."""
-    rows = train_segment_rows(counts)[-1]
-    blocks, nseg, hid = rows // TRAIN_ROW_TILE, len(counts), 512
-    nslab = train_slab_plan(rows)[1]
-    up = lambda n: (n + 255) & ~255
-    b = up(4 * rows) + up(4 * blocks) + up(4 * nseg * 2 * hid) + up(16 * rows) + 8 * up(4 * rows * hid) + 3 * up(4 * rows * int(out_dim)) + 2 * up(4 * rows * hid)
-    b += up(4 * blocks * 4 * hid) + 3 * up(4 * nseg * 4 * hid) + up(4 * nslab * hid * hid) + up(4 * blocks)
-    return b + 256
+    """Workspace bytes of one train_forward call on segments of `counts` points: distr_train_net_workspace_bytes on a description with
+    that out_dim (host code of the library, no GPU; a function of the counts and out_dim alone -- the code length and lin3's rows do
+    not enter the size, so fixed legal ones stand in). About 20 KB per 64-padded row and the slabs of the weight gradients; the three
+    per-row arrays z, tanh, dz have out_dim floats per row. ValueError for a list or an out_dim the calls refuse."""
+    counts = [int(c) for c in counts]
+    net = binding.TrainNet(latent_size=256, lin3_rows=253, out_dim=int(out_dim))
+    need = int(binding.lib().distr_train_net_workspace_bytes(C.byref(net), len(counts), (C.c_int64 * len(counts))(*counts)))
+    if not need:
+        raise ValueError('train_plan_bytes: %d segments of %r points, out_dim %r: not a list of one train call' % (len(counts), counts[:4], out_dim))
+    return need
 
 
 def render_train_chunks(counts, max_bytes):
@@ -1058,9 +1029,8 @@ def render_weight_grads(engine, cfg, ws, ws_b, B, weights, codes, max_bytes=None
     counts = [int(c) for c in counts_dev.cpu().tolist()]
     weights = [_f32c(w, engine.device) for w in weights]
     lat = _f32c(codes, engine.device).reshape(-1, engine.latent_size)
-    total = [torch.zeros_like(w) for w in weights]
+    total = None
     g_lat = torch.zeros(B, engine.latent_size, dtype=torch.float32, device=engine.device) if want_latent else None
-    first = True
     for piece in render_train_chunks(counts, train_max_bytes() if max_bytes is None else max_bytes):
         pts = torch.cat([xyz[v, a:a + n] for v, a, n in piece])
         cf = torch.cat([coef[v, a:a + n] for v, a, n in piece])
@@ -1068,15 +1038,11 @@ def render_weight_grads(engine, cfg, ws, ws_b, B, weights, codes, max_bytes=None
         _, saved = train_forward(weights, seg_codes, pts, [n for _, _, n in piece], clamp_dist=None)
         grads, rows = train_backward(saved, cf)
         del saved
-        if first:
-            total, first = grads, False
-        else:
-            for a, b in zip(total, grads):
-                a += b
+        total = _add_in_order(total, grads)
         if want_latent:
             for (v, _, _), row in zip(piece, rows):
                 g_lat[v] += row
-    return total, g_lat
+    return (total if total is not None else [torch.zeros_like(w) for w in weights]), g_lat
 
 
 def depth_samples_count(engine, cfg, depth):

@@ -370,6 +370,7 @@ def test_sgd_loop(fixture_decoder):
 
 def test_refusals(fixture_decoder, monkeypatch):
     import torch
+    import train_abi
     from core.utils.decoder_utils import decode_sdf_train
     from distr import binding, decoder_pack, functions
     Ws, bs, latent = fixture_decoder
@@ -408,13 +409,13 @@ def test_refusals(fixture_decoder, monkeypatch):
         rc = L.distr_train_forward(ctx.h, C.byref(tw), nseg, counts, p(lat), stride, p(pts), 0.1, p(out), p(ws), need, ctx.stream())
         return rc, L.distr_last_error(ctx.h).decode()
     for bad_c in (0, 509):
-        rc, err = call(functions._train_weight_struct(weights, bad_c))
+        rc, err = call(train_abi.train_weights(weights, bad_c))
         assert rc == -1 and 'latent_size' in err, (bad_c, rc, err)
-    tw = functions._train_weight_struct(weights, 256)
+    tw = train_abi.train_weights(weights, 256)
     tw.b[6] = None
     rc, err = call(tw)
     assert rc == -1 and 'lin6' in err, (rc, err)
-    tw = functions._train_weight_struct(weights, 256)
+    tw = train_abi.train_weights(weights, 256)
     for kw, word in ((dict(nseg=0), 'nseg'), (dict(counts=(C.c_int64 * 2)(9, -1)), 'negative'), (dict(stride=100), 'latent_stride')):
         rc, err = call(tw, **kw)
         assert rc == -1 and word in err, (kw, rc, err)

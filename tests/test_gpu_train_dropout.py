@@ -505,6 +505,7 @@ def test_sgd_loop(fixture_decoder, monkeypatch):
 def test_refusals(fixture_decoder):
     import ctypes as C
     import torch
+    import train_abi
     from core.utils.decoder_utils import decode_sdf_train
     from distr import binding, decoder_pack, functions
     Ws, bs, _ = fixture_decoder
@@ -531,7 +532,7 @@ def test_refusals(fixture_decoder):
     need = L.distr_train_workspace_bytes(256, 2, cnt)
     out = torch.empty(8, 1, device='cuda')
     ws = torch.empty(need, dtype=torch.uint8, device='cuda')
-    tw = functions._train_weight_struct(weights, 256)
+    tw = train_abi.train_weights(weights, 256)
     good = dict(layer_mask=0xff, threshold=858993459, scale=1.25, seed=1, segment_base=0)
 
     def call(td):

@@ -116,6 +116,7 @@ def test_decode_sdf_train_takes_a_seed(fixture_decoder):
 
 def test_c_calls_refuse_bad_dropout_structs():
     """The struct is checked before anything touches the device: a context made without one answers."""
+    import train_abi
     from distr import binding
     binding.build_library()
     L = binding.lib()
@@ -129,10 +130,8 @@ def test_c_calls_refuse_bad_dropout_structs():
     assert h
     try:
         dummy = (C.c_float * 4)()
-        tw = binding.TrainWeights(latent_size=256)
-        tg = binding.TrainGrads()
-        for l in range(9):
-            tw.W[l] = tw.b[l] = tg.g_W[l] = tg.g_b[l] = C.addressof(dummy)
+        tw = train_abi.train_weights([C.addressof(dummy)] * 18, 256)
+        tg = train_abi.train_grads([C.addressof(dummy)] * 18)
         bad = [('struct_size', dict(good), 24), ('layer_mask', dict(good, layer_mask=0x100), None), ('scale', dict(good, scale=0.5), None),
                ('scale', dict(good, scale=float('nan')), None), ('scale', dict(good, scale=float('inf')), None),
                ('segment_base', dict(good, segment_base=-1), None)]
