@@ -16,7 +16,7 @@ from .renderer import SDFRenderer
 class SDFRenderer_color(SDFRenderer):
     # reference: renderer_rgb.py:13
     def __init__(self, decoder, decoder_color, intrinsic, img_hw=None, march_step=50, buffer_size=5, ray_marching_ratio=1.5,
-                 max_sample_dist=0.2, threshold=5e-5, use_gpu=True, is_eval=True):
+                 max_sample_dist=0.2, threshold=5e-5, use_gpu=True, is_eval=True, color_decoder_grad=False):
         super(SDFRenderer_color, self).__init__(decoder, intrinsic, img_hw=img_hw, march_step=march_step, buffer_size=buffer_size,
                                                 ray_marching_ratio=ray_marching_ratio, max_sample_dist=max_sample_dist,
                                                 threshold=threshold, use_gpu=use_gpu, is_eval=is_eval)
@@ -26,10 +26,24 @@ class SDFRenderer_color(SDFRenderer):
                                                   'has code length %d' % nlat)
         self.decoder_color = decoder_color.eval() if is_eval else decoder_color
         functions.get_color_engine(self.decoder_color, self.device)
+        # color_decoder_grad (not in the reference, where autograd simply does it): render / render_batch also back-propagate a loss on the
+        # colour image to decoder_color.parameters() -- one host sync per backward, so such a backward cannot be captured into a graph
+        # (DESIGN.md section 8j); off (the default) nothing changes. Also settable later (self.color_decoder_grad). The SDF decoder gets
+        # nothing from the colour image (its points are constants there): decoder_grad keeps its meaning
+        self.color_decoder_grad = bool(color_decoder_grad)
 
     @property
     def _color_engine(self):
         return functions.get_color_engine(self.decoder_color, self.device)
+
+    def _color_decoder_weights(self, no_grad=False):
+        """W0..W8, b0..b8 of decoder_color on its autograd graph (weight norm folded there) when this call back-propagates to it:
+        color_decoder_grad set, grad enabled, no_grad false and a parameter of decoder_color that requires grad; None otherwise."""
+        if not self.color_decoder_grad or no_grad or not torch.is_grad_enabled() or not any(p.requires_grad for p in self.decoder_color.parameters()):
+            return None
+        functions._check_eval(self.decoder_color)
+        Ws, bs = decoder_pack.effective_weights_torch_color(self.decoder_color)
+        return Ws + bs
 
     # reference: renderer_rgb.py:20
     def render_color(self, latent_color, latent, cam_pos, cam_rays, Zdepth, valid_mask, no_grad=False):
@@ -65,6 +79,13 @@ class SDFRenderer_color(SDFRenderer):
     # reference: renderer_rgb.py:73
     def render(self, latent_color, latent, R, T, clamp_dist=0.1, profile=False, no_grad=False, lighting_locations=None,
                lighting_energies=None):
+        if self._color_decoder_weights(no_grad) is not None:
+            # color_decoder_grad: the colours come from the colour stage's node with B = 1 (the node that carries the weight gradients);
+            # depth, normal, mask and min_sdf are bit for bit those below, the colours agree to rounding (render_batch's contract)
+            R, T = torch.as_tensor(R), torch.as_tensor(T)
+            outs = self.render_batch(latent_color, latent, R[None], T[None], clamp_dist=clamp_dist, no_grad=no_grad,
+                                     lighting_locations=lighting_locations, lighting_energies=lighting_energies)
+            return tuple(o[0] for o in outs)
         h, w = self.img_hw
         cfg = self._cfg(clamp_dist, 'recursive', True, want_normal=True, no_grad_depth=no_grad, no_grad_mask=no_grad,
                         no_grad_camera=no_grad)
@@ -97,7 +118,9 @@ class SDFRenderer_color(SDFRenderer):
         pixels compacted on the device, their points rebuilt from the rays, one segmented colour evaluation, one shading epilogue): every
         view's bytes and gradients are those of its own B = 1 call; against `render` the colours agree to rounding (the points are formed
         in another f32 order). Gradients reach both codes, the cameras and, with lights, the normal image -- and through it the render;
-        lights and energies are observations (ValueError if one requires grad). no_grad detaches what render(no_grad=True) detaches."""
+        lights and energies are observations (ValueError if one requires grad). no_grad detaches what render(no_grad=True) detaches.
+        With color_decoder_grad the backward also reaches decoder_color.parameters() (functions.ColorStageFunction's weights: one host
+        sync per backward); every other byte, forward and backward, is that of the flag-off call."""
         h, w = self.img_hw
         dev = self.calib_map.device
         to_dev = lambda t: t.to(device=dev, dtype=torch.float32)      # (per view, like render_depth_batch)
@@ -116,7 +139,7 @@ class SDFRenderer_color(SDFRenderer):
         if no_grad:
             depth, min_sdf = depth.detach(), min_sdf.detach()
         color = functions.color_stage_call(ceng, cfg, latent_color, latent, Rs, Ts, zdepth.detach(), mask, normal, lighting_locations,
-                                           lighting_energies, detach_color=no_grad)
+                                           lighting_energies, detach_color=no_grad, weights=self._color_decoder_weights(no_grad))
         return depth, normal, color, mask.reshape(B, h, w), min_sdf.reshape(B, h, w)
 
     def relight(self, color, normal, Zdepth, mask, R, T, lighting_locations, lighting_energies=None):

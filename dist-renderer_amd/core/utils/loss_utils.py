@@ -107,10 +107,20 @@ def compute_loss_normal(normal_output, valid_mask, normal_gt, valid_mask_gt, vis
     return (-cos).mean(), visualizer
 
 
+def compute_loss_color_batch(color_output, valid_mask, color_gt, valid_mask_gt, use_ssim=False):
+    """compute_loss_color of B views in one launch sequence (no counterpart in the reference, which runs once per view): color_output,
+    color_gt (B, H, W, 3), masks (B, H, W) -> (l1 (B,), ssim (B,) or None, overlap (B,) int32), the fused masked L1 and the reference's
+    SSIM term (functions.ColorLossFunction). Gradient flows to color_output only; color_gt requiring grad raises
+    ValueError. One divergence from the reference: a view with an empty overlap gives l1 = 0 with a zero gradient (the reference yields
+    NaN or raises) -- overlap[v] == 0 lets the caller see it."""
+    from distr import functions
+    return functions.color_loss_batch(color_output, valid_mask, color_gt, valid_mask_gt, use_ssim)
+
+
 def compute_loss_color(color_output, valid_mask, color_gt, valid_mask_gt, visualizer=None,
                        name=('color_output', 'color_gt', 'loss_color'), use_ssim=False):
-    """Mean L1 colour difference over the pixels valid in both masks (loss_utils.py:174-205; the SSIM variant needs the
-    reference's pytorch_ssim package and is taken from there when a reference checkout is importable)."""
+    """Mean L1 colour difference over the pixels valid in both masks (loss_utils.py:174-205; the SSIM variant is taken from the
+    reference's pytorch_ssim package when a reference checkout is importable, and from the fused loss otherwise)."""
     _show(visualizer, name[0], color_output)
     _show(visualizer, name[1], color_gt)
     both = _b(valid_mask) & _b(valid_mask_gt)
@@ -125,8 +135,12 @@ def compute_loss_color(color_output, valid_mask, color_gt, valid_mask_gt, visual
     loss = diff.abs().mean()
     if use_ssim:
         # (loss_utils.py:202-208: SSIM of the two images with everything outside the common mask zeroed; returned as a third value)
-        from core.utils import pytorch_ssim        # the reference's own package (extended __path__); absent -> ImportError
-        a = torch.where(both[..., None], color_gt, torch.zeros_like(color_gt)).permute(2, 0, 1)[None]
+        try:
+            from core.utils import pytorch_ssim    # the reference's own package (extended __path__) where a reference checkout is importable
+        except ImportError:                        # without one: the fused loss with B = 1, the same formula
+            _, ssim, _ = compute_loss_color_batch(color_output[None], valid_mask[None], color_gt[None], valid_mask_gt[None], use_ssim=True)
+            return loss, ssim[0], visualizer
+        a =torch.where(both[..., None], color_gt, torch.zeros_like(color_gt)).permute(2, 0, 1)[None]
         b = torch.where(both[..., None], color_output, torch.zeros_like(color_output)).permute(2, 0, 1)[None]
         return loss, pytorch_ssim.loss_ssim(a, b)[0], visualizer
     return loss, visualizer

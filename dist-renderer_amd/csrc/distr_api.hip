@@ -20,6 +20,7 @@
 #include "distr_samples.hpp"
 #include "distr_normal_grad.hpp"
 #include "distr_color_batch.hpp"
+#include "distr_color_loss.hpp"
 #include "distr_train.hpp"
 
 using namespace distr;
@@ -2622,6 +2623,82 @@ int distr_color_stage_backward_batch(distr_ctx* ctx, const distr_render_cfg* cfg
     hipLaunchKernelGGL(cbatch::k_cb_cam_fin, dim3(NV), blk, 0, s, p.G, C, (const int*)f.totals, (const float*)w.part, p.nblk, g_R, g_T);
     LAUNCH_CHECK("k_cb_cam_fin");
   }
+  return DISTR_OK;
+}
+
+// ---- the decoder list of the stage's backward, written out (include/distr_color_train.h). The same two carves as the stage: f.totals,
+// f.index and f.xyz are the forward's, w.g_col is what k_cb_bwd_pre wrote -- k_color_bwd reads it (const) and writes g_xyz and the tile
+// partials, k_points_latent_grad and the camera kernels write regions of their own, so it is intact when the backward returns.
+int distr_color_stage_samples_export_batch(distr_ctx* ctx, const distr_render_cfg* cfg, int32_t nviews, const void* ws_fwd, size_t ws_fwd_bytes,
+                                           const void* ws_bwd, size_t ws_bwd_bytes, float* xyz_out, float* up_out, int32_t* index_out, int64_t cap,
+                                           int32_t* counts_dev, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  CbPlan p;
+  if (int rc = cb_plan(ctx, cfg, nviews, p)) return rc;
+  if (!ws_fwd || !ws_bwd) return fail(ctx, DISTR_ERR_INVALID_ARG, "null workspace");
+  if (!xyz_out || !up_out || !counts_dev) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (cap < (int64_t)p.P) return fail(ctx, DISTR_ERR_INVALID_ARG, "colour stage export: cap %lld is below the %d rows a view's list can hold", (long long)cap, p.P);
+  if (ws_fwd_bytes < cb_fwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "colour stage: forward workspace too small: %zu < %zu", ws_fwd_bytes, cb_fwd_ws(nullptr, p).bytes);
+  if (ws_bwd_bytes < cb_bwd_ws(nullptr, p).bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "colour stage: backward workspace too small: %zu < %zu", ws_bwd_bytes, cb_bwd_ws(nullptr, p).bytes);
+  const CbFwdWs f = cb_fwd_ws(const_cast<void*>(ws_fwd), p);
+  const CbBwdWs w = cb_bwd_ws(const_cast<void*>(ws_bwd), p);
+  hipLaunchKernelGGL(cbatch::k_cb_export, dim3((unsigned)((p.P + cbatch::MB - 1) / cbatch::MB), (unsigned)nviews), dim3(cbatch::MB), 0, (hipStream_t)stream, p.P,
+                     (const int*)f.totals, (const int32_t*)f.index, (const float*)f.xyz, (const float*)w.g_col, xyz_out, up_out, index_out, cap, counts_dev);
+  LAUNCH_CHECK("k_cb_export");
+  return DISTR_OK;
+}
+
+// ---- the photometric loss of a batch of colour images (include/distr_color_train.h, kernels: distr_color_loss.hpp)
+size_t distr_color_loss_workspace_bytes(int32_t H, int32_t W, int32_t nviews, int32_t backward) {
+  if (H < 1 || W < 1 || (int64_t)H * W > ((int64_t)1 << 24) || nviews < 1 || nviews > DISTR_MAX_VIEWS) return 0;
+  const size_t P = (size_t)H * W, nblk = (P + closs::CB - 1) / closs::CB;
+  return (backward ? (size_t)nviews * P * 9 : (size_t)nviews * nblk * 3) * sizeof(float) + 256;
+}
+
+static int color_loss_args(distr_ctx* ctx, int32_t H, int32_t W, int32_t nviews, const void* ws, size_t ws_bytes, bool backward) {
+  if (H < 1 || W < 1 || (int64_t)H * W > ((int64_t)1 << 24)) return fail(ctx, DISTR_ERR_INVALID_ARG, "colour loss: image size %d x %d: at least 1 x 1, at most 2^24 pixels", H, W);
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
+  const size_t need = distr_color_loss_workspace_bytes(H, W, nviews, backward ? 1 : 0);
+  if (!ws || ws_bytes < need) return fail(ctx, DISTR_ERR_WORKSPACE, "colour loss: %s workspace too small: %zu < %zu", backward ? "backward" : "forward", ws ? ws_bytes : (size_t)0, need);
+  return DISTR_OK;
+}
+
+int distr_color_loss_forward_batch(distr_ctx* ctx, int32_t H, int32_t W, int32_t nviews, const float* rgb, const uint8_t* mask, const float* gt,
+                                   const uint8_t* gt_mask, int32_t want_ssim, float* l1_out, float* ssim_out, int32_t* overlap_out, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (!rgb || !mask || !gt || !gt_mask || !l1_out || !overlap_out || (want_ssim && !ssim_out)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (int rc = color_loss_args(ctx, H, W, nviews, ws, ws_bytes, false)) return rc;
+  const closs::Imgs I{H, W, H * W, rgb, gt, mask, gt_mask};
+  const int nblk = (I.P + closs::CB - 1) / closs::CB;
+  float* part = WsCarve(ws).take<float>((size_t)nviews * nblk * 3);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(closs::k_cl_fwd, dim3((unsigned)nblk, (unsigned)nviews), dim3(closs::CB), 0, s, I, want_ssim ? 1 : 0, nblk, part);
+  LAUNCH_CHECK("k_cl_fwd");
+  hipLaunchKernelGGL(closs::k_cl_fin, dim3((unsigned)nviews), dim3(closs::CB), 0, s, I.P, nblk, (const float*)part, l1_out, want_ssim ? ssim_out : (float*)nullptr, overlap_out);
+  LAUNCH_CHECK("k_cl_fin");
+  return DISTR_OK;
+}
+
+int distr_color_loss_backward_batch(distr_ctx* ctx, int32_t H, int32_t W, int32_t nviews, const float* rgb, const uint8_t* mask, const float* gt,
+                                    const uint8_t* gt_mask, const int32_t* overlap_dev, const float* g_l1, const float* g_ssim, float* g_rgb_out,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (!rgb || !mask || !gt || !gt_mask || !overlap_dev || !g_rgb_out) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (int rc = color_loss_args(ctx, H, W, nviews, ws, ws_bytes, true)) return rc;
+  const closs::Imgs I{H, W, H * W, rgb, gt, mask, gt_mask};
+  const dim3 grid((unsigned)((I.P + closs::CB - 1) / closs::CB), (unsigned)nviews);
+  float* dpart = WsCarve(ws).take<float>((size_t)nviews * I.P * 9);
+  hipStream_t s = (hipStream_t)stream;
+  if (g_ssim) {
+    hipLaunchKernelGGL(closs::k_cl_bwd_part, grid, dim3(closs::CB), 0, s, I, g_ssim, dpart);
+    LAUNCH_CHECK("k_cl_bwd_part");
+  }
+  hipLaunchKernelGGL(closs::k_cl_bwd, grid, dim3(closs::CB), 0, s, I, g_l1, overlap_dev, g_ssim ? (const float*)dpart : (const float*)nullptr, g_rgb_out);
+  LAUNCH_CHECK("k_cl_bwd");
   return DISTR_OK;
 }
 

@@ -16,6 +16,8 @@
 //     (k_latent_consts, k_ng_seg_table, k_color_bwd, k_points_latent_grad)
 //   8 k_cb_cam_bwd    per valid pixel: g_q = M g_x + the shading's g_q; g_d = z g_q, g_c = g_q; the explicit R of R l_m; 12 sums per block
 //   9 k_cb_cam_fin    per view: the block sums in block order, then c = -R^T T: g_R = ray part - T (x) g_c, g_T = -R g_c
+//   after the backward, on request (weight gradients of the colour decoder)
+//  10 k_cb_export     per valid pixel: its point, its upstream g_col and its pixel, out of the two workspaces into the caller's arrays
 //
 // Shading term of a pixel (renderer_rgb.py:54-62, 122-123): q = c + d z (no M^T), u_m = L_m - q, l_m = u_m / |u_m|,
 //   s = sum_m e_m ((R l_m) . n),  n = the transformed normal image's pixel.  With g_s = sum_c g_rgb_c colour_c:
@@ -305,6 +307,28 @@ DISTR_GLOBAL void __launch_bounds__(MB) k_cb_cam_fin(const Geo G, const Cams C, 
       if (g_T) g_T[3 * v + j] = -(R[j * 3 + 0] * tot.a[9] + R[j * 3 + 1] * tot.a[10] + R[j * 3 + 2] * tot.a[11]);
     }
   }
+}
+
+// The decoder list of the backward, written out (distr_color_stage_samples_export_batch, include/distr_color_train.h): grid (blocks of MB
+// list positions, views). Row r < N_v of view v: the point k_cb_points built, the upstream k_cb_bwd_pre wrote and the pixel, from
+// [v * P + r] of the workspaces to [v * cap + r] of the outputs; rows at or beyond N_v are not touched. counts[v] = N_v, the scan's total.
+// Reads both workspaces, changes neither.
+DISTR_GLOBAL void __launch_bounds__(MB) k_cb_export(int P, const int* __restrict__ totals, const int32_t* __restrict__ index,
+                                                    const float* __restrict__ xyz, const float* __restrict__ g_col, float* __restrict__ xyz_out,
+                                                    float* __restrict__ up_out, int32_t* __restrict__ index_out, int64_t cap,
+                                                    int32_t* __restrict__ counts) {
+  const int v = blockIdx.y;
+  const int N = max(min(totals[v], P), 0);          // (P <= cap: checked by the host)
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[v] = N;
+  const int i = blockIdx.x * MB + threadIdx.x;
+  if (i >= N) return;
+  const size_t from = (size_t)v * P + i, to = (size_t)v * (size_t)cap + i;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    xyz_out[3 * to + k] = xyz[3 * from + k];
+    up_out[3 * to + k] = g_col[3 * from + k];
+  }
+  if (index_out) index_out[to] = index[from];
 }
 
 }  // namespace cbatch

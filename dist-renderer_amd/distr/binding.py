@@ -50,6 +50,9 @@ TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset',
 LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list']
 # the render backward's gradient-sample list, written out (include/distr_render_train.h, included by distr.h): weight gradients through render
 RENDER_TRAIN_EXPORTS = ['distr_render_max_samples', 'distr_render_samples_export_batch']
+# the colour stage's decoder list, written out (include/distr_color_train.h, included by distr.h): weight gradients through the colour render
+COLOR_TRAIN_EXPORTS = ['distr_color_stage_samples_export_batch', 'distr_color_loss_workspace_bytes', 'distr_color_loss_forward_batch',
+                       'distr_color_loss_backward_batch']
 MAX_SEGMENTS = 64                                   # DISTR_MAX_VIEWS: segments of one distr_mlp_*_multi call
 SEG_TILE = 64                                       # points per tile of a segmented list; every segment owns whole tiles
 SAMPLES_MODES = {'surface': 0, 'freespace': 1}      # DISTR_SAMPLES_*
@@ -175,9 +178,10 @@ class RenderStats(_Sized):
 
 
 SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.hpp', 'distr_mlp.hpp', 'distr_mlp_split.hpp', 'distr_losses.hpp',
-           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp', 'distr_philox.hpp')
+           'distr_dense_asm.hpp', 'distr_mesh.hpp', 'distr_samples.hpp', 'distr_normal_grad.hpp', 'distr_color_batch.hpp', 'distr_train.hpp', 'distr_philox.hpp',
+           'distr_color_loss.hpp')
 HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h', 'distr_live_order.h',
-           'distr_render_train.h')                    # include/: the C ABI
+           'distr_render_train.h', 'distr_color_train.h')                    # include/: the C ABI
 INST_GROUPS = 10           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
@@ -448,6 +452,11 @@ def lib():
             L.distr_render_max_samples.argtypes = [C.POINTER(RenderCfg)]
             L.distr_render_max_samples.restype = i64
             L.distr_render_samples_export_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, vp, C.c_size_t, vp, C.c_size_t, fp, fp, vp, i64, vp, vp]
+            L.distr_color_stage_samples_export_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, vp, C.c_size_t, vp, C.c_size_t, fp, fp, vp, i64, vp, vp]
+            L.distr_color_loss_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            L.distr_color_loss_workspace_bytes.restype = C.c_size_t
+            L.distr_color_loss_forward_batch.argtypes = [vp, i32, i32, i32, fp, u8p, fp, u8p, i32, fp, fp, vp, vp, C.c_size_t, vp]
+            L.distr_color_loss_backward_batch.argtypes = [vp, i32, i32, i32, fp, u8p, fp, u8p, vp, fp, fp, fp, vp, C.c_size_t, vp]
             _lib = L
     return _lib
 

@@ -978,12 +978,13 @@ def train_plan_bytes(counts, out_dim=1):
     return need
 
 
-def render_train_chunks(counts, max_bytes):
+def render_train_chunks(counts, max_bytes, out_dim=1):
     """The plan of the train calls over the sample lists of B views: counts[v] rows per view -> a list of pieces, each a list of segments
-    (view, first row, rows). Every piece fits max_bytes (train_plan_bytes of its segments' rows) and has at most 64 segments; a view's
-    list is cut only at multiples of 64 rows from its start (whole tiles of the train path: a cut moves no row to another tile); views
-    without rows get no segment; pieces and segments follow the view order. A function of the counts and the limit alone: the same
-    inputs give the same plan, and so the same bytes. ValueError when not even 64 rows fit the limit."""
+    (view, first row, rows). Every piece fits max_bytes (train_plan_bytes of its segments' rows, for a net of out_dim outputs: 1 the SDF
+    decoder, 3 the colour decoder) and has at most 64 segments; a view's list is cut only at multiples of 64 rows from its start (whole
+    tiles of the train path: a cut moves no row to another tile); views without rows get no segment; pieces and segments follow the
+    view order. A function of the counts, the limit and out_dim alone: the same inputs give the same plan, and so the same bytes.
+    ValueError when not even 64 rows fit the limit."""
     counts = [int(c) for c in counts]
     if min(counts + [0]) < 0:
         raise ValueError('counts must be >= 0, got %r' % (counts,))
@@ -994,7 +995,7 @@ def render_train_chunks(counts, max_bytes):
         while at < c:
             have = [n for _, _, n in cur]
             left = c - at
-            fits = lambda n: train_plan_bytes(have + [n]) <= max_bytes
+            fits = lambda n: train_plan_bytes(have + [n], out_dim) <= max_bytes
             if len(cur) < binding.MAX_SEGMENTS and fits(min(left, TRAIN_ROW_TILE)):
                 if fits(left):
                     n = left
@@ -1011,7 +1012,7 @@ def render_train_chunks(counts, max_bytes):
                 cur = []
             else:
                 raise ValueError('render_train_chunks: %d bytes do not hold one tile of 64 samples (%d bytes)'
-                                 % (max_bytes, train_plan_bytes([TRAIN_ROW_TILE])))
+                                 % (max_bytes, train_plan_bytes([TRAIN_ROW_TILE], out_dim)))
     if cur:
         pieces.append(cur)
     return pieces
@@ -1418,16 +1419,80 @@ def color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mas
     return rgb, saved
 
 
+def color_stage_samples(engine, cfg, saved, ws_b):
+    """distr_color_stage_samples_export_batch on `saved` (color_stage_forward's second value: it holds the forward workspace) and the
+    backward workspace `ws_b` as distr_color_stage_backward_batch of the same views left it, having been given a g_latent_cat (tests and
+    tools; color_stage_weight_grads): -> (xyz (B, P, 3), up (B, P, 3), index (B, P) int32, counts_dev (B,) int32 on the device). View
+    v's list is its first counts_dev[v] rows: the surface points of its valid pixels in row-major order, the upstream g_rgb * s that
+    reached the decoder there, and the pixels; the rows behind them are not written (uninitialised memory)."""
+    dev, B, P = engine.device, saved['B'], saved['P']
+    xyz = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    up = torch.empty(B, P, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(B, P, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    p = binding.ptr
+    engine.ctx.check(engine.ctx.L.distr_color_stage_samples_export_batch(
+        engine.ctx.h, C.byref(cfg), B, p(saved['ws']), saved['ws'].numel(), p(ws_b), ws_b.numel(), p(xyz), p(up), p(index), P, p(counts),
+        engine.ctx.stream()))
+    return xyz, up, index, counts
+
+
+def color_stage_weight_grads(engine, cfg, saved, ws_b, weights, max_bytes=None, want_latent=False):
+    """Weight gradients of the colour decoder from one colour-stage backward: dL/dW_l, dL/db_l = sum over the valid pixels of every view
+    of (g_rgb * s) . d rgb / d(W_l, b_l). saved / ws_b: see color_stage_samples; weights: W0..W8, b0..b8 of the
+    colour decoder the engine was packed from. Exports the list, READS THE B COUNTS ON THE HOST (one sync: such a backward cannot be
+    captured into a graph), cuts the views' rows into train calls (render_train_chunks with out_dim = 3 under DISTR_TRAIN_MAX_BYTES or
+    max_bytes), runs train_forward / train_backward on the net color_train_net(weights) per piece, the code rows [shape | colour] being
+    the stage's own, and adds the pieces' gradients in piece order. -> ([g_W0..g_W8, g_b0..g_b8], g_latent_cat (B, 256 + cs): the
+    layer-wise code gradient of every view, a cross-check of the fused one, which is the one autograd returns; None without
+    want_latent)."""
+    _eighteen(weights)
+    dev, B = engine.device, saved['B']
+    weights = [_f32c(w, dev) for w in weights]
+    net = color_train_net(weights)
+    if net[0] != engine.latent_size:
+        raise ValueError('the weights describe a colour decoder of code length %d, the engine holds one of %d' % (net[0], engine.latent_size))
+    xyz, up, _, counts_dev = color_stage_samples(engine, cfg, saved, ws_b)
+    counts = [int(c) for c in counts_dev.cpu().tolist()]
+    lat = saved['lat']
+    total = None
+    g_lat = torch.zeros(B, engine.latent_size, dtype=torch.float32, device=dev) if want_latent else None
+    for piece in render_train_chunks(counts, train_max_bytes() if max_bytes is None else max_bytes, out_dim=net[2]):
+        pts = torch.cat([xyz[v, a:a + n] for v, a, n in piece])
+        u = torch.cat([up[v, a:a + n] for v, a, n in piece])
+        seg_codes = lat if lat.shape[0] == 1 else lat[[v for v, _, _ in piece]]
+        _, sv = train_forward(weights, seg_codes, pts, [n for _, _, n in piece], net=net, caller='color_stage_weight_grads')
+        grads, rows = train_backward(sv, u)
+        del sv
+        total = _add_in_order(total, grads)
+        if want_latent:
+            for (v, _, _), row in zip(piece, rows):
+                g_lat[v] += row
+    return (total if total is not None else [torch.zeros_like(w) for w in weights]), g_lat
+
+
 class ColorStageFunction(torch.autograd.Function):
     """The colour stage of B rendered views as ONE node: (color_codes (1, cs) / (B, cs), shape_codes (1, 256) / (B, 256), R (B,3,3),
     T (B,3), normal (B,H,W,3) or None) + observations (zdepth, mask, lights, energies) -> rgb (B,H,W,3). backward =
     distr_color_stage_backward_batch: gradients to both codes (summed over the views of a shared code), the cameras and -- with lights --
-    the normal image. detach_color: the colours are constants (render(no_grad=True)); only the shading terms carry gradient."""
+    the normal image. detach_color: the colours are constants (render(no_grad=True)); only the shading terms carry gradient.
+    `weights` (optional, trailing): W0..W8, b0..b8 of the colour decoder the engine was packed from
+    (decoder_pack.effective_weights_torch_color) -- the backward then also returns their eighteen gradients (color_stage_weight_grads,
+    DESIGN.md section 8j: ONE HOST SYNC per backward, so such a backward cannot be captured into a graph). The decoder backward then
+    runs whether or not a code requires grad (it writes the upstream the list carries). The gradients of codes, cameras and the normal
+    image are those of the fused backward; without weights every byte is what it was before the option existed."""
 
     @staticmethod
-    def forward(ctx, color_codes, shape_codes, R, T, normal, engine, cfg, zdepth, mask, lights, energies, detach_color):
+    def forward(ctx, color_codes, shape_codes, R, T, normal, engine, cfg, zdepth, mask, lights, energies, detach_color, *weights):
+        if weights:
+            _eighteen(weights)
+            if detach_color:          # (the backward would export an upstream that was never written)
+                raise ValueError('detach_color makes the colours constants: no gradient reaches the colour decoder, pass no weights')
         rgb, saved = color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal, lights, energies)
         ctx.engine, ctx.cfg, ctx.saved, ctx.detach_color = engine, cfg, saved, bool(detach_color)
+        ctx.nweights = len(weights)
+        if weights:
+            ctx.save_for_backward(*weights)
         ctx.generation = engine.generation
         ctx.codes = (color_codes.detach(), shape_codes.detach())
         ctx.shapes = (R.shape, T.shape, None if normal is None else normal.shape)
@@ -1444,7 +1509,7 @@ class ColorStageFunction(torch.autograd.Function):
         loc, en, st = sv['lights']
         need_c, need_s, need_R, need_T, need_n = ctx.needs_input_grad[:5]
         gs = _f32c(g, dev).reshape(-1)
-        g_lat = torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev) if (need_c or need_s) and not ctx.detach_color else None
+        g_lat = torch.empty(B, engine.latent_size, dtype=torch.float32, device=dev) if (need_c or need_s or ctx.nweights) and not ctx.detach_color else None
         g_R = torch.empty(B, 9, dtype=torch.float32, device=dev) if need_R else None
         g_T = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_T else None
         g_n = torch.empty(B, cfg.H, cfg.W, 3, dtype=torch.float32, device=dev) if need_n and st is not None else None
@@ -1452,23 +1517,94 @@ class ColorStageFunction(torch.autograd.Function):
         engine.ctx.check(L.distr_color_stage_backward_batch(
             engine.ctx.h, C.byref(cfg), B, p(Rc), p(Tc), p(z), p(n), p(sv['lat']), sv['stride'], None if st is None else C.byref(st), p(sv['ws']),
             sv['ws'].numel(), p(gs), p(g_lat), p(g_R), p(g_T), p(g_n), p(ws_b), ws_b.numel(), engine.ctx.stream()))
+        g_weights = ()
+        if ctx.nweights:
+            weights = ctx.saved_tensors
+            grads, _ = color_stage_weight_grads(engine, cfg, sv, ws_b, weights)
+            g_weights = tuple(g.reshape(w.shape).to(device=w.device, dtype=w.dtype) for g, w in zip(grads, weights))
         g_c, g_s = _split_code_grad(g_lat, *ctx.codes) if g_lat is not None else (None, None)
         rs, ts, ns = ctx.shapes
         cam = [None if t is None else t.reshape(sh).to(device=d, dtype=dt) for t, sh, (d, dt) in zip((g_R, g_T), (rs, ts), ctx.in_meta[:2])]
         g_n = None if g_n is None else g_n.reshape(ns).to(device=ctx.in_meta[2][0], dtype=ctx.in_meta[2][1])
-        return ((g_c if need_c else None), (g_s if need_s else None), cam[0], cam[1], g_n) + (None,) * 7
+        return ((g_c if need_c else None), (g_s if need_s else None), cam[0], cam[1], g_n) + (None,) * 7 + g_weights
 
 
-def color_stage_call(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal=None, lights=None, energies=None, detach_color=False):
+def color_stage_call(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal=None, lights=None, energies=None, detach_color=False,
+                     weights=None):
     """The colour images of B rendered views (color_stage_forward), on the tape unless nothing requires grad. detach_color: see
-    ColorStageFunction."""
-    ins = (R, T, normal) if detach_color else (color_codes, shape_codes, R, T, normal)
+    ColorStageFunction. weights: None, or W0..W8, b0..b8 of the engine's colour decoder on the autograd graph
+    (decoder_pack.effective_weights_torch_color): the backward also returns their gradients (one host sync per backward, see
+    ColorStageFunction); they are not taken together with detach_color."""
+    weights = list(weights) if weights is not None else []
+    if weights:
+        _eighteen(weights)
+        if cfg.rows != 0:
+            raise NotImplementedError('color_decoder_grad: row bands are not implemented (render the whole image)')
+    ins = (R, T, normal) if detach_color else (color_codes, shape_codes, R, T, normal) + tuple(weights)
     if lights is None and detach_color:
         ins = ()
     if torch.is_grad_enabled() and any(getattr(t, 'requires_grad', False) for t in ins):
         return ColorStageFunction.apply(color_codes, shape_codes, R, T, normal if lights is not None else None, engine, cfg, zdepth, mask, lights, energies,
-                                        detach_color)
+                                        detach_color, *weights)
     return color_stage_forward(engine, cfg, color_codes, shape_codes, R, T, zdepth, mask, normal, lights, energies)[0]
+
+
+class ColorLossFunction(torch.autograd.Function):
+    """The photometric loss of B colour images as ONE node (distr_color_loss_forward_batch / _backward_batch):
+    rgb (B, H, W, 3) + observations (mask (B, H, W), gt (B, H, W, 3), gt_mask (B, H, W)) -> (l1 (B,), ssim (B,) -- empty without
+    want_ssim --, overlap (B,) int32): the masked L1 and the SSIM term of the reference's compute_loss_color(use_ssim=True), per view.
+    Gradient flows to rgb only. A view with an empty overlap has l1 = 0 and a zero L1 gradient; `overlap` shows it."""
+
+    @staticmethod
+    def forward(ctx, rgb, mask, gt, gt_mask, want_ssim):
+        dev = rgb.device
+        if dev.type != 'cuda':
+            raise RuntimeError('ColorLossFunction: tensors must be on the GPU (no CPU path in this build)')
+        c = _train_context(dev.index if dev.index is not None else torch.cuda.current_device())
+        r = _f32c(rgb, dev)
+        if r.dim() != 4 or r.shape[3] != 3 or not 1 <= r.shape[0] <= binding.MAX_VIEWS:
+            raise ValueError('color_output has shape %s; expected (B, H, W, 3) with 1 <= B <= %d' % (tuple(rgb.shape), binding.MAX_VIEWS))
+        B, H, W = r.shape[:3]
+        g, m, gm = _f32c(gt, dev), _u8c(mask, dev), _u8c(gt_mask, dev)
+        if g.shape != r.shape or m.shape != (B, H, W) or gm.shape != (B, H, W):
+            raise ValueError('expected color_gt %s and masks %s, got %s, %s and %s' % (tuple(r.shape), (B, H, W), tuple(gt.shape), tuple(mask.shape), tuple(gt_mask.shape)))
+        L, p = c.L, binding.ptr
+        need = L.distr_color_loss_workspace_bytes(H, W, B, 0)
+        if not need:
+            raise ValueError('colour loss: images of %d x %d pixels are refused (at most 2^24 pixels)' % (H, W))
+        l1 = torch.empty(B, dtype=torch.float32, device=dev)
+        ssim = torch.empty(B if want_ssim else 0, dtype=torch.float32, device=dev)
+        ov = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        c.check(L.distr_color_loss_forward_batch(c.h, H, W, B, p(r), p(m), p(g), p(gm), 1 if want_ssim else 0, p(l1), p(ssim) if want_ssim else None, p(ov),
+                                                 p(ws), ws.numel(), c.stream()))
+        ctx.c, ctx.dims, ctx.want_ssim, ctx.saved = c, (B, H, W), bool(want_ssim), (r, m, g, gm, ov)
+        ctx.in_meta = (rgb.shape, rgb.device, rgb.dtype)
+        ctx.mark_non_differentiable(ov)
+        return l1, ssim, ov
+
+    @staticmethod
+    def backward(ctx, g_l1, g_ssim, _g_ov):
+        c, (B, H, W) = ctx.c, ctx.dims
+        r, m, g, gm, ov = ctx.saved
+        dev = r.device
+        gl = _f32c(g_l1, dev).reshape(B)
+        gs = _f32c(g_ssim, dev).reshape(B) if ctx.want_ssim else None
+        g_rgb = torch.empty_like(r)
+        L, p = c.L, binding.ptr
+        ws = torch.empty(L.distr_color_loss_workspace_bytes(H, W, B, 1), dtype=torch.uint8, device=dev)
+        c.check(L.distr_color_loss_backward_batch(c.h, H, W, B, p(r), p(m), p(g), p(gm), p(ov), p(gl), p(gs), p(g_rgb), p(ws), ws.numel(), c.stream()))
+        shape, d, dt = ctx.in_meta
+        return g_rgb.reshape(shape).to(device=d, dtype=dt), None, None, None, None
+
+
+def color_loss_batch(rgb, mask, gt, gt_mask, want_ssim=False):
+    """ColorLossFunction on B views: -> (l1 (B,), ssim (B,) or None, overlap (B,) int32). gt is an observation: ValueError if it
+    requires grad."""
+    if getattr(gt, 'requires_grad', False):
+        raise ValueError('color_gt requires grad: the target is an observation here, no gradient reaches it (detach it)')
+    l1, ssim, ov = ColorLossFunction.apply(rgb, mask, gt, gt_mask, bool(want_ssim))
+    return l1, (ssim if want_ssim else None), ov
 
 
 def color_relight(engine, cfg, color, normal, zdepth, mask, R, T, lights, energies=None):

@@ -381,5 +381,7 @@ int distr_warp_loss_backward(distr_ctx* ctx, const distr_warp_cfg* cfg, const fl
 #include "distr_live_order.h"
 /* the render backward's gradient-sample list, written out: weight gradients through render on the layer-wise path */
 #include "distr_render_train.h"
+/* the colour stage's decoder list, written out: weight gradients of the colour decoder through the colour render */
+#include "distr_color_train.h"
 
 #endif /* DISTR_H_ */
