@@ -455,27 +455,52 @@ __device__ __forceinline__ uint32_t compact_npad(uint32_t nlive) {
   return npad < 32u ? 32u : npad;
 }
 
-// Before the layer's first barrier: the ReLU bits of this wave's rows (KEEP: into mask[], exactly as writeback() forms them), OR-ed
-// over the tile's 64 rays, published as the wave's words of C.bits.
+// (m << 1) | (v > 0) for a ReLU value v >= 0, as a negation and one v_alignbit_b32: -v has its sign bit set exactly when v > 0.
+// (min(v, 1) << n, left to the compiler, becomes a compare into vcc and a select of the constant 1 << n: two instructions with wait states
+// between them, and the constants in vector registers.)
+__device__ __forceinline__ uint32_t push_nonzero_bit(uint32_t m, int32_t v) {
+  return __builtin_amdgcn_alignbit(m, 0u - (uint32_t)v, 31);
+}
+
+// Row blocks of a wave whose ReLU values stay in vector registers from compact_publish to compact_store (one pass over their accumulators);
+// the values of a wave's other blocks are formed from the accumulators a second time behind the barrier. The held values take the place of
+// the k-loop's operand registers, which are free at the boundary. Three blocks (96 registers) is what every kernel takes without scratch or
+// a larger register count; with all four the k_step variants spill (profiles/compact_writeback.md: the build figures per count).
+constexpr int COMPACT_HELD_BLOCKS = 3;
+template <int NOB>
+struct HeldRelu {
+  static constexpr int N = NOB < COMPACT_HELD_BLOCKS ? NOB : COMPACT_HELD_BLOCKS;
+  int32_t v[N ? N : 1][2][16];
+};
+
+// Before the layer's first barrier: the integer ReLU of this wave's rows (the held blocks' into hv), their bits (KEEP: into mask[], the bits
+// writeback() forms) OR-ed over the tile's 64 rays, published as the wave's words of C.bits.
 template <int NOB, bool KEEP>
-__device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&acc)[NOB][2], int wave, int lane, uint32_t (&mask)[4]) {
+__device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&acc)[NOB][2], HeldRelu<NOB>& hv, int wave, int lane, uint32_t (&mask)[4]) {
   uint32_t lw[4] = {0u, 0u, 0u, 0u};
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob) {
     uint32_t m = 0u;
+    int32_t rv[2][16];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        rv[rb][r] = max(__float_as_int(acc[ob][rb][r]), 0);
+        if (ob < HeldRelu<NOB>::N) hv.v[ob][rb][r] = rv[rb][r];
+      }
+    }
+    // bits from the last element down, so that element e ends at bit e
     if (KEEP) {
 #pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) m |= min((uint32_t)max(__float_as_int(acc[ob][rb][r]), 0), 1u) << (rb * 16 + r);
-      }
+      for (int e = 31; e >= 0; --e) m = push_nonzero_bit(m, rv[e >> 4][e & 15]);
       asm volatile("" : "+v"(m));
       mask[ob] = m;
       lw[ob] = (m | (m >> 16)) & 0xffffu;
     } else {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) m |= min((uint32_t)max(max(__float_as_int(acc[ob][0][r]), __float_as_int(acc[ob][1][r])), 0), 1u) << r;
+      for (int r = 15; r >= 0; --r) m = push_nonzero_bit(m, rv[0][r] | rv[1][r]);   // (both >= 0: the OR is zero iff both are)
       asm volatile("" : "+v"(m));
       lw[ob] = m;
     }
@@ -486,8 +511,11 @@ __device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&ac
 
 // Between the layer's two barriers: positions from the published bits, the live rows to X[pos], klist, the zero rows of the padding.
 // XYZ (lin3): the three xyz rows follow the live rows as features 253..255 (lin4's xyz columns). Returns the padded row count.
+// hv: the ReLU values compact_publish kept. The rows' offsets are fetched from postab four quads at a time, ahead of the stores that use them
+// (a store to X may alias the table as far as the compiler knows, so a fetch placed behind a store waits for its own round trip).
 template <int NOB, bool XYZ>
-__device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const float* xyz, const f32x16 (&acc)[NOB][2], int wave, int lane) {
+__device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const float* xyz, const f32x16 (&acc)[NOB][2], const HeldRelu<NOB>& hv, int wave,
+                                                  int lane) {
   constexpr int RW = 32 * NOB;             // rows of a wave
   const int tid = threadIdx.x;
   const int h = lane >> 5, j = lane & 31;
@@ -503,20 +531,34 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
     if (live) C.klist[pos] = (uint16_t)f;
   }
   __builtin_amdgcn_sched_barrier(0);
-  char* xl = reinterpret_cast<char*>(X) + 4 * j;
+  // this lane's column of X as one register (opaque: a known base of X is otherwise added behind the row's offset, a second add per row)
+  uint32_t xl = lds_off(X) + 4u * (uint32_t)j;
+  asm volatile("" : "+v"(xl));
+  using lds_float = __attribute__((address_space(3))) float;
+  // quads (of four rows): 4 * NOB. Four are fetched at a time, the next four two quads ahead of their use -- behind the stores of two
+  // quads, whose 16 values no longer occupy registers: only the first fetch is waited for
+  constexpr int NQ = 4 * NOB, POS_BATCH = 4, POS_AHEAD = 2;
+  uint4 pt[NQ];
+  auto fetch = [&](int k0) {
 #pragma unroll
-  for (int ob = 0; ob < NOB; ++ob) {
+    for (int k = k0; k < k0 + POS_BATCH; ++k) pt[k] = *reinterpret_cast<const uint4*>(&C.postab[wave * RW + 32 * (k >> 2) + 8 * (k & 3) + 4 * h]);
+  };
+  fetch(0);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint4 pt = *reinterpret_cast<const uint4*>(&C.postab[wave * RW + 32 * ob + 8 * q + 4 * h]);
-      const uint32_t po[4] = {pt.x, pt.y, pt.z, pt.w};
+  for (int k = 0; k < NQ; ++k) {
+    if (k % POS_BATCH == POS_BATCH - POS_AHEAD && k + POS_AHEAD < NQ) fetch(k + POS_AHEAD);
+    const int ob = k >> 2, q = k & 3;
+    const uint32_t po[4] = {pt[k].x, pt[k].y, pt[k].z, pt[k].w};
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float* dst = reinterpret_cast<float*>(xl + po[i]);
+    for (int i = 0; i < 4; ++i) {
+      lds_float* dst = (lds_float*)(xl + po[i]);
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
+      for (int rb = 0; rb < 2; ++rb) {
+        if (ob < HeldRelu<NOB>::N) {
+          dst[32 * rb] = __int_as_float(hv.v[ob][rb][4 * q + i]);
+        } else {
           int bits = __float_as_int(acc[ob][rb][4 * q + i]);
-          asm volatile("" : "+v"(bits));      // opaque: the ReLU values formed for the live bits must not stay in VGPRs across the barrier
+          asm volatile("" : "+v"(bits));      // opaque: this block's ReLU values, formed for the live bits, must not stay in VGPRs across the barrier
           dst[32 * rb] = __int_as_float(max(bits, 0));
         }
       }
@@ -545,9 +587,10 @@ template <int NOB, bool KEEP, bool XYZ, class SM>
 __device__ __forceinline__ uint32_t writeback_compact(SM& S, const f32x16 (&acc)[NOB][2], int wave, int lane, uint32_t (&mask)[4]) {
   static_assert(sizeof(CompactLds) <= sizeof(S.part) + sizeof(S.aux), "CompactLds lives in S.part .. S.aux");
   CompactLds& C = *reinterpret_cast<CompactLds*>(S.part);
-  compact_publish<NOB, KEEP>(C, acc, wave, lane, mask);
+  HeldRelu<NOB> hv;
+  compact_publish<NOB, KEEP>(C, acc, hv, wave, lane, mask);
   __syncthreads();
-  const uint32_t npad = compact_store<NOB, XYZ>(C, S.X, S.xyz, acc, wave, lane);
+  const uint32_t npad = compact_store<NOB, XYZ>(C, S.X, S.xyz, acc, hv, wave, lane);
   __syncthreads();
   return npad;
 }
