@@ -43,6 +43,7 @@ struct distr_ctx {
   bool profiling = false;
   int hybrid_threshold = 8192;  // t32: largest remainder of a march step (rays) that runs on 32-ray tiles (fine_split)
   int tail16_threshold = 4096;  // t16: ... and on 16-ray tiles (16x16x4 MFMA)
+  bool compact32 = true;        // DISTR_COMPACT32=0: the 32-ray role of the exact-f32 step kernel keeps the dense loop (a time knob; only effective with dense_compact)
   bool dense_compact = true;    // DISTR_DENSE_COMPACT=0: the exact-f32 64-ray tile (march and saved-mask backward) multiplies every hidden unit, live for the tile or not (a time knob)
   bool live_order = true;       // DISTR_LIVE_ORDER=0: every full-resolution step appends its survivors atomically, in completion order (no k_live_pack; a time knob)
   bool ray_blocks = true;       // DISTR_RAY_BLOCKS=0: the setup kernels enumerate pixels in strips of 256 instead of 16 x 16 blocks (a time knob)
@@ -654,14 +655,15 @@ int distr_create_abi(distr_ctx** out, int hip_device, uint32_t abi_version) {
   if (const char* e = getenv("DISTR_XCHG_TS")) ctx->xchg_ts = atoi(e) != 0;
   if (const char* e = getenv("DISTR_CLUSTER_TEST_ABORT")) ctx->cluster_test_abort = atoi(e);     // 1: abort at assembly; 2: member 0 drops out behind its last slice
   if (const char* e = getenv("DISTR_SAVE_MASKS")) ctx->save_masks = atoi(e) != 0;
-  if (const char* e = getenv("DISTR_DENSE_COMPACT")) {
-    if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
-      ctx->err = std::string("DISTR_DENSE_COMPACT must be 0 or 1 (got '") + e + "')";
-      *out = ctx;
-      return DISTR_ERR_INVALID_ARG;
+  for (const char* name : {"DISTR_DENSE_COMPACT", "DISTR_COMPACT32"})
+    if (const char* e = getenv(name)) {
+      if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
+        ctx->err = std::string(name) + " must be 0 or 1 (got '" + e + "')";
+        *out = ctx;
+        return DISTR_ERR_INVALID_ARG;
+      }
+      (strcmp(name, "DISTR_COMPACT32") == 0 ? ctx->compact32 : ctx->dense_compact) = e[0] == '1';
     }
-    ctx->dense_compact = e[0] == '1';
-  }
   for (const char* name : {"DISTR_LIVE_ORDER", "DISTR_RAY_BLOCKS"})
     if (const char* e = getenv(name)) {
       if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
@@ -1064,10 +1066,13 @@ inline bool wide_decoder(const distr_ctx* ctx) { return ctx->D.nlat < LAT; }
 // runs and the context packed the k-major weights for it (D.Wk); every other tile keeps the dense loop.
 inline bool compact_tile(const distr_ctx* ctx, int rb, int arith) { return ctx->D.Wk != nullptr && rb == 2 && arith == 0; }
 
+// k_step's compaction level: 1 = its 64-ray role walks live units, 2 = its 32-ray role too (DISTR_COMPACT32, on top of DISTR_DENSE_COMPACT)
+inline int step_compact_level(const distr_ctx* ctx, int arith) { return compact_tile(ctx, 2, arith) ? (ctx->compact32 ? 2 : 1) : 0; }
+
 int launch_step(distr_ctx* ctx, const char* what, bool keep, int arith, unsigned grid, hipStream_t s, const MarchArgs& A, const StepGrid& G) {
-  const bool compact = compact_tile(ctx, 2, arith);
+  const int compact = step_compact_level(ctx, arith);
   DISTR_ALL_GROUPS(DISTR_TRY_STEP, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT, DISTR_NO_VARIANT)
-  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_step<%d, %d, %d> (distr_inst.hpp)", (int)keep, arith, (int)compact);
+  return fail(ctx, DISTR_ERR_UNSUPPORTED, "no variant k_step<%d, %d, %d> (distr_inst.hpp)", (int)keep, arith, compact);
 }
 
 int launch_tail(distr_ctx* ctx, const char* what, bool keep, unsigned grid, hipStream_t s, const MarchArgs& A) {
@@ -1648,6 +1653,38 @@ int distr_debug_mlp_layer(distr_ctx* ctx, const float* latent, const float* xyz,
   return DISTR_OK;
 }
 
+// the 32-point tile as k_step's 32-ray role runs it: compacted (level 2) on its own layout, else the dense loop on Smem<1>.
+// layer < 0: the stamped build (out = sdf[n], ts_out[tiles][40]); else the layer's activations by feature (out = [n][512])
+static int debug_tile32(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, int layer, float* out, long long* ts_out, void* ws,
+                        size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (!ctx->has_decoder) return fail(ctx, DISTR_ERR_NO_DECODER, "distr_set_decoder has not been called");
+  if (wide_decoder(ctx)) return fail(ctx, DISTR_ERR_UNSUPPORTED, "test aid built for the narrow tile layout (code length >= 256)");
+  if (n == 0) return fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument");      // (no empty list here: there is nothing to look at)
+  hipStream_t s = (hipStream_t)stream;
+  PointList pl = plain_list(n);
+  const bool timing = layer < 0;
+  const int rc = point_list_prologue(ctx, ctx->D, pl, latent, 0, n > 0 && xyz && out && (timing ? ts_out != nullptr : layer <= 7), ws, ws_bytes, false, s);
+  if (rc) return rc;
+  const unsigned tiles = (unsigned)((n + 31) / 32);
+  if (step_compact_level(ctx, 0) == 2) hipLaunchKernelGGL((k_debug_layer<1, true>), dim3(tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, timing ? 8 : layer, out, ctx->D, ts_out);
+  else hipLaunchKernelGGL((k_debug_layer<1>), dim3(tiles), dim3(NTHREADS), 0, s, xyz, n, (const float*)pl.c0c4, timing ? 8 : layer, out, ctx->D, ts_out);
+  LAUNCH_CHECK("k_debug_layer<32>");
+  return DISTR_OK;
+}
+
+int distr_debug_mlp_layer32(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, int layer, float* out, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (layer < 0) return ctx ? fail(ctx, DISTR_ERR_INVALID_ARG, "bad argument") : DISTR_ERR_INVALID_ARG;
+  return debug_tile32(ctx, latent, xyz, n, layer, out, nullptr, ws, ws_bytes, stream);
+}
+
+int distr_debug_tile_timing32(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float* sdf_out, long long* ts_out, void* ws,
+                              size_t ws_bytes, void* stream) {
+  return debug_tile32(ctx, latent, xyz, n, -1, sdf_out, ts_out, ws, ws_bytes, stream);
+}
+
 int distr_debug_tile_timing(distr_ctx* ctx, const float* latent, const float* xyz, int64_t n, float* sdf_out, long long* ts_out,
                             void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return DISTR_ERR_INVALID_ARG;
@@ -1784,6 +1821,23 @@ int distr_get_kstep_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const voi
     for (int st = 0; st < V.lv[l].steps; ++st) put(C->kstep_coarse[l][st & 15]);
   for (int t = 0; t < V.fine_steps; ++t) put(C->kstep_fine[t]);
   *n = k;
+  return DISTR_OK;
+}
+
+int distr_get_kstep32_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws, int64_t* out, int32_t cap, int32_t* n, void* stream) {
+  if (!ctx || !ws || !out || !n) return fail(ctx, DISTR_ERR_INVALID_ARG, "null argument");
+  EntryGuard guard_(ctx);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  View V;
+  const Consts* C;
+  if ((rc = read_consts(ctx, cfg, ws, (hipStream_t)stream, V, &C))) return rc;
+  for (int t = 0; t < V.fine_steps && t < cap; ++t) {
+    const unsigned long long word = C->kstep_fine32[t];
+    const int64_t tiles = (int64_t)(word >> KSTEP_BITS);
+    out[3 * t] = tiles; out[3 * t + 1] = (int64_t)(word & ((1ull << KSTEP_BITS) - 1)); out[3 * t + 2] = tiles * KSTEP_DENSE;
+  }
+  *n = V.fine_steps;
   return DISTR_OK;
 }
 

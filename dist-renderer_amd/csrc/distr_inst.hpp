@@ -16,11 +16,12 @@ namespace distr {
 //   STEP(KEEP, ARITH, COMPACT)  TAIL(KEEP)  MARCH(MODE, RB, KEEP, ARITH, WIDE, COMPACT)  MARCH16(MODE, KEEP)  BWD(MODE, RB, ARITH, WIDE, COMPACT)
 // KEEP = save the ReLU masks, RB = 32-ray blocks of a tile, ARITH = DISTR_ARITH_* (0 f32, 1 bf16x6, 2 f16x3), WIDE = the layout for
 // code lengths below 256, COMPACT = the 64-ray / 64-sample tile walks the live hidden units of a tile only (exact f32, narrow layout;
-// distr_mlp.hpp; the backward: the tile over saved masks, BWD_SAVED, whose live sets are known before its chain starts).
+// distr_mlp.hpp; the backward: the tile over saved masks, BWD_SAVED, whose live sets are known before its chain starts). STEP's COMPACT is a
+// level: 0 none, 1 the 64-ray role, 2 the 64- and the 32-ray role.
 
 // the full-resolution step of the exact-f32 march (the headline kernel)
 #define DISTR_GROUP_1(STEP, TAIL, MARCH, MARCH16, BWD) \
-  STEP(true, 0, false) STEP(false, 0, false)
+  STEP(true, 0, 0) STEP(false, 0, 0)
 // the persistent tail launch
 #define DISTR_GROUP_2(STEP, TAIL, MARCH, MARCH16, BWD) \
   TAIL(true) TAIL(false)
@@ -32,7 +33,7 @@ namespace distr {
   MARCH16(MODE_EVAL, false) MARCH16(MODE_COARSE, true) MARCH16(MODE_COARSE, false)
 // the step kernel in the two opt-in arithmetics
 #define DISTR_GROUP_4(STEP, TAIL, MARCH, MARCH16, BWD) \
-  STEP(true, 1, false) STEP(false, 1, false) STEP(true, 2, false) STEP(false, 2, false)
+  STEP(true, 1, 0) STEP(false, 1, 0) STEP(true, 2, 0) STEP(false, 2, 0)
 // march tiles in the two opt-in arithmetics
 #define DISTR_GROUP_5(STEP, TAIL, MARCH, MARCH16, BWD) \
   MARCH(MODE_COARSE, 1, true, 1, false, false) MARCH(MODE_COARSE, 1, false, 1, false, false) MARCH(MODE_COARSE, 2, true, 1, false, false) MARCH(MODE_COARSE, 2, false, 1, false, false) \
@@ -50,9 +51,9 @@ namespace distr {
   MARCH(MODE_FINE, 2, true, 0, true, false) MARCH(MODE_FINE, 2, false, 0, true, false) \
   BWD(BWD_FULL, 2, 0, true, false) BWD(BWD_POINTGRAD, 2, 0, true, false) BWD(BWD_SAVED, 2, 0, true, false) BWD(BWD_SAVED, 1, 0, true, false)
 
-// the compacted 64-ray tile (DISTR_DENSE_COMPACT, the default): the step kernel ...
+// the compacted 64-ray tile (DISTR_DENSE_COMPACT, the default): the step kernel with a dense 32-ray role (level 1: DISTR_COMPACT32=0) ...
 #define DISTR_GROUP_8(STEP, TAIL, MARCH, MARCH16, BWD) \
-  STEP(true, 0, true) STEP(false, 0, true)
+  STEP(true, 0, 1) STEP(false, 0, 1)
 // ... and the 64-ray march tiles
 #define DISTR_GROUP_9(STEP, TAIL, MARCH, MARCH16, BWD) \
   MARCH(MODE_EVAL, 2, false, 0, false, true) MARCH(MODE_COARSE, 2, true, 0, false, true) MARCH(MODE_COARSE, 2, false, 0, false, true) \
@@ -62,11 +63,16 @@ namespace distr {
 #define DISTR_GROUP_10(STEP, TAIL, MARCH, MARCH16, BWD) \
   BWD(BWD_SAVED, 2, 0, false, true)
 
-constexpr int DISTR_NUM_INST_GROUPS = 10;
+// ... and the step kernel whose 32-ray role is compacted too (level 2: DISTR_COMPACT32, the default)
+#define DISTR_GROUP_11(STEP, TAIL, MARCH, MARCH16, BWD) \
+  STEP(true, 0, 2) STEP(false, 0, 2)
+
+constexpr int DISTR_NUM_INST_GROUPS = 11;
 
 #define DISTR_ALL_GROUPS(...) \
   DISTR_GROUP_1(__VA_ARGS__) DISTR_GROUP_2(__VA_ARGS__) DISTR_GROUP_3(__VA_ARGS__) DISTR_GROUP_4(__VA_ARGS__) DISTR_GROUP_5(__VA_ARGS__) \
-  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__) DISTR_GROUP_8(__VA_ARGS__) DISTR_GROUP_9(__VA_ARGS__) DISTR_GROUP_10(__VA_ARGS__)
+  DISTR_GROUP_6(__VA_ARGS__) DISTR_GROUP_7(__VA_ARGS__) DISTR_GROUP_8(__VA_ARGS__) DISTR_GROUP_9(__VA_ARGS__) DISTR_GROUP_10(__VA_ARGS__) \
+  DISTR_GROUP_11(__VA_ARGS__)
 #define DISTR_NO_VARIANT(...)      // for the families a use of the lists does not ask for
 
 // in a group's translation unit only that group is instantiated; the launching unit declares all of them extern

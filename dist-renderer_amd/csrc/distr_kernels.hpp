@@ -57,6 +57,9 @@ struct Consts {
   // kstep_coarse[l][t]: step t of pyramid level l. Statistics only (distr_get_kstep_stats); the dense count is tiles * KSTEP_DENSE.
   alignas(8) unsigned long long kstep_fine[MAX_STEPS + 2];
   unsigned long long kstep_coarse[MAX_LEVELS][16];
+  // the same word for the 32-ray tiles of k_step's 32-ray role at full-resolution step t (exact f32): compacted tiles add what they executed,
+  // dense ones KSTEP_DENSE. Kept apart from kstep_fine, which speaks of 64-ray tiles only.
+  unsigned long long kstep_fine32[MAX_STEPS + 2];
 };
 constexpr int KSTEP_BITS = 40;
 constexpr int HINT_ORDER_OFF = 16;   // k_finalize's hint words of one render configuration: [0] tail launch, [HINT_ORDER_OFF] end of the ordered steps
@@ -410,7 +413,7 @@ DISTR_GLOBAL void __launch_bounds__(256) k_prep(View V0, DecoderDev D, const flo
   if (blockIdx.x == 0) {
     const int t = threadIdx.x;
     for (int k = t; k < D.nlat; k += 256) C->latent[k] = latent[k];
-    for (int i = t; i < MAX_STEPS + 2; i += 256) { C->cnt_live[i] = 0; C->cnt_sticky[i] = 0; C->tail_sync[2 * i] = 0; C->tail_sync[2 * i + 1] = 0; C->kstep_fine[i] = 0ull; }
+    for (int i = t; i < MAX_STEPS + 2; i += 256) { C->cnt_live[i] = 0; C->cnt_sticky[i] = 0; C->tail_sync[2 * i] = 0; C->tail_sync[2 * i + 1] = 0; C->kstep_fine[i] = 0ull; C->kstep_fine32[i] = 0ull; }
     if (t < MAX_LEVELS * 16) C->kstep_coarse[t >> 4][t & 15] = 0ull;
     for (int i = t; i < PSTRIDE; i += 256) C->red[i] = 0.f;
     if (t < 12) C->cam_acc[t] = 0.f;
@@ -791,9 +794,10 @@ __device__ __forceinline__ void slot_append(bool flag, int32_t id, const View& V
 }
 
 // one compacted 64-ray tile of level `lvl`, step `step` executed `ksteps` k-steps (Consts::kstep_fine / kstep_coarse); one lane, one atomic
-__device__ __forceinline__ void kstep_count(Consts* C, int lvl, int step, uint32_t ksteps) {
+// (tile32: a 32-ray tile of a full-resolution step -- kstep_fine32)
+__device__ __forceinline__ void kstep_count(Consts* C, int lvl, int step, uint32_t ksteps, bool tile32 = false) {
   if (threadIdx.x != 0) return;
-  unsigned long long* p = (lvl == 0) ? &C->kstep_fine[step] : &C->kstep_coarse[lvl][step & 15];
+  unsigned long long* p = tile32 ? &C->kstep_fine32[step] : (lvl == 0) ? &C->kstep_fine[step] : &C->kstep_coarse[lvl][step & 15];
   atomicAdd(p, (1ull << KSTEP_BITS) | (unsigned long long)ksteps);
 }
 
@@ -889,11 +893,13 @@ __device__ __forceinline__ TopkPlace fine_commit(const View& V, const RayPre& st
 // Returns false when the tile lies beyond this role's range (nothing done).
 // ARITH = 0: exact f32 MFMA tile (distr_mlp.hpp); 1: six-product split-bf16, 2: three-product split-f16 -- the split tile
 // (distr_mlp_split.hpp) in the format SplitFmt<ARITH>   (distr_render_cfg.arith)
-template <int RB, int ARITH> struct TileSmem { using type = SmemSplit<SplitFmt<ARITH>, RB>; };
-template <int RB> struct TileSmem<RB, 0> { using type = Smem<RB>; };
+// (COMPACT: the compacted tile -- distr_mlp.hpp; the 32-ray one has a layout of its own)
+template <int RB, int ARITH, bool COMPACT = false> struct TileSmem { using type = SmemSplit<SplitFmt<ARITH>, RB>; };
+template <int RB, bool COMPACT> struct TileSmem<RB, 0, COMPACT> { using type = Smem<RB>; };
+template <> struct TileSmem<1, 0, true> { using type = SmemC32; };
 
 template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
-__device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev& D, typename TileSmem<RB, ARITH>::type& S, int tile, int ntile_grid,
+__device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev& D, typename TileSmem<RB, ARITH, COMPACT>::type& S, int tile, int ntile_grid,
                                            int which, int origin_tile) {
   constexpr int TILE = 32 * RB;
   const View& V0 = A.V;
@@ -983,7 +989,8 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
   if constexpr (ARITH == 0) {
     uint32_t ksteps = 0u;
     pre = mlp_forward<RB, KEEP, false, true, WIDE, COMPACT>(D, c0, c4, S, masks, 8, nullptr, COMPACT ? &ksteps : nullptr);
-    if constexpr (COMPACT && MODE != MODE_EVAL) { if (!origin) kstep_count(V.C, MODE == MODE_COARSE ? A.lvl : 0, A.step, ksteps); }
+    if constexpr (MODE == MODE_FINE && RB == 1) { if (!origin) kstep_count(V.C, 0, A.step, COMPACT ? ksteps : (uint32_t)KSTEP_DENSE, true); }
+    else if constexpr (COMPACT && MODE != MODE_EVAL) { if (!origin) kstep_count(V.C, MODE == MODE_COARSE ? A.lvl : 0, A.step, ksteps); }
   } else pre = split_forward<SplitFmt<ARITH>, RB, KEEP>(D, A.planes[ARITH - 1], c0, c4, S, masks);
 
   // epilogue: wave 0 (kept whole for the ballot), lane = ray of the tile; lanes >= TILE are invalid
@@ -1037,6 +1044,7 @@ __device__ __forceinline__ bool march_tile(const MarchArgs& A, const DecoderDev&
 template <int MODE, int RB, bool KEEP, int ARITH = 0, bool WIDE = false, bool COMPACT = false>
 __global__ void __launch_bounds__(256, (RB == 1 && ARITH == 0) ? 2 : 1) k_march(MarchArgs A, DecoderDev D) {
   static_assert(!WIDE || (RB == 2 && ARITH == 0), "the wide layout: 64-ray tiles, exact f32");
+  static_assert(!(COMPACT && RB == 1), "the compacted 32-ray tile is a role of k_step (its layout needs a whole CU's LDS share)");
   __shared__ typename TileSmem<RB, ARITH>::type S;
   (void)march_tile<MODE, RB, KEEP, ARITH, WIDE, COMPACT>(A, D, S, (int)blockIdx.x, (int)gridDim.x, A.which, A.origin_tile);
 }
@@ -1761,8 +1769,11 @@ __global__ void __launch_bounds__(256, 1) k_tail(MarchArgs A, DecoderDev D, Deco
 // Against three launches per step this saves two empty launches (4-5 us each) on almost every step.
 struct StepGrid { int32_t n64, n32, n16; };
 
-template <bool KEEP, int ARITH = 0, bool COMPACT = false>
+// COMPACT: 0 every tile multiplies every hidden unit, 1 the 64-ray role walks a tile's live units only, 2 the 32-ray role too (exact f32).
+template <bool KEEP, int ARITH = 0, int COMPACT = 0>
 __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, DecoderDev16 D16, StepGrid G) {
+  constexpr bool COMPACT64 = COMPACT >= 1, COMPACT32 = COMPACT >= 2;
+  static_assert(COMPACT >= 0 && COMPACT <= 2 && (COMPACT == 0 || ARITH == 0), "compaction levels of the exact-f32 step");
   __shared__ __attribute__((aligned(16))) unsigned char raw[(sizeof(Smem<2>) > sizeof(SmemSplit<FmtB6, 2>)) ? sizeof(Smem<2>) : sizeof(SmemSplit<FmtB6, 2>)];
   static_assert(sizeof(Smem<2>) >= sizeof(Smem<1>) && sizeof(Smem<2>) >= sizeof(Smem16CLX) && sizeof(SmemSplit<FmtB6, 2>) >= sizeof(SmemSplit<FmtB6, 1>), "role shared memory");
   // role order in the grid: 32-ray tiles, 16-ray / cluster tiles, 64-ray tiles. On a tail step the cluster tiles start
@@ -1771,12 +1782,12 @@ __global__ void __launch_bounds__(256, 1) k_step(MarchArgs A, DecoderDev D, Deco
   // ARITH = 1 (split-bf16): 64- and 32-ray roles only (G.n16 = 0, t16 = 0); the views' origin tiles close the 32-ray role.
   const int b = blockIdx.x;
   if (b < G.n32) {
-    (void)march_tile<MODE_FINE, 1, KEEP, ARITH>(A, D, *reinterpret_cast<typename TileSmem<1, ARITH>::type*>(raw), b, G.n32, 32, ARITH ? A.origin_tile : 0);
+    (void)march_tile<MODE_FINE, 1, KEEP, ARITH, false, COMPACT32>(A, D, *reinterpret_cast<typename TileSmem<1, ARITH, COMPACT32>::type*>(raw), b, G.n32, 32, ARITH ? A.origin_tile : 0);
   } else if (b < G.n32 + G.n16) {
     if constexpr (ARITH == 0) march_tile16<MODE_FINE, KEEP>(A, D, D16, *reinterpret_cast<Smem16CLX*>(raw), b - G.n32, A.origin_tile);
   } else {
     for (int t = b - G.n32 - G.n16;; t += G.n64) {
-      if (!march_tile<MODE_FINE, 2, KEEP, ARITH, false, COMPACT>(A, D, *reinterpret_cast<typename TileSmem<2, ARITH>::type*>(raw), t, 0x7fffffff, 64, 0)) break;
+      if (!march_tile<MODE_FINE, 2, KEEP, ARITH, false, COMPACT64>(A, D, *reinterpret_cast<typename TileSmem<2, ARITH>::type*>(raw), t, 0x7fffffff, 64, 0)) break;
       __syncthreads();       // the tile's last LDS reads (mask store) are done before the next tile's points are written
     }
   }
@@ -1918,11 +1929,12 @@ DISTR_GLOBAL void __launch_bounds__(256, 1) k_color_bwd(const float* __restrict_
 }
 
 // test/debug only: post-activation of layer `layer` for n points -> out[n][512] (see tests/test_gpu_parity.py)
+// (RB = 1, COMPACT: the compacted 32-ray tile on its own layout, one workgroup per CU like the role of k_step it stands for)
 template <int RB, bool COMPACT = false>
-__global__ void __launch_bounds__(256, (RB == 1) ? 2 : 1) k_debug_layer(const float* xyz, int64_t n, const float* c0c4, int layer,
-                                                                        float* out, DecoderDev D, long long* ts_out) {
+__global__ void __launch_bounds__(256, (RB == 1 && !COMPACT) ? 2 : 1) k_debug_layer(const float* xyz, int64_t n, const float* c0c4, int layer,
+                                                                                    float* out, DecoderDev D, long long* ts_out) {
   constexpr int TILE = 32 * RB;
-  __shared__ Smem<RB> S;
+  __shared__ typename TileSmem<RB, 0, COMPACT>::type S;
   const int tid = threadIdx.x;
   const int64_t base = (int64_t)blockIdx.x * TILE;
   if (tid < TILE) {
@@ -1933,7 +1945,8 @@ __global__ void __launch_bounds__(256, (RB == 1) ? 2 : 1) k_debug_layer(const fl
   __syncthreads();
   uint32_t masks[8][4];
   long long* ts = ts_out ? ts_out + (size_t)blockIdx.x * 40 : nullptr;
-  const float pre = mlp_forward<RB, false, true, false, false, COMPACT>(D, c0c4, c0c4 + HID, S, masks, layer, ts);
+  if constexpr (RB == 1 && COMPACT) { stage_bias<RB, false>(D, c0c4, c0c4 + HID, S); }     // (STAGED below: the role stages them at the tile's head)
+  const float pre = mlp_forward<RB, false, true, RB == 1 && COMPACT, false, COMPACT>(D, c0c4, c0c4 + HID, S, masks, layer, ts);
   if (ts_out) {   // timing mode: whole forward, no activation dump
     if (tid == 0) { ts[36] = (long long)__builtin_readcyclecounter(); ts[37] = (long long)wall_clock64(); }
     if (tid < TILE && base + tid < n) out[base + tid] = tanh_spec(pre);

@@ -111,9 +111,12 @@ struct alignas(16) Smem : SmemBias<RB> {
 
 // WIDE: the tile layout of decoders with a code length C < 256 -- lin3 has 509 - C > 253 rows, so lin3 (padded to 509 rows, xyz carried
 // in rows 509..511) and lin4 (K = 512) are full 512 x 512 layers like lin1 / lin2. Narrow (the default): lin3 256 rows, lin4 K = 256.
-template <int RB, bool WIDE = false>
-__device__ __forceinline__ void stage_bias(const DecoderDev& D, const float* __restrict__ c0, const float* __restrict__ c4, Smem<RB>& S) {
-  if constexpr (RB == 2) {
+// (SM: Smem<RB>, or a role's own layout with the same members -- SmemC32 below; a layout stages the start values iff it has the bias rows)
+template <class SM> constexpr bool has_bias_rows = std::is_base_of<SmemBias<2>, SM>::value;
+
+template <int RB, bool WIDE = false, class SM>
+__device__ __forceinline__ void stage_bias(const DecoderDev& D, const float* __restrict__ c0, const float* __restrict__ c4, SM& S) {
+  if constexpr (has_bias_rows<SM>) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int l = 0; l < 8; ++l) {
@@ -126,16 +129,16 @@ __device__ __forceinline__ void stage_bias(const DecoderDev& D, const float* __r
 }
 
 // start values of layer l for this tile: LDS copy (RB == 2, after stage_bias + barrier) or the global arrays
-template <int RB>
-__device__ __forceinline__ const float* layer_init(const DecoderDev& D, const float* c0, const float* c4, const Smem<RB>& S, int l) {
-  if constexpr (RB == 2) return S.bias + l * HID;
+template <int RB, class SM>
+__device__ __forceinline__ const float* layer_init(const DecoderDev& D, const float* c0, const float* c4, const SM& S, int l) {
+  if constexpr (has_bias_rows<SM>) return S.bias + l * HID;
   else return (l == 0) ? c0 : (l == 4) ? c4 : D.bias[l];
 }
 
 // Smem<2>::bias, or nullptr for the tile that has none
-template <int RB>
-__device__ __forceinline__ float* bias_base(Smem<RB>& S) {
-  if constexpr (RB == 2) return S.bias;
+template <class SM>
+__device__ __forceinline__ float* bias_base(SM& S) {
+  if constexpr (has_bias_rows<SM>) return S.bias;
   else return nullptr;
 }
 
@@ -381,13 +384,34 @@ __device__ __forceinline__ void static_for(F&& f);     // (defined with the clus
 // feature order, zero rows up to the next multiple of 16 (at least 32), and the feature index of every position in `klist`; the next
 // layer (dense_asm_compact_*) walks positions instead of features and gathers its weights from the k-major pack by klist.
 // The bookkeeping lives in S.part .. S.aux (4 KiB, idle during the layers; the dense loop's tuple scratch in the other mode).
+// The 32-ray tile (RB = 1) is compacted the same way over its 32 rays -- rows of 128 bytes, live bits OR-ed over one ray block -- in a
+// layout of its own (SmemC32), since Smem<1> has neither the bias rows the generated loop starts from nor room for the bookkeeping.
 struct CompactLds {
-  uint32_t postab[HID];   // byte offset from X of the row a unit is stored to: position * 256, or the trash row for a dead unit
+  uint32_t postab[HID];   // byte offset from X of the row a unit is stored to: position * TILE * 4, or the trash row for a dead unit
   uint16_t klist[HID];    // feature index of position p
   uint32_t bits[16];      // live bits of the layer being written back: word 4 * wave + ob, bit = row within the block (feature order)
   uint32_t pad_[4];
   float trash[64];        // where the (+0) rows of dead units go
 };
+
+// The compacted 32-ray tile's shared memory: Smem<1>'s members behind the eight bias rows, and the bookkeeping as a member (3.4 KiB do not
+// fit Smem<1>::part .. aux). 85.9 KiB: only a kernel whose workgroups own a CU can hold it -- k_step, inside the role buffer Smem<2> sizes.
+struct alignas(16) SmemC32 : SmemBias<2> {
+  static constexpr int TILE = 32;
+  float X[HID * TILE];
+  float xyz[4 * TILE];
+  float part[12 * TILE];
+  float aux[4 * TILE];
+  CompactLds compact;
+};
+static_assert(sizeof(SmemC32) <= sizeof(Smem<2>), "the compacted 32-ray tile lives in k_step's role buffer");
+
+// where a layout keeps the compacted tile's bookkeeping
+template <class SM>
+__device__ __forceinline__ CompactLds* compact_lds(SM& S) {
+  if constexpr (std::is_same<SM, SmemC32>::value) return &S.compact;
+  else return reinterpret_cast<CompactLds*>(S.part);
+}
 
 __device__ __forceinline__ uint32_t spread4(uint32_t x) {   // bit 4q + i -> bit 8q + i
   return (x & 0xfu) | ((x & 0xf0u) << 4) | ((x & 0xf00u) << 8) | ((x & 0xf000u) << 12);
@@ -466,41 +490,43 @@ __device__ __forceinline__ uint32_t push_nonzero_bit(uint32_t m, int32_t v) {
 // the values of a wave's other blocks are formed from the accumulators a second time behind the barrier. The held values take the place of
 // the k-loop's operand registers, which are free at the boundary. Three blocks (96 registers) is what every kernel takes without scratch or
 // a larger register count; with all four the k_step variants spill (profiles/compact_writeback.md: the build figures per count).
-constexpr int COMPACT_HELD_BLOCKS = 3;
-template <int NOB>
+// The 32-ray tile (RB = 1) has half the accumulators and holds all four blocks.
+constexpr int COMPACT_HELD_BLOCKS = 3, COMPACT_HELD_BLOCKS_32 = 4;
+template <int NOB, int RB = 2>
 struct HeldRelu {
-  static constexpr int N = NOB < COMPACT_HELD_BLOCKS ? NOB : COMPACT_HELD_BLOCKS;
-  int32_t v[N ? N : 1][2][16];
+  static constexpr int HELD = RB == 2 ? COMPACT_HELD_BLOCKS : COMPACT_HELD_BLOCKS_32;
+  static constexpr int N = NOB < HELD ? NOB : HELD;
+  int32_t v[N ? N : 1][RB][16];
 };
 
 // Before the layer's first barrier: the integer ReLU of this wave's rows (the held blocks' into hv), their bits (KEEP: into mask[], the bits
-// writeback() forms) OR-ed over the tile's 64 rays, published as the wave's words of C.bits.
-template <int NOB, bool KEEP>
-__device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&acc)[NOB][2], HeldRelu<NOB>& hv, int wave, int lane, uint32_t (&mask)[4]) {
+// writeback() forms) OR-ed over the tile's 32 * RB rays, published as the wave's words of C.bits. (RB = 1: a mask word uses its low 16 bits.)
+template <int NOB, bool KEEP, int RB>
+__device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&acc)[NOB][RB], HeldRelu<NOB, RB>& hv, int wave, int lane, uint32_t (&mask)[4]) {
   uint32_t lw[4] = {0u, 0u, 0u, 0u};
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int ob = 0; ob < NOB; ++ob) {
     uint32_t m = 0u;
-    int32_t rv[2][16];
+    int32_t rv[RB][16];
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
+    for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         rv[rb][r] = max(__float_as_int(acc[ob][rb][r]), 0);
-        if (ob < HeldRelu<NOB>::N) hv.v[ob][rb][r] = rv[rb][r];
+        if (ob < HeldRelu<NOB, RB>::N) hv.v[ob][rb][r] = rv[rb][r];
       }
     }
     // bits from the last element down, so that element e ends at bit e
     if (KEEP) {
 #pragma unroll
-      for (int e = 31; e >= 0; --e) m = push_nonzero_bit(m, rv[e >> 4][e & 15]);
+      for (int e = 16 * RB - 1; e >= 0; --e) m = push_nonzero_bit(m, rv[e >> 4][e & 15]);
       asm volatile("" : "+v"(m));
       mask[ob] = m;
       lw[ob] = (m | (m >> 16)) & 0xffffu;
     } else {
 #pragma unroll
-      for (int r = 15; r >= 0; --r) m = push_nonzero_bit(m, rv[0][r] | rv[1][r]);   // (both >= 0: the OR is zero iff both are)
+      for (int r = 15; r >= 0; --r) m = push_nonzero_bit(m, rv[0][r] | rv[RB - 1][r]);   // (both >= 0: the OR is zero iff both are)
       asm volatile("" : "+v"(m));
       lw[ob] = m;
     }
@@ -513,10 +539,11 @@ __device__ __forceinline__ void compact_publish(CompactLds& C, const f32x16 (&ac
 // XYZ (lin3): the three xyz rows follow the live rows as features 253..255 (lin4's xyz columns). Returns the padded row count.
 // hv: the ReLU values compact_publish kept. The rows' offsets are fetched from postab four quads at a time, ahead of the stores that use them
 // (a store to X may alias the table as far as the compiler knows, so a fetch placed behind a store waits for its own round trip).
-template <int NOB, bool XYZ>
-__device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const float* xyz, const f32x16 (&acc)[NOB][2], const HeldRelu<NOB>& hv, int wave,
+template <int NOB, bool XYZ, int RB>
+__device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const float* xyz, const f32x16 (&acc)[NOB][RB], const HeldRelu<NOB, RB>& hv, int wave,
                                                   int lane) {
   constexpr int RW = 32 * NOB;             // rows of a wave
+  constexpr int TILE = 32 * RB;
   const int tid = threadIdx.x;
   const int h = lane >> 5, j = lane & 31;
   const uint32_t trash_off = lds_off(C.trash) - lds_off(X);
@@ -527,7 +554,7 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
   for (int t = 0; t < NOB / 2; ++t) {
     uint32_t f, pos;
     const bool live = unit_position<NOB>(L, t, wave, lane, f, pos);
-    C.postab[f] = live ? pos * 256u : trash_off;
+    C.postab[f] = live ? pos * (uint32_t)(TILE * 4) : trash_off;
     if (live) C.klist[pos] = (uint16_t)f;
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -553,8 +580,8 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
     for (int i = 0; i < 4; ++i) {
       lds_float* dst = (lds_float*)(xl + po[i]);
 #pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-        if (ob < HeldRelu<NOB>::N) {
+      for (int rb = 0; rb < RB; ++rb) {
+        if (ob < HeldRelu<NOB, RB>::N) {
           dst[32 * rb] = __int_as_float(hv.v[ob][rb][4 * q + i]);
         } else {
           int bits = __float_as_int(acc[ob][rb][4 * q + i]);
@@ -567,30 +594,31 @@ __device__ __forceinline__ uint32_t compact_store(CompactLds& C, float* X, const
   __builtin_amdgcn_sched_barrier(0);
   uint32_t nl = nlive;
   if (XYZ) {
-    if (tid < 3 * 64) {
-      const int k = tid >> 6;
-      X[(nlive + k) * 64 + (tid & 63)] = xyz[tid];
-      if ((tid & 63) == 0) C.klist[nlive + k] = (uint16_t)(253 + k);
+    if (tid < 3 * TILE) {
+      const int k = tid / TILE;
+      X[(nlive + k) * TILE + (tid & (TILE - 1))] = xyz[tid];
+      if ((tid & (TILE - 1)) == 0) C.klist[nlive + k] = (uint16_t)(253 + k);
     }
     nl += 3;
   }
   const uint32_t npad = compact_npad(nl);
   for (uint32_t p = nl + (uint32_t)wave; p < npad; p += 4) {      // zero rows: exact no-op links; their list entries name any valid unit
-    X[p * 64 + lane] = 0.f;
+    if (lane < TILE) X[p * TILE + lane] = 0.f;
     if (lane == 0) C.klist[p] = 0;
   }
   return npad;
 }
 
 // the compacting counterpart of "barrier, writeback(), barrier"
-template <int NOB, bool KEEP, bool XYZ, class SM>
-__device__ __forceinline__ uint32_t writeback_compact(SM& S, const f32x16 (&acc)[NOB][2], int wave, int lane, uint32_t (&mask)[4]) {
-  static_assert(sizeof(CompactLds) <= sizeof(S.part) + sizeof(S.aux), "CompactLds lives in S.part .. S.aux");
-  CompactLds& C = *reinterpret_cast<CompactLds*>(S.part);
-  HeldRelu<NOB> hv;
-  compact_publish<NOB, KEEP>(C, acc, hv, wave, lane, mask);
+template <int NOB, bool KEEP, bool XYZ, class SM, int RB>
+__device__ __forceinline__ uint32_t writeback_compact(SM& S, const f32x16 (&acc)[NOB][RB], int wave, int lane, uint32_t (&mask)[4]) {
+  static_assert(SM::TILE == 32 * RB, "the layout of this tile size");
+  static_assert(std::is_same<SM, SmemC32>::value || sizeof(CompactLds) <= sizeof(S.part) + sizeof(S.aux), "CompactLds lives in S.part .. S.aux");
+  CompactLds& C = *compact_lds(S);
+  HeldRelu<NOB, RB> hv;
+  compact_publish<NOB, KEEP, RB>(C, acc, hv, wave, lane, mask);
   __syncthreads();
-  const uint32_t npad = compact_store<NOB, XYZ>(C, S.X, S.xyz, acc, hv, wave, lane);
+  const uint32_t npad = compact_store<NOB, XYZ, RB>(C, S.X, S.xyz, acc, hv, wave, lane);
   __syncthreads();
   return npad;
 }
@@ -675,8 +703,8 @@ static_assert(KSTEP_DENSE == 768, "5 layers of 32 x 4, lin3 32 x 2, lin4 16 x 4"
 // One row of lin8 on the h7 activations in S.X: four 128-long chains per ray (one per wave), combined in fixed order.
 // Returns (every thread, for ray = tid & (TILE-1)) the pre-tanh value. Ends with every thread past a barrier on S.part
 // reads only if the caller adds one before the next call (colour decoder: three rows).
-template <int RB>
-__device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float b8, Smem<RB>& S) {
+template <int RB, class SM>
+__device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float b8, SM& S) {
   constexpr int TILE = 32 * RB;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -696,14 +724,15 @@ __device__ __forceinline__ float lin8_row(const float* __restrict__ w8row, float
 // Returns (every thread, for ray = tid & (TILE-1)) the pre-tanh output. masks[l] = ReLU bitmasks of layer l
 // (bit rb*16+r of masks[l][ob]). DEBUG_STOP: (test builds only) return right after layer `stop` is in X.
 // STAGED: the caller already ran stage_bias (early, so that its loads overlap the tile's prologue).
-// COMPACT (64-ray narrow tile only; needs D.Wk): layers 1..7 walk the live hidden units of the tile (same values, fewer MFMAs).
-template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false, bool COMPACT = false>
+// COMPACT (narrow layout only; needs D.Wk; the 32-ray tile: on SmemC32): layers 1..7 walk the live hidden units of the tile (same values,
+// fewer MFMAs).
+template <int RB, bool KEEP, bool DEBUG_STOP = false, bool STAGED = false, bool WIDE = false, bool COMPACT = false, class SM>
 __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* __restrict__ c0,
-                                             const float* __restrict__ c4, Smem<RB>& S, uint32_t (&masks)[8][4],
+                                             const float* __restrict__ c4, SM& S, uint32_t (&masks)[8][4],
                                              int stop = 8, long long* ts = nullptr, uint32_t* ksteps = nullptr) {
   constexpr int TILE = 32 * RB;
   // ksteps (COMPACT only, may be null): receives the k-steps layers 1..7 executed for this tile, weighted by the layer's output blocks
-  // per wave (wave-uniform; the dense tile's figure is KSTEP_DENSE)
+  // per wave (wave-uniform; the dense tile's figure is KSTEP_DENSE, for either tile size)
   uint32_t kdone = 0u;
   // test builds: shader-clock / wall-clock stamps of wave 0 at phase boundaries (ts[2i], ts[2i+1])
 #define DISTR_TS(i) do { if (DEBUG_STOP && ts && threadIdx.x == 0) { ts[2 * (i)] = (long long)__builtin_readcyclecounter(); ts[2 * (i) + 1] = (long long)wall_clock64(); } } while (0)
@@ -714,7 +743,9 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
   const int h = lane >> 5;
   const int ray = tid & (TILE - 1);
   float* X = S.X;
-  static_assert(!COMPACT || (RB == 2 && !WIDE), "the compacted tile is the 64-ray tile of the narrow layout");
+  static_assert(SM::TILE == TILE, "the layout of this tile size");
+  static_assert(!COMPACT || !WIDE, "the compacted tile is a tile of the narrow layout");
+  static_assert(!COMPACT || has_bias_rows<SM>, "the compacted k-loop starts from the LDS bias rows");
   using CH = Chain<WIDE>;
   uint32_t npad = HID;   // compacted tile: rows of X the next layer walks
   // first weight group of every layer travels while the previous layer finishes (dense_pf)
@@ -750,12 +781,12 @@ __device__ __forceinline__ float mlp_forward(const DecoderDev& D, const float* _
   //   hand-scheduled (64-ray tile): dense_asm_k* (distr_dense_asm.hpp). Every layer's accumulators start from the LDS copy of its bias (srcC of
   //     the first MFMAs); the next layer's first weight group travels in `wpre` across the write-back; S.part..S.aux (4 KiB, idle during the
   //     layers) is the scratch of the tuple -> register move.
-  //   C++ (32-ray tile): acc_init + dense_pf, the first weight group in `wpre` likewise.
+  //   C++ (dense 32-ray tile): acc_init + dense_pf, the first weight group in `wpre` likewise.
   // per-thread operands of the two asm engines, each marked with the engine that reads it (an engine that is not instantiated leaves
   // its operands unused; the C++ engine reads none of them: it takes pointers)
   const uint32_t xaddr = lds_off(X) + (uint32_t)h * (TILE * 4) + (uint32_t)(lane & 31) * 4;            // (compacted, hand-scheduled) this lane's column of X
   const uint32_t bias0 = lds_off(bias_base(S)) + (uint32_t)h * 16;     // (compacted, hand-scheduled) + l * 2048 + (the wave's first row) * 4: start values of layer l's rows
-  const uint32_t kaddr = lds_off(reinterpret_cast<CompactLds*>(S.part)->klist) + (uint32_t)h * 2;      // (compacted only) this half-wave's entries of klist
+  const uint32_t kaddr = lds_off(compact_lds(S)->klist) + (uint32_t)h * 2;      // (compacted only) this half-wave's entries of klist
   const uint32_t voff = (uint32_t)lane * 16;                                                            // (hand-scheduled only) lane offset into a weight fragment
   const uint32_t scratch = lds_off(S.part) + (uint32_t)wave * 1024 + (uint32_t)lane * 16;              // (hand-scheduled only) tuple -> register scratch
   rsrc_t rs[8];                                                                                         // (hand-scheduled only) fragment streams of lin1..lin7

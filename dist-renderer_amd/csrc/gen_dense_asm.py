@@ -312,15 +312,20 @@ __device__ __forceinline__ void %s(f32x4 (&acc)[%d], f32x4 (&t)[8], uint32_t xad
 # by a ds_read_u16 one group earlier and sits in a VGPR pair with the constant lane offset -- no VALU per load. The trip count is an
 # SGPR operand (npad / 16 - 1, clamped by the caller). No cross-layer prefetch: the first features of the next layer are not known
 # before its write-back, so the 16 registers of gen()'s `t` tuples hold the index pairs instead.
+# RB = 1 (the 32-ray tile): the same stream with one ray block -- X rows of 128 bytes, one B read and one MFMA per (k-step, row block), the
+# B registers of the second block unused; a group's 4 gathers, 4 B reads and 4 index reads sit in its 16 (NOB = 2: 8, two per gap) MFMA gaps.
 #   v[160:167] four (index, lane offset) pairs   v168 running klist address   (A0/A1/B0/B1/VX/bias tuples as in gen())
 # A registers: A[buf] + NOB*s + ob (one load = all row blocks of k-step s).
 IDX = 160
 VK = 168
 
 
-def gen_compact(NOB, INIT='bias'):
-    """INIT: 'bias' (accumulators start from LDS bias tuples: the forward) or 'zero' (the backward's dX chain: no bias reads, no bias operand)."""
+def gen_compact(NOB, INIT='bias', RB=2):
+    """INIT: 'bias' (accumulators start from LDS bias tuples: the forward) or 'zero' (the backward's dX chain: no bias reads, no bias operand).
+    RB: ray blocks of the tile (2: 64 rays; 1: the 32-ray tile -- one B read and one MFMA per (k-step, row block), X rows of 128 bytes)."""
+    assert RB in (1, 2)
     bias = INIT == 'bias'
+    TILE = 32 * RB
     L = []
     emit = L.append
     width = {4: 'dwordx4', 2: 'dwordx2'}[NOB]
@@ -348,14 +353,14 @@ def gen_compact(NOB, INIT='bias'):
         pend = []
         if loads:
             pend += [('a', s) for s in range(4)]
-            pend += [('b', s, rb) for s in range(4) for rb in range(2)]
+            pend += [('b', s, rb) for s in range(4) for rb in range(RB)]
             pend += [('i', s) for s in range(4)]
+        per = -(-len(pend) // (4 * NOB * RB))     # loads per MFMA gap: one, or two where a group has fewer MFMAs than loads (RB = 1, NOB = 2)
         for s in range(4):
             for ob in range(NOB):
-                for rb in range(2):
+                for rb in range(RB):
                     mfma(cur, s, ob, rb)
-                    if pend:
-                        p = pend.pop(0)
+                    for p in [pend.pop(0) for _ in range(min(per, len(pend)))]:
                         if p[0] == 'a':
                             load_a(nxt, p[1])
                         elif p[0] == 'b':
@@ -387,12 +392,12 @@ def gen_compact(NOB, INIT='bias'):
                 lds('ds_read_b128 %s, %%[bias] offset:%d' % (ar(BIAS[slot_of[ob]] + 4 * q, 4), ob * 128 + q * 32), 'bias%d' % ob)
 
     def b0(s):
-        for rb in range(2):
+        for rb in range(RB):
             lds('ds_read_b32 %s, %%[xaddr] offset:%d' % (vr(B[0] + 2 * s + rb), s * 2 * TILE * 4 + rb * 128), 'b0s%d' % s)
 
     def first_mfmas(ob):
         wait_for('b0s0', 'bias%d' % ob)
-        for rb in range(2):
+        for rb in range(RB):
             mfma(0, 0, ob, rb, ar(BIAS[slot_of[ob]], 16) if bias else '0')
 
     # ---------------------------------------------------------------- prologue: groups 0 and 1 requested, indices of group 2 read
@@ -424,11 +429,11 @@ def gen_compact(NOB, INIT='bias'):
     else:
         b0(1); b0(2); b0(3)
         first_mfmas(1)
-    pend = [(ps, prb) for ps in range(4) for prb in range(2)]
+    pend = [(ps, prb) for ps in range(4) for prb in range(RB)]
     for s in range(1, 4):
         wait_for('b0s%d' % s)
         for ob in range(NOB):
-            for rb in range(2):
+            for rb in range(RB):
                 mfma(0, s, ob, rb)
                 if pend and s >= 2:
                     ps, prb = pend.pop(0)
@@ -449,29 +454,30 @@ def gen_compact(NOB, INIT='bias'):
     emit('s_nop 3')
     body = '\n'.join('      "%s\\n"' % x for x in L)
 
-    name = 'dense_asm_compact_n%d_%s' % (NOB, INIT)
-    outs = ', '.join('[c%d%d] "=&a"(acc[%d][%d])' % (ob, rb, ob, rb) for ob in range(NOB) for rb in range(2))
+    name = 'dense_asm_compact_n%d_%s%s' % (NOB, 'r1_' if RB == 1 else '', INIT)
+    outs = ', '.join('[c%d%d] "=&a"(acc[%d][%d])' % (ob, rb, ob, rb) for ob in range(NOB) for rb in range(RB))
     ins = '[xaddr] "v"(xaddr), [kaddr] "v"(kaddr), [voff] "v"(voff), [rs] "s"(rs), [soff] "s"(soff), [nit] "s"(nit)' + (', [bias] "v"(biasaddr)' if bias else '')
     clob = ['"v%d"' % i for i in range(IDX, VK + 1)] + ['"v%d"' % i for i in range(A[0], VX + 1)] + (['"a%d"' % i for i in range(BIAS[0], BIAS[2] + 16)] if bias else []) + ['"%s"' % S_CNT, '"scc"', '"memory"']
     if bias:
-        head = '// compacted tile: %d row blocks of 32 per wave; nit = positions / 16 - 1 (>= 1); klist / Wk: see gen_dense_asm.py' % NOB
+        head = '// compacted %stile: %d row blocks of 32 per wave; nit = positions / 16 - 1 (>= 1); klist / Wk: see gen_dense_asm.py' % ('32-ray ' if RB == 1 else '', NOB)
         tail = ',\n    uint32_t nit, uint32_t biasaddr) {'
     else:
         head = '// compacted tile, accumulators start from zero (the backward dX chain; weights: the transposed k-major pack Wkb): %d row blocks of 32 per wave' % NOB
         tail = ',\n    uint32_t nit) {'
     return name, '''%s
-__device__ __forceinline__ void %s(f32x16 (&acc)[%d][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff%s
+__device__ __forceinline__ void %s(f32x16 (&acc)[%d][%d], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff%s
   asm volatile(
 %s
       : %s
       : %s
       : %s);
 }
-''' % (head, name, NOB, tail, body, outs, ins, ', '.join(clob))
+''' % (head, name, NOB, RB, tail, body, outs, ins, ', '.join(clob))
 
 
 DENSE_SHAPES = ((512, 4, 4), (512, 4, 2), (512, 2, 4), (256, 4, 4), (512, 4, 0))      # (K, NOB, NOUT) of the 64-ray tile's layers
 COMPACT_SHAPES = (4, 2)                                                              # NOB
+COMPACT_FORMS = (('bias', 2), ('zero', 2), ('bias', 1))                              # (INIT, RB): forward and backward of the 64-ray tile, forward of the 32-ray tile
 
 
 def gen_dispatch():
@@ -489,15 +495,15 @@ def gen_dispatch():
                      % (kw, K, NOB, NOUT, '' if init == 'bias' else '!', K, NOB, NOUT, init))
             kw = 'else if'
     L += ['  else static_assert(K < 0, "no generated k-loop of this layer shape");', '}', '',
-          '// ... of the compacted tile (biasaddr: unused when the accumulators start from zero)',
-          'template <int NOB, bool BIAS>',
-          '__device__ __forceinline__ void dense_asm_compact(f32x16 (&acc)[NOB][2], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff,',
+          '// ... of the compacted tile of RB ray blocks, the accumulator\'s second extent (biasaddr: unused when the accumulators start from zero)',
+          'template <int NOB, bool BIAS, int RB>',
+          '__device__ __forceinline__ void dense_asm_compact(f32x16 (&acc)[NOB][RB], uint32_t xaddr, uint32_t kaddr, uint32_t voff, rsrc_t rs, uint32_t soff,',
           '    uint32_t nit, uint32_t biasaddr) {']
     kw = 'if'
-    for init in ('bias', 'zero'):
+    for (init, RB) in COMPACT_FORMS:
         for NOB in COMPACT_SHAPES:
-            L.append('  %s constexpr (NOB == %d && %sBIAS) dense_asm_compact_n%d_%s(acc, xaddr, kaddr, voff, rs, soff, nit%s);'
-                     % (kw, NOB, '' if init == 'bias' else '!', NOB, init, ', biasaddr' if init == 'bias' else ''))
+            L.append('  %s constexpr (NOB == %d && %sBIAS && RB == %d) dense_asm_compact_n%d_%s%s(acc, xaddr, kaddr, voff, rs, soff, nit%s);'
+                     % (kw, NOB, '' if init == 'bias' else '!', RB, NOB, 'r1_' if RB == 1 else '', init, ', biasaddr' if init == 'bias' else ''))
             kw = 'else if'
     L += ['  else static_assert(NOB < 0, "no generated compacted k-loop of this layer shape");', '}', '']
     return '\n'.join(L)
@@ -513,10 +519,9 @@ def main():
             out.append(gen(K, NOB, NOUT, init)[1])
     for (K, NB, NOUT) in ((512, 8, 8), (512, 8, 4), (512, 4, 8), (256, 8, 8), (512, 8, 0)):
         out.append(gen16(K, NB, NOUT)[1])
-    for NOB in COMPACT_SHAPES:
-        out.append(gen_compact(NOB)[1])
-    for NOB in COMPACT_SHAPES:
-        out.append(gen_compact(NOB, 'zero')[1])
+    for (init, RB) in COMPACT_FORMS:
+        for NOB in COMPACT_SHAPES:
+            out.append(gen_compact(NOB, init, RB)[1])
     out.append(gen_dispatch())
     out.append('}  // namespace distr')
     sys.stdout.write('\n'.join(out) + '\n')

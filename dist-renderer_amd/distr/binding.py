@@ -47,7 +47,8 @@ TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset',
                  # the same path on a described network: the colour decoder
                  'distr_train_net_workspace_bytes', 'distr_train_net_activation_offset', 'distr_train_net_forward', 'distr_train_net_backward']
 # the ordered live list seen from outside (include/distr_live_order.h, included by distr.h): block enumeration, k-step counts, list read-back
-LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list']
+LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list', 'distr_get_kstep32_stats',
+                      'distr_debug_mlp_layer32', 'distr_debug_tile_timing32']
 # the render backward's gradient-sample list, written out (include/distr_render_train.h, included by distr.h): weight gradients through render
 RENDER_TRAIN_EXPORTS = ['distr_render_max_samples', 'distr_render_samples_export_batch']
 # the colour stage's decoder list, written out (include/distr_color_train.h, included by distr.h): weight gradients through the colour render
@@ -182,7 +183,7 @@ SOURCES = ('distr_api.hip', 'distr_inst.hip', 'distr_inst.hpp', 'distr_kernels.h
            'distr_color_loss.hpp')
 HEADERS = ('distr.h', 'distr_mesh.h', 'distr_samples.h', 'distr_multi.h', 'distr_normal_grad.h', 'distr_color_batch.h', 'distr_train.h', 'distr_live_order.h',
            'distr_render_train.h', 'distr_color_train.h')                    # include/: the C ABI
-INST_GROUPS = 10           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
+INST_GROUPS = 11           # distr_inst.hpp: DISTR_NUM_INST_GROUPS translation units of explicit kernel instantiations
 HIPCC_FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-fPIC']
 
 
@@ -218,7 +219,8 @@ def build_commands(obj_dir=None):
 
 # kernels that contain the cluster tile (hand-counted vmcnt waits, live data in fixed registers between asm statements): unit, symbol part
 CLUSTER_KERNELS = (('inst1', 'k_stepILb1ELi0'), ('inst1', 'k_stepILb0ELi0'), ('inst2', 'k_tailILb1'), ('inst2', 'k_tailILb0'),
-                   ('inst3', 'k_march16ILi1ELb1'), ('inst3', 'k_march16ILi1ELb0'), ('inst8', 'k_stepILb1ELi0ELb1'), ('inst8', 'k_stepILb0ELi0ELb1'))
+                   ('inst3', 'k_march16ILi1ELb1'), ('inst3', 'k_march16ILi1ELb0'), ('inst8', 'k_stepILb1ELi0ELi1'), ('inst8', 'k_stepILb0ELi0ELi1'),
+                   ('inst11', 'k_stepILb1ELi0ELi2'), ('inst11', 'k_stepILb0ELi0ELi2'))
 NO_SCRATCH = ('k_step', 'k_march', 'k_bwd', 'k_tail')          # kernels that must not carry scratch (private segment 0): name parts
 
 
@@ -426,6 +428,9 @@ def lib():
             L.distr_block_pixel.argtypes = [i32, i32, i32, i32]
             L.distr_block_pixel.restype = i32
             L.distr_get_kstep_stats.argtypes = [vp, C.POINTER(RenderCfg), vp, i64p, i32, C.POINTER(C.c_int32), vp]
+            L.distr_get_kstep32_stats.argtypes = [vp, C.POINTER(RenderCfg), vp, i64p, i32, C.POINTER(C.c_int32), vp]
+            L.distr_debug_mlp_layer32.argtypes = L.distr_debug_mlp_layer.argtypes
+            L.distr_debug_tile_timing32.argtypes = L.distr_debug_tile_timing.argtypes
             i32p = C.POINTER(C.c_int32)
             L.distr_debug_live_list.argtypes = [vp, C.POINTER(RenderCfg), fp, fp, fp, i32, i32p, i32p, i32, i32p, i32p, i32p, vp, C.c_size_t, vp]
             L.distr_train_workspace_bytes.argtypes = [i32, i32, i64p]
@@ -607,7 +612,8 @@ class Context(object):
 
     def render_stats(self, cfg, ws, ksteps=False):
         """Counters of the forward that used `ws`. ksteps=True adds 'ksteps': per march launch (the order of live_counts) a tuple
-        (tiles, k-steps executed, k-steps of as many dense tiles) of the compacted 64-ray forward tiles (distr_get_kstep_stats)."""
+        (tiles, k-steps executed, k-steps of as many dense tiles) of the compacted 64-ray forward tiles (distr_get_kstep_stats), and
+        'ksteps32': the same tuple per FULL-RESOLUTION step for the 32-ray tiles of the step kernel's 32-ray role (distr_get_kstep32_stats)."""
         st = RenderStats()
         self.check(self.L.distr_get_render_stats(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), C.byref(st), self.stream()))
         out = {k: getattr(st, k) for k, _ in RenderStats._fields_ if k not in ('struct_size', 'reserved')}
@@ -616,6 +622,8 @@ class Context(object):
             buf, n = (C.c_int64 * (3 * cap))(), C.c_int32()
             self.check(self.L.distr_get_kstep_stats(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), buf, cap, C.byref(n), self.stream()))
             out['ksteps'] = [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(min(cap, n.value))]
+            self.check(self.L.distr_get_kstep32_stats(self.h, C.byref(cfg), C.c_void_p(ws.data_ptr()), buf, cap, C.byref(n), self.stream()))
+            out['ksteps32'] = [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(min(cap, n.value))]
         return out
 
     def debug_live_list(self, cfg, latent, R, T, step, ws):

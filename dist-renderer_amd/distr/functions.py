@@ -1163,13 +1163,25 @@ def debug_mlp_layer(engine, latent, points, layer):
     return out
 
 
+def debug_mlp_layer32(engine, latent, points, layer):
+    """Test aid: debug_mlp_layer on 32-point tiles, as the step kernel's 32-ray role runs them (compacted or dense by the engine's knobs)."""
+    L = engine.ctx.L
+    lat, x, n = _point_list(engine, latent, points)
+    out = torch.empty(n, 512, dtype=torch.float32, device=engine.device)
+    _list_call(engine, L.distr_debug_mlp_layer32, L.distr_mlp_workspace_bytes, lat, x, n, int(layer), out)
+    return out
+
+
 def debug_tile_timing(engine, latent, points, tile):
-    """Test aid: (sdf (n,), stamps (tiles, 20, 2) int64 [shader clock, 100 MHz wall clock]) of the decoder tile phases."""
+    """Test aid: (sdf (n,), stamps (tiles, 20, 2) int64 [shader clock, 100 MHz wall clock]) of the decoder tile phases; tile = 64, or 32 for
+    the 32-point tile of the step kernel's 32-ray role."""
     L, dev = engine.ctx.L, engine.device
+    if tile not in (32, 64):
+        raise ValueError('tile: 64 or 32')
     lat, x, n = _point_list(engine, latent, points)
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
     ts = torch.zeros((n + tile - 1) // tile, 20, 2, dtype=torch.int64, device=dev)
-    _list_call(engine, L.distr_debug_tile_timing, L.distr_mlp_workspace_bytes, lat, x, n, sdf, ts)
+    _list_call(engine, L.distr_debug_tile_timing if tile == 64 else L.distr_debug_tile_timing32, L.distr_mlp_workspace_bytes, lat, x, n, sdf, ts)
     return sdf, ts
 
 

@@ -33,6 +33,19 @@ int32_t distr_block_pixel(int32_t w, int32_t h, int32_t block, int32_t thread);
  * layer's k-loop, weighted by the layer's output blocks per wave (768 per dense tile). *n = launches; at most `cap` of them are written. */
 int distr_get_kstep_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws_dev, int64_t* out, int32_t cap, int32_t* n, void* stream);
 
+/* the same three figures for the 32-ray tiles of the step kernel's 32-ray role (exact f32), per FULL-RESOLUTION step only (out[3 t + ..],
+ * t = 0 .. fine steps - 1; *n = fine steps): a compacted tile (DISTR_COMPACT32, default 1, on top of DISTR_DENSE_COMPACT) adds the k-steps
+ * it executed, a dense one 768. These tiles are not part of distr_get_kstep_stats. */
+int distr_get_kstep32_stats(distr_ctx* ctx, const distr_render_cfg* cfg, const void* ws_dev, int64_t* out, int32_t cap, int32_t* n, void* stream);
+
+/* test aids: the 32-point tile as the step kernel's 32-ray role runs it (compacted or dense by the two knobs, read at distr_create), on a
+ * point list of 32-point tiles -- distr_debug_mlp_layer / distr_debug_tile_timing (distr.h) for the 32-ray tile, same arguments and outputs
+ * (ts_dev[ceil(n / 32)][40]). */
+int distr_debug_mlp_layer32(distr_ctx* ctx, const float* latent_dev, const float* xyz_dev, int64_t n, int layer, float* out_dev, void* ws_dev,
+                            size_t ws_bytes, void* stream);
+int distr_debug_tile_timing32(distr_ctx* ctx, const float* latent_dev, const float* xyz_dev, int64_t n, float* sdf_dev, long long* ts_dev,
+                              void* ws_dev, size_t ws_bytes, void* stream);
+
 /* test only: the live list full-resolution step `step` (0 .. fine steps - 2) read and the one it left for step + 1. Renders ONE view of
  * cfg up to and including that step into `ws_dev` (a forward workspace; no outputs are written), then copies both lists to the HOST arrays
  * read[cap] / left[cap] and their lengths to *nread / *nleft (entries = pixel indices). *ordered = 1 when the step kept the list in order,

@@ -4,7 +4,7 @@ random points of the cube (nearly every unit live for some ray: what tests/gpu_d
 the per-layer MFMA / write-back stamps of wave 0 (shader clock), the tile total, and the live fraction per layer counted on the device.
 DISTR_DENSE_COMPACT=0|1 in the environment chooses the loop (read at distr_create).
 
-    python profiles/tools/diag_compact_tile.py [--n 65536] [--reps 10] [--cube]
+    python profiles/tools/diag_compact_tile.py [--n 65536] [--reps 10] [--cube] [--tile 32 --n 8192]
 """
 import argparse
 import os
@@ -40,6 +40,8 @@ def main():
     ap.add_argument('--n', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--cube', action='store_true', help='random points of the cube instead of image rows')
+    ap.add_argument('--tile', type=int, default=64, choices=[64, 32], help='32: the 32-point tile of the step kernel\'s 32-ray role (DISTR_COMPACT32=0|1 chooses its loop); '
+                    'use --n 8192 for one tile per compute unit, as the role runs')
     args = ap.parse_args()
     from distr import fixture, functions
     Ws, bs, latent = fixture.make_decoder_weights()
@@ -62,8 +64,10 @@ def main():
     print('points: %s; DISTR_DENSE_COMPACT=%s' % ('cube' if args.cube else 'image rows', os.environ.get('DISTR_DENSE_COMPACT', '(default)')))
     print('distr_mlp_eval n=%d: median %.3f ms (min %.3f) = %.1f algorithmic TFLOP/s = %.3f of the f32-MFMA peak'
           % (args.n, med, min(ts), FLOP * args.n / med / 1e9, FLOP * args.n / med / 1e9 / PEAK))
-    nst = min(args.n, 256 * 64 * 4) // 64 * 64
-    _, st = functions.debug_tile_timing(eng, lat, pts[:nst], 64)
+    T = args.tile
+    nst = min(args.n, 256 * 64 * 4) // T * T
+    print('stamps: %d tiles of %d points; DISTR_COMPACT32=%s' % (nst // T, T, os.environ.get('DISTR_COMPACT32', '(default)')))
+    _, st = functions.debug_tile_timing(eng, lat, pts[:nst], T)
     st = st.cpu().numpy().astype(np.int64)
     cyc, wall = st[:, :, 0], st[:, :, 1]
     d = np.median(cyc[:, 1:19] - cyc[:, 0:18], axis=0)
@@ -71,10 +75,11 @@ def main():
     print('tile total %.0f cycles = %.1f us (clock %.3f GHz)' % (tot_c, tot_w / 100.0, tot_c / (tot_w * 10.0) if tot_w else 0))
     names = ['L%d %s' % (l, w) for l in range(8) for w in ('mfma', 'wb')] + ['lin8', 'end']
     print(' '.join('%s:%.0f' % (nm, v) for nm, v in zip(names, d)))
-    ntile = min(64, args.n // 64)
+    ntile = min(64, args.n // T)
     fr = []
+    layer_dump = functions.debug_mlp_layer if T == 64 else functions.debug_mlp_layer32
     for l in range(7):
-        a = functions.debug_mlp_layer(eng, lat, pts[:ntile * 64], l).reshape(ntile, 64, 512)[:, :, :253 if l == 3 else 512]
+        a = layer_dump(eng, lat, pts[:ntile * T], l).reshape(ntile, T, 512)[:, :, :253 if l == 3 else 512]
         fr.append(float((a > 0).any(dim=1).float().mean()))
     print('live fraction per layer (%d tiles): ' % ntile + ' '.join('L%d:%.3f' % (l, v) for l, v in enumerate(fr)))
 
