@@ -2163,6 +2163,57 @@ int distr_nearest_sqdist(distr_ctx* ctx, const float* a, int64_t na, const float
   return DISTR_OK;
 }
 
+size_t distr_mesh_sdf_workspace_bytes(int64_t nq, int64_t nfaces) {
+  if (nq < 1 || nfaces < 1) return 0;
+  const int64_t nchunks = (nfaces + mesh::SDF_CHUNK - 1) / mesh::SDF_CHUNK;
+  WsCarve c(nullptr);
+  c.take<unsigned long long>(nq);
+  c.take<double>(nchunks * nq);
+  return c.bytes();
+}
+
+int distr_mesh_sdf(distr_ctx* ctx, const float* verts, int64_t nverts, const int32_t* faces, int64_t nfaces, const float* q, int64_t nq,
+                   float* sdf, float* d2, float* winding, int32_t* face, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  const int64_t nchunks = (nfaces + mesh::SDF_CHUNK - 1) / mesh::SDF_CHUNK;
+  if (nverts < 1 || nfaces < 1 || nfaces > INT32_MAX || nchunks > 65535 || nq < 0 || nq > INT32_MAX)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "signed distance needs a mesh with vertices and 1 .. %d triangles (%lld, %lld) and 0 <= nq < 2^31 (%lld)",
+                65535 * mesh::SDF_CHUNK, (long long)nverts, (long long)nfaces, (long long)nq);
+  if (!verts || !faces || (nq > 0 && (!q || !sdf || !ws))) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < distr_mesh_sdf_workspace_bytes(nq, nfaces)) return fail(ctx, DISTR_ERR_WORKSPACE, "signed-distance workspace too small");
+  if (nq == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  WsCarve c(ws);
+  unsigned long long* best = c.take<unsigned long long>(nq);
+  double* wsum = c.take<double>(nchunks * nq);
+  const unsigned qblocks = (unsigned)((nq + mesh::MB - 1) / mesh::MB);
+  const mesh::SurfMesh m{verts, nverts, faces, nfaces};
+  hipLaunchKernelGGL(mesh::k_sdf_init, dim3(qblocks), dim3(mesh::MB), 0, s, best, (long long)nq);
+  LAUNCH_CHECK("k_sdf_init");
+  hipLaunchKernelGGL(mesh::k_sdf_pairs, dim3(qblocks, (unsigned)nchunks), dim3(mesh::MB), 0, s, m, q, (long long)nq, best, wsum);
+  LAUNCH_CHECK("k_sdf_pairs");
+  hipLaunchKernelGGL(mesh::k_sdf_finish, dim3(qblocks), dim3(mesh::MB), 0, s, q, (long long)nq, (const unsigned long long*)best,
+                     (const double*)wsum, (long long)nchunks, sdf, d2, winding, face);
+  LAUNCH_CHECK("k_sdf_finish");
+  return DISTR_OK;
+}
+
+int distr_sdf_queries(distr_ctx* ctx, const float* surf, int64_t ns, float sigma_a, float sigma_b, int64_t n_uniform, float half_extent,
+                      uint64_t seed, float* q_out, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (ns < 0 || n_uniform < 0 || ns > INT32_MAX || n_uniform > INT32_MAX)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "query counts %lld, %lld (need 0 <= count < 2^31)", (long long)ns, (long long)n_uniform);
+  const int64_t n = std::max(ns, n_uniform);
+  if ((ns > 0 && !surf) || (n > 0 && !q_out)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (n == 0) return DISTR_OK;
+  hipLaunchKernelGGL(mesh::k_sdf_queries, dim3((unsigned)((n + mesh::MB - 1) / mesh::MB)), dim3(mesh::MB), 0, (hipStream_t)stream, surf,
+                     (long long)ns, sigma_a, sigma_b, (long long)n_uniform, half_extent, seed, q_out);
+  LAUNCH_CHECK("k_sdf_queries");
+  return DISTR_OK;
+}
+
 }  // extern "C"
 
 // ---- depth maps back-projected into SDF samples (include/distr_samples.h, kernels: distr_samples.hpp)

@@ -3,6 +3,9 @@
 //   marching cubes     over a dense f32 grid (nx, ny, nz), x slowest (the layout create_sdf_grid returns)
 //   surface sampling   area-weighted, trimesh.sample.sample_surface's rule (searchsorted on the cumulative area, folded parallelogram)
 //   nearest distance   brute force squared distance from every point of A to the nearest of B (one chamfer direction)
+// and the way back from a mesh to training data (no counterpart in the reference, which loads preprocessed files; at the end of the file):
+//   signed distance    brute force exact point-to-triangle distance, signed by the generalised winding number
+//   query points       DeepSDF-style: surface samples perturbed at two scales plus uniform points, from the sampler's generator
 //
 // No MFMA: scans and VALU loops. Every output position comes from an exclusive scan in a fixed order (per-thread serial run of
 // MTILE / MB items -> LDS scan over the block -> one ordered pass over the block totals), never from an atomic, so every output is
@@ -615,6 +618,207 @@ DISTR_GLOBAL void __launch_bounds__(MB) k_dist_sums(const float* __restrict__ d2
   D2 tot;
   block_excl_scan(s, lds, &tot);
   if (threadIdx.x == 0) btot[blockIdx.x] = tot;
+}
+
+// ------------------------------------------------------------------------------------------ signed distance to a triangle mesh
+// k_sdf_pairs: one thread per query q, faces staged through LDS in tiles of SDF_TILE records (a, ab = b - a, ac = c - a and a flag:
+// three float4 per face, 12 KB per tile; every lane reads the same record, a broadcast). blockIdx.y = one chunk of SDF_CHUNK faces, a
+// compile-time constant: which faces a thread sums together never depends on nq or on the device, so the row of a query does not
+// depend on which other queries are in the call. Brute force over all pairs, like k_nearest.
+//
+// A face is SKIPPED (no distance, no solid angle) when it names a vertex outside [0, nv) (face_ok), when one of its nine coordinates
+// is not finite, or when its float32 cross product ab x ac is exactly (0, 0, 0): (aby*acz - abz*acy, abz*acx - abx*acz, abx*acy - aby*acx).
+//
+// Per pair, all in float32, no fused multiply-add (-ffp-contract=off), IEEE division and square root; dot(u, v) is
+// (ux*vx + uy*vy) + uz*vz throughout:
+//   ap = q - a,  bp = ap - ab,  cp = ap - ac                          (componentwise)
+//   d1 = dot(ab, ap)  d2 = dot(ac, ap)  d3 = dot(ab, bp)  d4 = dot(ac, bp)  d5 = dot(ab, cp)  d6 = dot(ac, cp)
+//   vc = d1*d4 - d3*d2,  vb = d5*d2 - d1*d6,  va = d3*d6 - d5*d4,  e43 = d4 - d3,  e56 = d5 - d6
+//   (sn, sd, tn, td) and the second direction e, the first of (Ericson, Real-Time Collision Detection 5.1.5, in its order):
+//     d1 <= 0 and d2 <= 0                 vertex a   (0, 1, 0, 1)                                   e = ac
+//     d3 >= 0 and d4 <= d3                vertex b   (1, 1, 0, 1)                                   e = ac
+//     vc <= 0 and d1 >= 0 and d3 <= 0     edge ab    (d1, d1 - d3, 0, 1)                            e = ac
+//     d6 >= 0 and d5 <= d6                vertex c   (0, 1, 1, 1)                                   e = ac
+//     vb <= 0 and d2 >= 0 and d6 <= 0     edge ac    (0, 1, d2, d2 - d6)                            e = ac
+//     va <= 0 and e43 >= 0 and e56 >= 0   edge bc    (1, 1, e43, e43 + e56)                         e = ac - ab
+//     otherwise                           interior   (vb, (va + vb) + vc, vc, (va + vb) + vc)       e = ac
+//   s = sn / sd,  t = tn / td,  p = (a + s*ab) + t*e,  d = q - p,  dist2 = (dx*dx + dy*dy) + dz*dz
+// (edge bc is Ericson's b + w (c - b) with b = a + ab: two independently rounded weights s + t = 1 on ab and ac would leave p off the
+// edge by an ulp of the edge's length in every coordinate, also in those where b and c agree.)
+// A pair counts for the minimum only when dist2 < +inf (a 0 / 0 of a face too small for float32, or an overflow, never wins). Ties go
+// to the lowest face index: within a thread faces come in ascending order under a strict <, between chunks the key
+// (bits(dist2) << 32) | face meets in an integer atomicMin (dist2 >= +0, so the order of the bits is the order of the values).
+//
+// Signed solid angle (Van Oosterom & Strackee) of the same pair:
+//   A = a - q,  B = A + ab,  C = A + ac
+//   cr = (By*Cz - Bz*Cy, Bz*Cx - Bx*Cz, Bx*Cy - By*Cx),  num = dot(A, cr)
+//   la = sqrt(dot(A, A)),  lb = sqrt(dot(B, B)),  lc = sqrt(dot(C, C))
+//   den = ((((la*lb)*lc) + dot(A, B)*lc) + dot(B, C)*la) + dot(C, A)*lb
+//   half = atan2f(num, den)                                            (Omega = 2 * half)
+// A thread adds `half` in float32 over one tile in face order (from +0), adds the tile sums to a float64 in tile order and writes the
+// chunk's float64 to wsum[chunk][query]; k_sdf_finish adds the chunks in chunk order and scales by 1 / (2 pi): the generalised winding
+// number w = sum(Omega) / (4 pi), +1 inside a closed mesh whose normals point outwards, 0 outside. No float atomic anywhere.
+constexpr int SDF_TILE = 256;      // face records per LDS tile
+constexpr int SDF_CHUNK = 1024;    // faces per blockIdx.y: a constant of the ABI (distr.mesh.SDF_CHUNK mirrors it)
+constexpr unsigned long long SDF_NONE = 0x7f800000ffffffffull;     // (+inf, face -1): no face counted
+
+__device__ __forceinline__ float dot3(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
+__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_init(unsigned long long* __restrict__ best, long long n) {
+  const long long i = (long long)blockIdx.x * MB + threadIdx.x;
+  if (i < n) best[i] = SDF_NONE;
+}
+
+DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_pairs(const SurfMesh m, const float* __restrict__ Q, long long nq,
+                                                    unsigned long long* __restrict__ best, double* __restrict__ wsum) {
+  __shared__ float4 tile[3][SDF_TILE];     // [0] a.xyz, ab.x   [1] ab.yz, ac.xy   [2] ac.z, flag (1 counted, 0 skipped), -, -
+  const long long i = (long long)blockIdx.x * MB + threadIdx.x;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (i < nq) { qx = Q[3 * i]; qy = Q[3 * i + 1]; qz = Q[3 * i + 2]; }
+  const float inf = __int_as_float(0x7f800000);
+  float bestd = inf;
+  unsigned bestf = 0xffffffffu;
+  double wacc = 0.0;
+  const long long f0 = (long long)blockIdx.y * SDF_CHUNK, f1 = f0 + SDF_CHUNK < m.nf ? f0 + SDF_CHUNK : m.nf;
+  for (long long t0 = f0; t0 < f1; t0 += SDF_TILE) {
+    const int cnt = (int)(f1 - t0 < SDF_TILE ? f1 - t0 : SDF_TILE);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const long long f = t0 + threadIdx.x;
+      float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
+      if (face_ok(m, f)) {
+        const int* fi = m.faces + 3 * f;
+        const float* a = m.verts + 3 * (long long)fi[0];
+        const float* b = m.verts + 3 * (long long)fi[1];
+        const float* c = m.verts + 3 * (long long)fi[2];
+        const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2], cx = c[0], cy = c[1], cz = c[2];
+        const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
+        const float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+        const bool fin = finite_f(ax) && finite_f(ay) && finite_f(az) && finite_f(bx) && finite_f(by) && finite_f(bz) && finite_f(cx) &&
+                         finite_f(cy) && finite_f(cz);
+        const bool ok = fin && !(nx == 0.f && ny == 0.f && nz == 0.f);
+        if (ok) {
+          r0 = make_float4(ax, ay, az, abx);
+          r1 = make_float4(aby, abz, acx, acy);
+          r2 = make_float4(acz, 1.f, 0.f, 0.f);
+        }
+      }
+      tile[0][threadIdx.x] = r0;
+      tile[1][threadIdx.x] = r1;
+      tile[2][threadIdx.x] = r2;
+    }
+    __syncthreads();
+    float wt = 0.f;
+#pragma unroll 2
+    for (int k = 0; k < cnt; ++k) {
+      const float4 r2 = tile[2][k];
+      if (r2.y == 0.f) continue;                               // a skipped face (the same for every lane)
+      const float4 r0 = tile[0][k], r1 = tile[1][k];
+      const float ax = r0.x, ay = r0.y, az = r0.z, abx = r0.w, aby = r1.x, abz = r1.y, acx = r1.z, acy = r1.w, acz = r2.x;
+      // closest point of the triangle
+      const float apx = qx - ax, apy = qy - ay, apz = qz - az;
+      const float bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
+      const float cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
+      const float d1 = dot3(abx, aby, abz, apx, apy, apz), d2 = dot3(acx, acy, acz, apx, apy, apz);
+      const float d3 = dot3(abx, aby, abz, bpx, bpy, bpz), d4 = dot3(acx, acy, acz, bpx, bpy, bpz);
+      const float d5 = dot3(abx, aby, abz, cpx, cpy, cpz), d6 = dot3(acx, acy, acz, cpx, cpy, cpz);
+      const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+      const float e43 = d4 - d3, e56 = d5 - d6;
+      float sn = vb, tn = vc, sd = (va + vb) + vc, td = sd;    // interior, then the regions from the last to the first in priority
+      bool bc = false;
+      if (va <= 0.f && e43 >= 0.f && e56 >= 0.f) { sn = 1.f; sd = 1.f; tn = e43; td = e43 + e56; bc = true; }
+      if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { sn = 0.f; sd = 1.f; tn = d2; td = d2 - d6; bc = false; }
+      if (d6 >= 0.f && d5 <= d6) { sn = 0.f; sd = 1.f; tn = 1.f; td = 1.f; bc = false; }
+      if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { sn = d1; sd = d1 - d3; tn = 0.f; td = 1.f; bc = false; }
+      if (d3 >= 0.f && d4 <= d3) { sn = 1.f; sd = 1.f; tn = 0.f; td = 1.f; bc = false; }
+      if (d1 <= 0.f && d2 <= 0.f) { sn = 0.f; sd = 1.f; tn = 0.f; td = 1.f; bc = false; }
+      const float s = sn / sd, t = tn / td;
+      const float ex = bc ? acx - abx : acx, ey = bc ? acy - aby : acy, ez = bc ? acz - abz : acz;
+      const float dx = qx - ((ax + s * abx) + t * ex), dy = qy - ((ay + s * aby) + t * ey), dz = qz - ((az + s * abz) + t * ez);
+      const float dist2 = (dx * dx + dy * dy) + dz * dz;
+      if (dist2 < bestd) { bestd = dist2; bestf = (unsigned)(t0 + k); }       // NaN never passes; +inf never beats the initial +inf
+      // signed solid angle
+      const float Ax = ax - qx, Ay = ay - qy, Az = az - qz;
+      const float Bx = Ax + abx, By = Ay + aby, Bz = Az + abz;
+      const float Cx = Ax + acx, Cy = Ay + acy, Cz = Az + acz;
+      const float num = dot3(Ax, Ay, Az, By * Cz - Bz * Cy, Bz * Cx - Bx * Cz, Bx * Cy - By * Cx);
+      const float la = sqrtf(dot3(Ax, Ay, Az, Ax, Ay, Az)), lb = sqrtf(dot3(Bx, By, Bz, Bx, By, Bz)), lc = sqrtf(dot3(Cx, Cy, Cz, Cx, Cy, Cz));
+      const float den = ((((la * lb) * lc) + dot3(Ax, Ay, Az, Bx, By, Bz) * lc) + dot3(Bx, By, Bz, Cx, Cy, Cz) * la) +
+                        dot3(Cx, Cy, Cz, Ax, Ay, Az) * lb;
+      wt += atan2f(num, den);
+    }
+    wacc += (double)wt;
+  }
+  if (i < nq) {
+    wsum[(long long)blockIdx.y * nq + i] = wacc;
+    if (bestf != 0xffffffffu) atomicMin(best + i, (unsigned long long)__float_as_uint(bestd) << 32 | bestf);
+  }
+}
+
+// Adds the chunks' float64 solid-angle sums in chunk order and writes the outputs: sdf = (|w| > 0.5 ? -1 : +1) * sqrtf(dist2) with w in
+// float32 (|w|: a consistently inward-wound mesh gives the same signs). No counted face: sdf = +inf, face = -1. A query with a
+// coordinate that is not finite: sdf = dist2 = w = NaN, face = -1. d2 / w / face may be null.
+DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_finish(const float* __restrict__ Q, long long nq, const unsigned long long* __restrict__ best,
+                                                     const double* __restrict__ wsum, long long nchunks, float* __restrict__ sdf,
+                                                     float* __restrict__ d2, float* __restrict__ wind, int* __restrict__ face) {
+  const long long i = (long long)blockIdx.x * MB + threadIdx.x;
+  if (i >= nq) return;
+  double tot = 0.0;
+  for (long long c = 0; c < nchunks; ++c) tot += wsum[c * nq + i];
+  float w = (float)(tot * 0.15915494309189535);                  // 1 / (2 pi): the sums are of Omega / 2
+  const unsigned long long key = best[i];
+  float dist2 = __uint_as_float((unsigned)(key >> 32));
+  int f = (int)(unsigned)(key & 0xffffffffu);
+  float out = (fabsf(w) > 0.5f ? -1.f : 1.f) * sqrtf(dist2);
+  if (!(finite_f(Q[3 * i]) && finite_f(Q[3 * i + 1]) && finite_f(Q[3 * i + 2]))) {
+    out = dist2 = w = __int_as_float(0x7fc00000);
+    f = -1;
+  }
+  sdf[i] = out;
+  if (d2) d2[i] = dist2;
+  if (wind) wind[i] = w;
+  if (face) face[i] = f;
+}
+
+// ------------------------------------------------------------------------------------------ DeepSDF-style query points
+// From ns surface points (distr_sample_surface) 2 * ns + nu queries, each a pure function of (seed, its index):
+//   out[2 i]     = p_i + sigma_a * (z0, z1, z2)          out[2 i + 1] = p_i + sigma_b * (z3, z4, z5)         i < ns
+//   out[2 ns + j] = ((2 ux - 1) * h, (2 uy - 1) * h, (2 uz - 1) * h)                                           j < nu
+// Random words: W(n) = rnd_bits(seed, n, 3) -- slot k = 3, which k_sample (k = 0..2 of its sample index) never draws: the counters
+// 4 n + 3 and 4 i + k <= 2 differ for every n and i. Surface point i owns W(8 i), W(8 i + 1), W(8 i + 2), uniform point j owns
+// W(8 j + 4), W(8 j + 5). A word gives two 24-bit numbers, hi = W >> 40 and lo = (W >> 8) & 0xffffff.
+//   Box-Muller of word m = 0, 1, 2 of point i: u1 = (hi + 1) * 2^-24 in (0, 1], u2 = lo * 2^-24 in [0, 1),
+//     r = sqrtf(-2 * logf(u1)),  ang = 6.2831855f * u2,  z(2m) = r * cosf(ang),  z(2m + 1) = r * sinf(ang)
+//   uniform point j: ux = hi(W(8 j + 4)) * 2^-24, uy = lo(W(8 j + 4)) * 2^-24, uz = hi(W(8 j + 5)) * 2^-24
+DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_queries(const float* __restrict__ surf, long long ns, float sigma_a, float sigma_b,
+                                                      long long nu, float h, uint64_t seed, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * MB + threadIdx.x;
+  if (i < ns) {
+    float z[6];
+#pragma unroll
+    for (int mth = 0; mth < 3; ++mth) {
+      const uint64_t w = rnd_bits(seed, 8ull * (uint64_t)i + mth, 3);
+      const float u1 = (float)((unsigned)(w >> 40) + 1u) * 0x1.0p-24f, u2 = (float)((unsigned)(w >> 8) & 0xffffffu) * 0x1.0p-24f;
+      const float r = sqrtf(-2.f * logf(u1)), ang = 6.2831855f * u2;
+      z[2 * mth] = r * cosf(ang);
+      z[2 * mth + 1] = r * sinf(ang);
+    }
+    const float* p = surf + 3 * i;
+    float* d = out + 6 * i;
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+      d[x] = p[x] + sigma_a * z[x];
+      d[3 + x] = p[x] + sigma_b * z[3 + x];
+    }
+  }
+  if (i < nu) {
+    const uint64_t w0 = rnd_bits(seed, 8ull * (uint64_t)i + 4, 3), w1 = rnd_bits(seed, 8ull * (uint64_t)i + 5, 3);
+    float* d = out + 3 * (2 * ns + i);
+    d[0] = (2.f * ((float)(unsigned)(w0 >> 40) * 0x1.0p-24f) - 1.f) * h;
+    d[1] = (2.f * ((float)((unsigned)(w0 >> 8) & 0xffffffu) * 0x1.0p-24f) - 1.f) * h;
+    d[2] = (2.f * ((float)(unsigned)(w1 >> 40) * 0x1.0p-24f) - 1.f) * h;
+  }
 }
 
 }  // namespace mesh

@@ -27,7 +27,9 @@ EXPORTS = ['distr_version', 'distr_abi_version', 'distr_create_abi', 'distr_dest
            'distr_render_forward_batch', 'distr_render_backward_batch', 'distr_render_normal_batch', 'distr_mlp_eval_bf16x6', 'distr_mlp_eval_f16x3']
 # shape evaluation (include/distr_mesh.h, included by distr.h): marching cubes, surface sampling, nearest-point distances
 MESH_EXPORTS = ['distr_mc_workspace_bytes', 'distr_mc_count', 'distr_mc_emit', 'distr_sample_workspace_bytes', 'distr_sample_surface',
-                'distr_nearest_workspace_bytes', 'distr_nearest_sqdist']
+                'distr_nearest_workspace_bytes', 'distr_nearest_sqdist',
+                # signed distances to a mesh and DeepSDF-style query points: SDF training samples
+                'distr_mesh_sdf_workspace_bytes', 'distr_mesh_sdf', 'distr_sdf_queries']
 # depth maps back-projected into SDF samples (include/distr_samples.h, included by distr.h): SDFRenderer_deepsdf
 SAMPLES_EXPORTS = ['distr_depth_samples_workspace_bytes', 'distr_depth_samples_count', 'distr_depth_samples_forward',
                    'distr_depth_samples_backward']
@@ -396,6 +398,10 @@ def lib():
             L.distr_nearest_workspace_bytes.argtypes = [i64]
             L.distr_nearest_workspace_bytes.restype = C.c_size_t
             L.distr_nearest_sqdist.argtypes = [vp, fp, i64, fp, i64, fp, vp, vp, C.c_size_t, vp]
+            L.distr_mesh_sdf_workspace_bytes.argtypes = [i64, i64]
+            L.distr_mesh_sdf_workspace_bytes.restype = C.c_size_t
+            L.distr_mesh_sdf.argtypes = [vp, fp, i64, vp, i64, fp, i64, fp, fp, fp, vp, vp, C.c_size_t, vp]
+            L.distr_sdf_queries.argtypes = [vp, fp, i64, C.c_float, C.c_float, i64, C.c_float, C.c_uint64, fp, vp]
             szp, scfg = C.POINTER(C.c_size_t), C.POINTER(SamplesCfg)
             L.distr_depth_samples_workspace_bytes.argtypes = [vp, scfg, i32, i64p, szp, szp, szp]
             L.distr_depth_samples_count.argtypes = [vp, scfg, i32, fp, vp, i64p, vp, C.c_size_t, vp]

@@ -1,5 +1,6 @@
 """Shape evaluation on the MI355X (include/distr_mesh.h, csrc/distr_mesh.hpp): marching cubes, area-weighted surface sampling,
-nearest-point distances and the chamfer distance, plus a plain-numpy PLY writer / reader.
+nearest-point distances and the chamfer distance, plus a plain-numpy PLY writer / reader; and the way back from a mesh to training
+data: signed distances to a triangle mesh and DeepSDF-style SDF samples (signed_distance, sdf_samples, the pos / neg npz layout).
 
 What the reference does on the host with scikit-image (marching_cubes_lewiner), plyfile, trimesh (sample_surface) and two scipy
 KD-trees (core/evaluation/create_mesh.py, transforms.py, eval_func.py). No third-party package beyond torch and numpy; no CPU path:
@@ -129,6 +130,115 @@ def chamfer(p1, p2, use_square_dist=True, separate=False):
     if separate:
         return d21, d12
     return d21 + d12
+
+
+# ------------------------------------------------------------------------------------------------- SDF samples from a mesh
+SDF_CHUNK = 1024                  # faces per chunk of distr_mesh_sdf (SDF_CHUNK of csrc/distr_mesh.hpp): one float64 per query and chunk
+_SDF_WS_BYTES = 64 << 20          # signed_distance takes its queries in pieces whose workspace stays below this
+
+
+def signed_distance(verts, faces, points, details=False):
+    """Signed distance of points (Q, 3) to the triangle mesh, float32 (Q,) on the mesh's device: the distance to the closest point of
+    the nearest triangle (exact point-to-triangle distance in float32, brute force over all pairs), negative where the generalised
+    winding number w says inside (|w| > 0.5; w = +1 inside a closed mesh wound like marching_cubes' output, 0 outside, fractional for
+    an open one). details=True: (sdf, squared distance, w float32, nearest face int64 -- the lowest index among equal distances).
+    Triangles that name a vertex outside the array, have a coordinate that is not finite or a float32 cross product of exactly zero
+    are skipped; with no triangle left the distance is +inf and the face -1. A point with a coordinate that is not finite gives NaN
+    and face -1. The queries are processed in pieces so that the workspace stays bounded; every row depends on its own point only."""
+    v = _cuda(verts, torch.float32)
+    f = _cuda(faces, torch.int32, v.device)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError('signed_distance: verts (V, 3) and faces (F, 3) expected')
+    if f.shape[0] == 0 or v.shape[0] == 0:
+        raise ValueError('signed_distance: the mesh has no triangles')
+    q = _cuda(points, torch.float32, v.device).reshape(-1, 3)
+    nq, nf = q.shape[0], f.shape[0]
+    ctx = _context(v.device)
+    L = ctx.L
+    sdf = torch.empty((nq,), dtype=torch.float32, device=v.device)
+    d2 = torch.empty((nq,), dtype=torch.float32, device=v.device) if details else None
+    w = torch.empty((nq,), dtype=torch.float32, device=v.device) if details else None
+    fidx = torch.empty((nq,), dtype=torch.int32, device=v.device) if details else None
+    nchunks = (nf + SDF_CHUNK - 1) // SDF_CHUNK
+    piece = max(256, min(1 << 16, _SDF_WS_BYTES // (8 * (nchunks + 1))) // 256 * 256)
+    ws = _workspace(L.distr_mesh_sdf_workspace_bytes(min(piece, max(nq, 1)), nf), v.device)
+    with torch.cuda.device(v.device):
+        s = ctx.stream()
+        for i0 in range(0, nq, piece):
+            n = min(piece, nq - i0)
+            ctx.check(L.distr_mesh_sdf(ctx.h, binding.ptr(v), v.shape[0], binding.ptr(f), nf, binding.ptr(q[i0:]), n, binding.ptr(sdf[i0:]),
+                                       binding.ptr(d2[i0:]) if details else None, binding.ptr(w[i0:]) if details else None,
+                                       binding.ptr(fidx[i0:]) if details else None, binding.ptr(ws), ws.numel(), s))
+    if details:
+        return sdf, d2, w, fidx.long()
+    return sdf
+
+
+def sdf_queries(surface_points, sigmas, n_uniform, half_extent=1.0, seed=0):
+    """DeepSDF-style query points (2 * S + n_uniform, 3) float32 from S surface points: rows 2 i and 2 i + 1 are point i plus
+    sigmas[0] resp. sigmas[1] times standard normals, the last n_uniform rows are uniform in [-half_extent, half_extent)^3. Every row
+    is a function of (seed, its index) alone."""
+    p = _cuda(surface_points, torch.float32).reshape(-1, 3)
+    ns, nu = p.shape[0], int(n_uniform)
+    if nu < 0:
+        raise ValueError('sdf_queries: n_uniform must not be negative')
+    ctx = _context(p.device)
+    out = torch.empty((2 * ns + nu, 3), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        ctx.check(ctx.L.distr_sdf_queries(ctx.h, binding.ptr(p), ns, float(sigmas[0]), float(sigmas[1]), nu, float(half_extent),
+                                          int(seed) & (2 ** 64 - 1), binding.ptr(out), ctx.stream()))
+    return out
+
+
+def sdf_samples(verts, faces, n_surface, seed=0, sigmas=(0.005 ** 0.5, 0.0005 ** 0.5), n_uniform=None, half_extent=1.0):
+    """SDF training samples of a mesh, the input of decode_sdf_train: n_surface area-weighted surface points (sample_surface), each
+    perturbed twice (standard deviations `sigmas`), plus n_uniform points uniform in [-half_extent, half_extent)^3 (default
+    n_surface // 10), all with their signed distance. Returns {'pos': (Np, 4), 'neg': (Nn, 4)} float32 on the mesh's device, rows
+    (x, y, z, sdf), split by sign (pos: sdf >= 0) in query order; Np + Nn = 2 * n_surface + n_uniform less the queries whose distance
+    is NaN (none for a mesh with finite vertices). The defaults follow the recipe DeepSDF published for its preprocessing (variances
+    0.005 and 0.0005 in the unit sphere); they are parameters, and nothing here reproduces that program's samples."""
+    n_surface = int(n_surface)
+    if n_uniform is None:
+        n_uniform = n_surface // 10
+    pts, _ = sample_surface(verts, faces, n_surface, seed=seed)
+    q = sdf_queries(pts, sigmas, n_uniform, half_extent, seed)
+    sdf = signed_distance(verts, faces, q)
+    rows = torch.cat([q, sdf[:, None]], 1)
+    return {'pos': rows[sdf >= 0], 'neg': rows[sdf < 0]}
+
+
+def write_sdf_npz(fname, samples):
+    """DeepSDF's sample file: an npz with float32 arrays 'pos' and 'neg' of rows (x, y, z, sdf)."""
+    arrs = {k: np.ascontiguousarray(samples[k].detach().cpu().numpy() if torch.is_tensor(samples[k]) else samples[k], dtype=np.float32).reshape(-1, 4)
+            for k in ('pos', 'neg')}
+    with open(fname, 'wb') as out:
+        np.savez(out, **arrs)
+
+
+def read_sdf_npz(fname):
+    """{'pos': (Np, 4), 'neg': (Nn, 4)} float32 numpy arrays of a file written by write_sdf_npz (or by DeepSDF's preprocessing)."""
+    with np.load(fname) as z:
+        return {k: np.ascontiguousarray(z[k], dtype=np.float32).reshape(-1, 4) for k in ('pos', 'neg')}
+
+
+def normalize_to_unit_sphere(verts, buffer=1.03):
+    """(verts', offset, scale) with verts' = (verts + offset) * scale: the bounding box's centre moved to the origin and the farthest
+    vertex to radius 1 / buffer. offset (3,) and scale are float64; the convention is the one the reference's loaders apply to cameras
+    and depth maps with normalization_params['offset'] / ['scale']. verts' is float32, a tensor on the input's device for a tensor."""
+    v = verts.detach().cpu().numpy() if torch.is_tensor(verts) else np.asarray(verts)
+    v = v.reshape(-1, 3)
+    if len(v) == 0:
+        raise ValueError('normalize_to_unit_sphere: no vertices')
+    v64 = v.astype(np.float64)
+    offset = -(v.max(0).astype(np.float64) + v.min(0).astype(np.float64)) / 2
+    r = np.sqrt(((v64 + offset) ** 2).sum(1).max())
+    if not np.isfinite(r) or r == 0:
+        raise ValueError('normalize_to_unit_sphere: vertices that are not finite, or a single point')
+    scale = 1.0 / (r * float(buffer))
+    out = ((v64 + offset) * scale).astype(np.float32)
+    if torch.is_tensor(verts):
+        out = torch.from_numpy(out).to(verts.device)
+    return out, offset, scale
 
 
 # --------------------------------------------------------------------------------------------------------------------------- PLY

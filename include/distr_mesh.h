@@ -1,7 +1,8 @@
 /*
  * distr_mesh.h -- C ABI of libdistr.so, part 2: shape evaluation (marching cubes, surface sampling, nearest-point distances for the
  * chamfer distance). Included by distr.h; the reference's counterpart is core/evaluation/ (create_mesh.py's marching cubes through
- * scikit-image, transforms.py's trimesh sampling, eval_func.py's scipy KD-tree chamfer).
+ * scikit-image, transforms.py's trimesh sampling, eval_func.py's scipy KD-tree chamfer). At the end, without a counterpart there:
+ * signed distances to a triangle mesh and DeepSDF-style query points, the SDF samples a decoder is trained on.
  *
  * Same conventions as distr.h: caller-owned device buffers and workspaces, everything enqueued on `stream`, DISTR_OK or a negative
  * code with text in distr_last_error. These need a context (its device) but no decoder. Only distr_mc_count synchronises the stream:
@@ -52,6 +53,27 @@ int distr_sample_surface(distr_ctx* ctx, const float* verts_dev, int64_t nverts,
 size_t distr_nearest_workspace_bytes(int64_t na);
 int distr_nearest_sqdist(distr_ctx* ctx, const float* a_dev, int64_t na, const float* b_dev, int64_t nb, float* d2_dev,
                          double* sums_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* Signed distance of q_dev[nq][3] to the triangles faces_dev[nfaces][3] of verts_dev[nverts][3], brute force over all pairs:
+ * sdf_dev[i] = (|w_i| > 0.5 ? -1 : +1) * sqrtf(d2_i), d2_i = the smallest float32 squared distance to the closest point of a triangle
+ * (Ericson's seven regions; the operation order is spelled out in csrc/distr_mesh.hpp), w_i = the generalised winding number (sum of
+ * the triangles' signed solid angles / 4 pi: +1 inside a closed mesh whose normals point outwards, as distr_mc_emit winds them, 0
+ * outside; |w| so that an inward-wound mesh gives the same signs). Optional outputs (NULL: not written): d2_dev[nq], winding_dev[nq]
+ * (float32), face_dev[nq] = the nearest triangle, the lowest index among equal distances.
+ * A triangle is skipped -- no distance, no solid angle -- when it names a vertex outside [0, nverts), has a coordinate that is not
+ * finite, or its float32 cross product (b - a) x (c - a) is exactly zero. No triangle left: sdf = +inf, face = -1. A query with a
+ * coordinate that is not finite: sdf = d2 = winding = NaN, face = -1. nfaces < 1: DISTR_ERR_INVALID_ARG.
+ * The row of a query does not depend on the other queries of the call: triangles are summed in chunks of a fixed 1024. */
+size_t distr_mesh_sdf_workspace_bytes(int64_t nq, int64_t nfaces);
+int distr_mesh_sdf(distr_ctx* ctx, const float* verts_dev, int64_t nverts, const int32_t* faces_dev, int64_t nfaces, const float* q_dev,
+                   int64_t nq, float* sdf_dev, float* d2_dev, float* winding_dev, int32_t* face_dev, void* ws_dev, size_t ws_bytes,
+                   void* stream);
+/* DeepSDF-style query points from ns surface points surf_dev[ns][3] (distr_sample_surface): q_out_dev[2 * ns + n_uniform][3], rows
+ * 2 i and 2 i + 1 = surface point i plus sigma_a resp. sigma_b times three standard normals each (Box-Muller), rows 2 * ns + j uniform
+ * in [-half_extent, half_extent)^3. Counter-based like the sampler (slot k = 3 of its generator, which the sampler never draws):
+ * every row is a function of (seed, its index) alone. */
+int distr_sdf_queries(distr_ctx* ctx, const float* surf_dev, int64_t ns, float sigma_a, float sigma_b, int64_t n_uniform,
+                      float half_extent, uint64_t seed, float* q_out_dev, void* stream);
 
 #ifdef __cplusplus
 }
