@@ -323,6 +323,25 @@ class SDFRenderer(object):
             return depth, normal, mask.reshape(h, w), min_sdf.reshape(h, w), inside.reshape(h, w, num_forward_sampling)
         return depth, normal, mask.reshape(h, w), min_sdf.reshape(h, w)
 
+    def render_mesh(self, verts, faces, R, T, normal_frame='image', details=False):
+        """Depth, normal and mask maps of a triangle mesh seen by this renderer's camera (no counterpart in the reference, which loads
+        such maps from files its Blender pipeline wrote): distr.mesh.render_mesh with the renderer's own intrinsic, img_hw and
+        transform matrix, so a mesh render and an SDF render of the same object cannot disagree about the camera. R (3, 3) / T (3)
+        -> (depth (H, W), normal (H, W, 3), mask (H, W) uint8) like the first three results of render; R (B, 3, 3) / T (B, 3) -> a
+        leading B. normal_frame='image': the convention of render's normals; 'world': what SDFRenderer_deepsdf.get_samples takes.
+        details=True: also (zdepth, face, bary). The maps are observations: nothing here is differentiable."""
+        from distr import mesh
+        dev = self.calib_map.device
+        R = torch.as_tensor(R).detach().to(device=dev, dtype=torch.float32)
+        T = torch.as_tensor(T).detach().to(device=dev, dtype=torch.float32)
+        if tuple(R.shape[-2:]) != (3, 3) or R.dim() not in (2, 3) or tuple(T.shape) != tuple(R.shape[:-2]) + (3,):
+            raise ValueError('render_mesh: R has shape %s and T %s; (3, 3) and (3,), or (B, 3, 3) and (B, 3)' % (tuple(R.shape), tuple(T.shape)))
+        RT = torch.cat([R, T.unsqueeze(-1)], -1)
+        if not torch.is_tensor(verts) or not verts.is_cuda:
+            verts = mesh._cuda(verts, torch.float32, dev)
+        return mesh.render_mesh(verts, faces, self.intrinsic, RT, self.img_hw, transform_matrix=self._M_np, normal_frame=normal_frame,
+                                details=details)
+
     # reference: renderer.py:912
     def forward_sampling(self, latent, R, T, Zdepth, valid_mask, clamp_dist=0.1, num_forward_sampling=1, no_grad=False,
                          use_transform=True):

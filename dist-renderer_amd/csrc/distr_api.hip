@@ -2214,6 +2214,54 @@ int distr_sdf_queries(distr_ctx* ctx, const float* surf, int64_t ns, float sigma
   return DISTR_OK;
 }
 
+size_t distr_mesh_render_workspace_bytes(int32_t H, int32_t W, int32_t nviews) {
+  if (H < 1 || W < 1 || nviews < 1 || nviews > DISTR_MAX_VIEWS || (int64_t)H * W * nviews > INT32_MAX) return 0;
+  WsCarve c(nullptr);
+  c.take<unsigned long long>((size_t)H * W * nviews);
+  return c.bytes();
+}
+
+int distr_mesh_render(distr_ctx* ctx, const distr_mesh_render_cfg* cfg, const float* verts, int64_t nverts, const int32_t* faces,
+                      int64_t nfaces, int32_t nviews, const float* RT, float* depth, float* zdepth, float* normal, uint8_t* mask,
+                      int32_t* face, float* bary, void* ws, size_t ws_bytes, void* stream) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  if (!cfg) return fail(ctx, DISTR_ERR_INVALID_ARG, "null mesh render cfg");
+  if (cfg->struct_size != sizeof(distr_mesh_render_cfg))
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_mesh_render_cfg.struct_size %u: this library expects %zu (set it with DISTR_INIT)", cfg->struct_size, sizeof(distr_mesh_render_cfg));
+  if (nviews < 1 || nviews > DISTR_MAX_VIEWS) return fail(ctx, DISTR_ERR_INVALID_ARG, "nviews %d not in [1, %d]", nviews, DISTR_MAX_VIEWS);
+  if (cfg->H < 1 || cfg->W < 1 || (int64_t)cfg->H * cfg->W * nviews > INT32_MAX)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "image size %d x %d, %d views: need H * W * nviews < 2^31", cfg->H, cfg->W, nviews);
+  if (cfg->normal_frame != DISTR_MESH_NORMAL_WORLD && cfg->normal_frame != DISTR_MESH_NORMAL_IMAGE)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "normal_frame %d", cfg->normal_frame);
+  const int64_t nchunks = (nfaces + mesh::RC_CHUNK - 1) / mesh::RC_CHUNK;
+  if (nverts < 1 || nfaces < 1 || nfaces > INT32_MAX || nchunks > 65535)
+    return fail(ctx, DISTR_ERR_INVALID_ARG, "mesh render needs a mesh with vertices and 1 .. %d triangles (%lld, %lld)", 65535 * mesh::RC_CHUNK,
+                (long long)nverts, (long long)nfaces);
+  if (!verts || !faces || !RT || !ws) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < distr_mesh_render_workspace_bytes(cfg->H, cfg->W, nviews)) return fail(ctx, DISTR_ERR_WORKSPACE, "mesh render workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  mesh::CastGeo G;
+  G.H = cfg->H; G.W = cfg->W; G.P = cfg->H * cfg->W;
+  for (int i = 0; i < 9; ++i) { G.Ki[i] = cfg->K_inv[i]; G.M[i] = cfg->M[i]; }
+  G.frame = cfg->normal_frame;
+  WsCarve c(ws);
+  const long long n = (long long)G.P * nviews;
+  unsigned long long* best = c.take<unsigned long long>(n);
+  const mesh::SurfMesh m{verts, nverts, faces, nfaces};
+  const int per = mesh::MB * mesh::RC_PPT;
+  hipLaunchKernelGGL(mesh::k_sdf_init, dim3((unsigned)((n + mesh::MB - 1) / mesh::MB)), dim3(mesh::MB), 0, s, best, n);
+  LAUNCH_CHECK("k_sdf_init");
+  hipLaunchKernelGGL(mesh::k_mesh_cast, dim3((unsigned)((G.P + per - 1) / per), (unsigned)nchunks, (unsigned)nviews), dim3(mesh::MB), 0, s, m, G,
+                     RT, best);
+  LAUNCH_CHECK("k_mesh_cast");
+  const mesh::CastOut o{depth, zdepth, normal, mask, face, bary};
+  hipLaunchKernelGGL(mesh::k_mesh_finish, dim3((unsigned)((G.P + mesh::MB - 1) / mesh::MB), (unsigned)nviews), dim3(mesh::MB), 0, s, m, G, RT,
+                     (const unsigned long long*)best, o);
+  LAUNCH_CHECK("k_mesh_finish");
+  return DISTR_OK;
+}
+
 }  // extern "C"
 
 // ---- depth maps back-projected into SDF samples (include/distr_samples.h, kernels: distr_samples.hpp)

@@ -6,6 +6,8 @@
 // and the way back from a mesh to training data (no counterpart in the reference, which loads preprocessed files; at the end of the file):
 //   signed distance    brute force exact point-to-triangle distance, signed by the generalised winding number
 //   query points       DeepSDF-style: surface samples perturbed at two scales plus uniform points, from the sampler's generator
+// and from a mesh to images (the reference loads them from a Blender pipeline's files; at the very end):
+//   depth / normal / mask maps   brute force ray-triangle intersection in the renderer's camera convention, watertight in float32
 //
 // No MFMA: scans and VALU loops. Every output position comes from an exclusive scan in a fixed order (per-thread serial run of
 // MTILE / MB items -> LDS scan over the block -> one ordered pass over the block totals), never from an atomic, so every output is
@@ -26,7 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "distr_mlp.hpp"        // DISTR_GLOBAL
+#include "distr_kernels.hpp"    // DISTR_GLOBAL (distr_mlp.hpp), make_ray
 
 namespace distr {
 namespace mesh {
@@ -665,6 +667,28 @@ constexpr unsigned long long SDF_NONE = 0x7f800000ffffffffull;     // (+inf, fac
 __device__ __forceinline__ float dot3(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
 __device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+__device__ __forceinline__ void cross3(const float* p, const float* q, float* r) {
+  r[0] = p[1] * q[2] - p[2] * q[1];
+  r[1] = p[2] * q[0] - p[0] * q[2];
+  r[2] = p[0] * q[1] - p[1] * q[0];
+}
+
+// the skip rule (above) of k_sdf_pairs, and of k_mesh_cast further down: is face f counted
+__device__ __forceinline__ bool face_counted(const SurfMesh m, long long f) {
+  if (!face_ok(m, f)) return false;
+  const int* fi = m.faces + 3 * f;
+  const float* a = m.verts + 3 * (long long)fi[0];
+  const float* b = m.verts + 3 * (long long)fi[1];
+  const float* c = m.verts + 3 * (long long)fi[2];
+  const float ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  float n[3];
+  cross3(ab, ac, n);
+  bool fin = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) fin = fin && finite_f(a[i]) && finite_f(b[i]) && finite_f(c[i]);
+  return fin && !(n[0] == 0.f && n[1] == 0.f && n[2] == 0.f);
+}
+
 DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_init(unsigned long long* __restrict__ best, long long n) {
   const long long i = (long long)blockIdx.x * MB + threadIdx.x;
   if (i < n) best[i] = SDF_NONE;
@@ -687,22 +711,14 @@ DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_pairs(const SurfMesh m, const floa
     if ((int)threadIdx.x < cnt) {
       const long long f = t0 + threadIdx.x;
       float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-      if (face_ok(m, f)) {
+      if (face_counted(m, f)) {
         const int* fi = m.faces + 3 * f;
         const float* a = m.verts + 3 * (long long)fi[0];
         const float* b = m.verts + 3 * (long long)fi[1];
         const float* c = m.verts + 3 * (long long)fi[2];
-        const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2], cx = c[0], cy = c[1], cz = c[2];
-        const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
-        const float nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
-        const bool fin = finite_f(ax) && finite_f(ay) && finite_f(az) && finite_f(bx) && finite_f(by) && finite_f(bz) && finite_f(cx) &&
-                         finite_f(cy) && finite_f(cz);
-        const bool ok = fin && !(nx == 0.f && ny == 0.f && nz == 0.f);
-        if (ok) {
-          r0 = make_float4(ax, ay, az, abx);
-          r1 = make_float4(aby, abz, acx, acy);
-          r2 = make_float4(acz, 1.f, 0.f, 0.f);
-        }
+        r0 = make_float4(a[0], a[1], a[2], b[0] - a[0]);
+        r1 = make_float4(b[1] - a[1], b[2] - a[2], c[0] - a[0], c[1] - a[1]);
+        r2 = make_float4(c[2] - a[2], 1.f, 0.f, 0.f);
       }
       tile[0][threadIdx.x] = r0;
       tile[1][threadIdx.x] = r1;
@@ -819,6 +835,217 @@ DISTR_GLOBAL void __launch_bounds__(MB) k_sdf_queries(const float* __restrict__ 
     d[1] = (2.f * ((float)((unsigned)(w0 >> 8) & 0xffffffu) * 0x1.0p-24f) - 1.f) * h;
     d[2] = (2.f * ((float)(unsigned)(w1 >> 40) * 0x1.0p-24f) - 1.f) * h;
   }
+}
+
+// ------------------------------------------------------------------------------------------ depth, normal and mask maps of a mesh
+// k_mesh_cast: rays of up to DISTR_MAX_VIEWS pinhole views against every triangle, brute force over all (ray, triangle) pairs; the
+// nearest hit per pixel as the key (bits(t) << 32) | face in best[view][pixel]. k_mesh_finish decodes the key and writes the maps.
+// Not differentiable: the maps are observations (the depth / normal arguments of get_samples, the targets of the image losses).
+//
+// All rays of a view start at the camera, so the work happens in the mesh's frame with the camera at the origin. Everything is
+// float32, no fused multiply-add (-ffp-contract=off), IEEE division and square root; sums run left to right where no brackets are
+// written; dot(u, v) is (ux*vx + uy*vy) + uz*vz and cross(p, q) = (py*qz - pz*qy, pz*qx - px*qz, px*qy - py*qx).
+//
+// Per view (RT = [R | T], row-major 3 x 4; the order of k_prep and make_point):
+//   c[i] = -(R[0][i]*T[0] + R[1][i]*T[1] + R[2][i]*T[2]),   o[i] = M[0][i]*c[0] + M[1][i]*c[1] + M[2][i]*c[2]        (o = M^T c)
+// Per pixel (x, y) = (pix % W, pix / W) as floats: d and calib of make_ray(K_inv, R, x, y);
+//   e[i] = M[0][i]*d[0] + M[1][i]*d[1] + M[2][i]*d[2]                                                                 (e = M^T d)
+// Per triangle (a, b, c) and view: A = a - o, B = b - o, C = c - o;  Na = cross(C, B), Nb = cross(A, C), Nc = cross(B, A).
+// Per pair: U = dot(e, Na), V = dot(e, Nb), W = dot(e, Nc). The two triangles of an indexed mesh that share an edge get edge
+// functions that are exact negatives of each other (products commute, p*q - r*s = -(r*s - p*q)), so a ray never passes between them.
+// The pair is a HIT when
+//   not ((U < 0 or V < 0 or W < 0) and (U > 0 or V > 0 or W > 0))          zeros are inclusive
+//   det = (U + V) + W != 0
+//   t = dot(A, Ng) / dot(e, Ng) is finite and > 0, with E1 = B - A, E2 = C - A, Ng = cross(E1, E2)   (computed on such a pair only)
+// The nearest hit wins, the lowest face among equal t: t > 0, so the order of the keys is the order of (t, face); a thread keeps the
+// smallest key of its chunk, the chunks (blockIdx.y, RC_CHUNK faces, a compile-time constant) meet in the integer atomicMin of
+// k_sdf_pairs. The result depends neither on the arrival order nor on the chunking. No float atomic: the same bytes on every run.
+// Outputs of a hit (k_mesh_finish recomputes A .. Ng of the winning face with the same operations):
+//   zdepth = t,  depth = t * calib,  bary = (V / det, W / det) (the weights of b and c),  face,  mask = 1
+//   n = (dot(e, Ng) > 0 ? -Ng : Ng) / sqrtf(dot(Ng, Ng)) + 0                (towards the camera whatever the winding; + 0 turns a
+//                                                                            -0 component into +0, so both windings give the same bytes)
+//   world:  w[i] = M[i][0]*n[0] + M[i][1]*n[1] + M[i][2]*n[2]               (M n; get_samples multiplies by M^T itself)
+//   image:  r[i] = R[i][0]*w[0] + R[i][1]*w[1] + R[i][2]*w[2], r[0] = -r[0] (render's autograd normals: R (M n), x negated)
+// A miss: depth = zdepth = 1e11, normal = bary = 0, face = -1, mask = 0.
+// A face is SKIPPED by the rule of k_sdf_pairs (a vertex outside [0, nv), a coordinate that is not finite, a float32 cross product
+// (b - a) x (c - a) of exactly zero); a view whose RT holds a number that is not finite skips every face: all misses.
+//
+// Layout: a thread owns RC_PPT pixels (blockIdx.x * MB * RC_PPT + q * MB + threadIdx.x: every record read from LDS serves RC_PPT
+// edge tests); blockIdx.z = the view. The staging thread forms the record (Na, Nb, Nc, counted: three float4) of its face from the
+// vertices and the view's o, so there is no record workspace; every lane reads the same record, a broadcast.
+constexpr int RC_TILE = 256;       // face records per LDS tile (12 KB)
+constexpr int RC_CHUNK = 1024;     // faces per blockIdx.y (distr.mesh.RENDER_CHUNK mirrors it)
+constexpr int RC_PPT = 2;          // pixels per thread
+constexpr int FRAME_WORLD = 0, FRAME_IMAGE = 1;     // DISTR_MESH_NORMAL_*
+
+struct CastGeo {                   // per call
+  int H, W, P;                     // P = H * W
+  float Ki[9], M[9];
+  int frame;
+};
+struct CastCam { float R[9], o[3]; bool ok; };
+struct CastOut { float* depth; float* zdepth; float* normal; uint8_t* mask; int* face; float* bary; };     // [view][pixel]; any may be null
+
+__device__ __forceinline__ CastCam cast_cam(const CastGeo& G, const float* __restrict__ RT) {
+  CastCam k;
+  float T[3], c[3];
+  k.ok = true;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { k.R[j * 3 + i] = RT[j * 4 + i]; k.ok = k.ok && finite_f(k.R[j * 3 + i]); }
+    T[j] = RT[j * 4 + 3];
+    k.ok = k.ok && finite_f(T[j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) c[i] = -(k.R[0 * 3 + i] * T[0] + k.R[1 * 3 + i] * T[1] + k.R[2 * 3 + i] * T[2]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) k.o[i] = G.M[0 * 3 + i] * c[0] + G.M[1 * 3 + i] * c[1] + G.M[2 * 3 + i] * c[2];
+  return k;
+}
+
+// e = M^T d of pixel pix; returns calib
+__device__ __forceinline__ float cast_ray(const CastGeo& G, const CastCam& cam, int pix, float* e) {
+  const RayGeo g = make_ray(G.Ki, cam.R, (float)(pix % G.W), (float)(pix / G.W));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e[i] = G.M[0 * 3 + i] * g.d[0] + G.M[1 * 3 + i] * g.d[1] + G.M[2 * 3 + i] * g.d[2];
+  return g.calib;
+}
+
+// corners of a counted face relative to the camera
+__device__ __forceinline__ void face_rel(const SurfMesh m, long long f, const float* o, float* A, float* B, float* C) {
+  const int* fi = m.faces + 3 * f;
+  const float* a = m.verts + 3 * (long long)fi[0];
+  const float* b = m.verts + 3 * (long long)fi[1];
+  const float* c = m.verts + 3 * (long long)fi[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { A[i] = a[i] - o[i]; B[i] = b[i] - o[i]; C[i] = c[i] - o[i]; }
+}
+
+// t of a pair whose edge functions agree in sign; Ng and den = dot(e, Ng) on the way
+__device__ __forceinline__ float face_t(const float* A, const float* B, const float* C, const float* e, float* Ng, float* den) {
+  const float E1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, E2[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  cross3(E1, E2, Ng);
+  *den = dot3(e[0], e[1], e[2], Ng[0], Ng[1], Ng[2]);
+  return dot3(A[0], A[1], A[2], Ng[0], Ng[1], Ng[2]) / *den;
+}
+
+__device__ __forceinline__ bool signs_mixed(float U, float V, float W) {
+  return (U < 0.f || V < 0.f || W < 0.f) && (U > 0.f || V > 0.f || W > 0.f);
+}
+
+// grid (blocks of MB * RC_PPT pixels, chunks of RC_CHUNK faces, views); best[view][pixel] preset to SDF_NONE (k_sdf_init)
+DISTR_GLOBAL void __launch_bounds__(MB) k_mesh_cast(const SurfMesh m, const CastGeo G, const float* __restrict__ RT,
+                                                    unsigned long long* __restrict__ best) {
+  __shared__ float4 tile[3][RC_TILE];      // [0] Na.xyz, Nb.x   [1] Nb.yz, Nc.xy   [2] Nc.z, flag (1 counted, 0 skipped), -, -
+  const int v = blockIdx.z;
+  const CastCam cam = cast_cam(G, RT + 12 * v);
+  const long long i0 = (long long)blockIdx.x * (MB * RC_PPT) + threadIdx.x;
+  float e[RC_PPT][3];
+  unsigned long long bk[RC_PPT];
+#pragma unroll
+  for (int q = 0; q < RC_PPT; ++q) {
+    const long long i = i0 + q * MB;
+    cast_ray(G, cam, i < G.P ? (int)i : 0, e[q]);               // a lane beyond the image casts pixel 0's ray and writes nothing
+    bk[q] = SDF_NONE;
+  }
+  const long long f0 = (long long)blockIdx.y * RC_CHUNK, f1 = f0 + RC_CHUNK < m.nf ? f0 + RC_CHUNK : m.nf;
+  for (long long t0 = f0; t0 < f1; t0 += RC_TILE) {
+    const int cnt = (int)(f1 - t0 < RC_TILE ? f1 - t0 : RC_TILE);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const long long f = t0 + threadIdx.x;
+      float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
+      if (cam.ok && face_counted(m, f)) {
+        float A[3], B[3], C[3], Na[3], Nb[3], Nc[3];
+        face_rel(m, f, cam.o, A, B, C);
+        cross3(C, B, Na);
+        cross3(A, C, Nb);
+        cross3(B, A, Nc);
+        r0 = make_float4(Na[0], Na[1], Na[2], Nb[0]);
+        r1 = make_float4(Nb[1], Nb[2], Nc[0], Nc[1]);
+        r2 = make_float4(Nc[2], 1.f, 0.f, 0.f);
+      }
+      tile[0][threadIdx.x] = r0;
+      tile[1][threadIdx.x] = r1;
+      tile[2][threadIdx.x] = r2;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k = 0; k < cnt; ++k) {
+      const float4 r2 = tile[2][k];
+      if (r2.y == 0.f) continue;                                 // a skipped face (the same for every lane)
+      const float4 r0 = tile[0][k], r1 = tile[1][k];
+#pragma unroll
+      for (int q = 0; q < RC_PPT; ++q) {
+        const float U = dot3(e[q][0], e[q][1], e[q][2], r0.x, r0.y, r0.z);
+        const float V = dot3(e[q][0], e[q][1], e[q][2], r0.w, r1.x, r1.y);
+        const float W = dot3(e[q][0], e[q][1], e[q][2], r1.z, r1.w, r2.x);
+        if (signs_mixed(U, V, W) || (U + V) + W == 0.f) continue;
+        float A[3], B[3], C[3], Ng[3], den;                      // rare: a few faces per ray
+        face_rel(m, t0 + k, cam.o, A, B, C);
+        const float t = face_t(A, B, C, e[q], Ng, &den);
+        if (!(finite_f(t) && t > 0.f)) continue;
+        const unsigned long long key = (unsigned long long)__float_as_uint(t) << 32 | (unsigned)(t0 + k);
+        if (key < bk[q]) bk[q] = key;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < RC_PPT; ++q) {
+    const long long i = i0 + q * MB;
+    if (i < G.P && bk[q] != SDF_NONE) atomicMin(best + (long long)v * G.P + i, bk[q]);
+  }
+}
+
+// grid (blocks of MB pixels, views)
+DISTR_GLOBAL void __launch_bounds__(MB) k_mesh_finish(const SurfMesh m, const CastGeo G, const float* __restrict__ RT,
+                                                      const unsigned long long* __restrict__ best, const CastOut O) {
+  const int i = blockIdx.x * MB + threadIdx.x, v = blockIdx.y;
+  if (i >= G.P) return;
+  const long long at = (long long)v * G.P + i;
+  const unsigned long long key = best[at];
+  float depth = 1e11f, z = 1e11f, n[3] = {0.f, 0.f, 0.f}, bu = 0.f, bv = 0.f;
+  int f = -1;
+  if (key != SDF_NONE) {
+    f = (int)(unsigned)(key & 0xffffffffu);
+    const CastCam cam = cast_cam(G, RT + 12 * v);
+    float e[3], A[3], B[3], C[3], Nb[3], Nc[3], Ng[3], den;
+    const float calib = cast_ray(G, cam, i, e);
+    face_rel(m, f, cam.o, A, B, C);
+    float Na[3];
+    cross3(C, B, Na);
+    cross3(A, C, Nb);
+    cross3(B, A, Nc);
+    const float U = dot3(e[0], e[1], e[2], Na[0], Na[1], Na[2]);
+    const float V = dot3(e[0], e[1], e[2], Nb[0], Nb[1], Nb[2]);
+    const float W = dot3(e[0], e[1], e[2], Nc[0], Nc[1], Nc[2]);
+    const float det = (U + V) + W;
+    z = face_t(A, B, C, e, Ng, &den);                            // the bits of the key
+    depth = z * calib;
+    bu = V / det;
+    bv = W / det;
+    const float len = sqrtf(dot3(Ng[0], Ng[1], Ng[2], Ng[0], Ng[1], Ng[2]));
+    float g[3], w[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[k] = (den > 0.f ? -Ng[k] : Ng[k]) / len + 0.f;          // + 0: a zero component is +0 for either winding
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = G.M[k * 3 + 0] * g[0] + G.M[k * 3 + 1] * g[1] + G.M[k * 3 + 2] * g[2];
+    if (G.frame == FRAME_IMAGE) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) n[k] = cam.R[k * 3 + 0] * w[0] + cam.R[k * 3 + 1] * w[1] + cam.R[k * 3 + 2] * w[2];
+      n[0] = -n[0];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) n[k] = w[k];
+    }
+  }
+  if (O.depth) O.depth[at] = depth;
+  if (O.zdepth) O.zdepth[at] = z;
+  if (O.normal) { O.normal[3 * at] = n[0]; O.normal[3 * at + 1] = n[1]; O.normal[3 * at + 2] = n[2]; }
+  if (O.mask) O.mask[at] = f >= 0 ? 1 : 0;
+  if (O.face) O.face[at] = f;
+  if (O.bary) { O.bary[2 * at] = bu; O.bary[2 * at + 1] = bv; }
 }
 
 }  // namespace mesh

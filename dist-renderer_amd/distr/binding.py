@@ -29,7 +29,9 @@ EXPORTS = ['distr_version', 'distr_abi_version', 'distr_create_abi', 'distr_dest
 MESH_EXPORTS = ['distr_mc_workspace_bytes', 'distr_mc_count', 'distr_mc_emit', 'distr_sample_workspace_bytes', 'distr_sample_surface',
                 'distr_nearest_workspace_bytes', 'distr_nearest_sqdist',
                 # signed distances to a mesh and DeepSDF-style query points: SDF training samples
-                'distr_mesh_sdf_workspace_bytes', 'distr_mesh_sdf', 'distr_sdf_queries']
+                'distr_mesh_sdf_workspace_bytes', 'distr_mesh_sdf', 'distr_sdf_queries',
+                # depth, normal and mask maps of a mesh in the renderer's camera convention
+                'distr_mesh_render_workspace_bytes', 'distr_mesh_render']
 # depth maps back-projected into SDF samples (include/distr_samples.h, included by distr.h): SDFRenderer_deepsdf
 SAMPLES_EXPORTS = ['distr_depth_samples_workspace_bytes', 'distr_depth_samples_count', 'distr_depth_samples_forward',
                    'distr_depth_samples_backward']
@@ -129,6 +131,25 @@ class ColorLights(_Sized):
 class SamplesCfg(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K_inv', C.c_float * 9), ('M', C.c_float * 9),
                 ('clamp_dist', C.c_float), ('mode', C.c_int32), ('number', C.c_int32)]
+
+
+class MeshRenderCfg(_Sized):
+    """distr_mesh_render_cfg (include/distr_mesh.h)."""
+    _fields_ = [('struct_size', C.c_uint32), ('H', C.c_int32), ('W', C.c_int32), ('K_inv', C.c_float * 9), ('M', C.c_float * 9),
+                ('normal_frame', C.c_int32)]
+
+
+MESH_NORMAL_FRAMES = {'world': 0, 'image': 1}       # DISTR_MESH_NORMAL_*
+
+
+def make_mesh_render_cfg(img_hw, intrinsic, transform_matrix, normal_frame):
+    """distr_mesh_render_cfg of one render_mesh call; K_inv and M exactly as make_cfg hands them to the march."""
+    cfg = MeshRenderCfg()
+    cfg.H, cfg.W = int(img_hw[0]), int(img_hw[1])
+    cfg.K_inv = (C.c_float * 9)(*np.linalg.inv(np.asarray(intrinsic, dtype=np.float64)).astype(np.float32).reshape(-1))
+    cfg.M = (C.c_float * 9)(*np.asarray(transform_matrix, dtype=np.float32).reshape(-1))
+    cfg.normal_frame = MESH_NORMAL_FRAMES[normal_frame]
+    return cfg
 
 
 def make_samples_cfg(img_hw, intrinsic, transform_matrix, clamp_dist, mode, number=1):
@@ -402,6 +423,9 @@ def lib():
             L.distr_mesh_sdf_workspace_bytes.restype = C.c_size_t
             L.distr_mesh_sdf.argtypes = [vp, fp, i64, vp, i64, fp, i64, fp, fp, fp, vp, vp, C.c_size_t, vp]
             L.distr_sdf_queries.argtypes = [vp, fp, i64, C.c_float, C.c_float, i64, C.c_float, C.c_uint64, fp, vp]
+            L.distr_mesh_render_workspace_bytes.argtypes = [i32, i32, i32]
+            L.distr_mesh_render_workspace_bytes.restype = C.c_size_t
+            L.distr_mesh_render.argtypes = [vp, C.POINTER(MeshRenderCfg), fp, i64, vp, i64, i32, fp, fp, fp, fp, u8p, vp, fp, vp, C.c_size_t, vp]
             szp, scfg = C.POINTER(C.c_size_t), C.POINTER(SamplesCfg)
             L.distr_depth_samples_workspace_bytes.argtypes = [vp, scfg, i32, i64p, szp, szp, szp]
             L.distr_depth_samples_count.argtypes = [vp, scfg, i32, fp, vp, i64p, vp, C.c_size_t, vp]

@@ -1,6 +1,7 @@
 """Shape evaluation on the MI355X (include/distr_mesh.h, csrc/distr_mesh.hpp): marching cubes, area-weighted surface sampling,
 nearest-point distances and the chamfer distance, plus a plain-numpy PLY writer / reader; and the way back from a mesh to training
-data: signed distances to a triangle mesh and DeepSDF-style SDF samples (signed_distance, sdf_samples, the pos / neg npz layout).
+data: signed distances to a triangle mesh and DeepSDF-style SDF samples (signed_distance, sdf_samples, the pos / neg npz layout); and
+from a mesh to images: depth, normal and mask maps in the renderer's camera convention (render_mesh).
 
 What the reference does on the host with scikit-image (marching_cubes_lewiner), plyfile, trimesh (sample_surface) and two scipy
 KD-trees (core/evaluation/create_mesh.py, transforms.py, eval_func.py). No third-party package beyond torch and numpy; no CPU path:
@@ -205,6 +206,75 @@ def sdf_samples(verts, faces, n_surface, seed=0, sigmas=(0.005 ** 0.5, 0.0005 **
     sdf = signed_distance(verts, faces, q)
     rows = torch.cat([q, sdf[:, None]], 1)
     return {'pos': rows[sdf >= 0], 'neg': rows[sdf < 0]}
+
+
+# ------------------------------------------------------------------------------------------------- images of a mesh
+RENDER_TILE = 256                 # face records per LDS tile of distr_mesh_render (RC_TILE of csrc/distr_mesh.hpp)
+RENDER_CHUNK = 1024               # faces per chunk (RC_CHUNK): the chunks' nearest hits meet in an integer atomic min
+RENDER_BLOCK = 512                # pixels per block of k_mesh_cast (MB * RC_PPT)
+_MAX_VIEWS = binding.MAX_VIEWS    # views per distr_mesh_render call; more go in pieces
+
+
+def render_mesh(verts, faces, intrinsic, RT, img_hw, transform_matrix=None, normal_frame='image', details=False):
+    """Depth, normal and mask maps of a triangle mesh in the renderer's camera convention: what SDFRenderer.render returns for a
+    decoder, for a mesh -- a ground-truth shape, a scan, the output of marching_cubes. intrinsic (3, 3), RT (3, 4) = [R | T] or
+    (B, 3, 4) for any B (more than 64 views go in pieces, byte for byte the same), img_hw (H, W), transform_matrix (3, 3) as
+    SDFRenderer's (default: the renderer's [[1, 0, 0], [0, 0, -1], [0, 1, 0]]).
+    Returns (depth float32 (H, W), normal float32 (H, W, 3), mask uint8 (H, W)) on the mesh's device, with a leading B for a batch:
+    depth = ray parameter t times calib_map (render's depth; 1e11 where no triangle is hit), normal = the hit triangle's geometric
+    normal oriented towards the camera whatever the winding (0 for a miss) -- normal_frame='image': R (M n) with x negated, the
+    convention of render's normals; 'world': M n, what SDFRenderer_deepsdf.get_samples expects. details=True: also zdepth (t; 1e11 for a
+    miss), face (int64, -1 for a miss: the lowest index among equally near triangles) and bary (H, W, 2), the weights of the hit
+    triangle's second and third corner.
+    Brute force over all (ray, triangle) pairs in float32 with edge functions that are exact negatives of each other on a shared edge:
+    a closed indexed mesh has no holes along its edges. Not differentiable: the maps are observations. Triangles that name a vertex
+    outside the array, have a coordinate that is not finite or a float32 cross product of exactly zero are skipped; a view whose RT is
+    not finite sees nothing."""
+    v = _cuda(verts, torch.float32)
+    f = _cuda(faces, torch.int32, v.device)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError('render_mesh: verts (V, 3) and faces (F, 3) expected')
+    if f.shape[0] == 0 or v.shape[0] == 0:
+        raise ValueError('render_mesh: the mesh has no triangles')
+    if normal_frame not in binding.MESH_NORMAL_FRAMES:
+        raise ValueError("render_mesh: normal_frame %r: 'image' or 'world'" % (normal_frame,))
+    rt = _cuda(RT, torch.float32, v.device)
+    if tuple(rt.shape) != (3, 4) and (rt.dim() != 3 or tuple(rt.shape[1:]) != (3, 4) or rt.shape[0] == 0):
+        raise ValueError('render_mesh: RT has shape %s; (3, 4) or (B, 3, 4) expected' % (tuple(rt.shape),))
+    single = rt.dim() == 2
+    rt = rt.reshape(-1, 3, 4)
+    if torch.is_tensor(intrinsic):
+        intrinsic = intrinsic.detach().cpu().numpy()
+    if transform_matrix is None:
+        transform_matrix = np.array([[1., 0., 0.], [0., 0., -1.], [0., 1., 0.]])       # SDFRenderer's default
+    elif torch.is_tensor(transform_matrix):
+        transform_matrix = transform_matrix.detach().cpu().numpy()
+    if np.asarray(intrinsic).shape != (3, 3) or np.asarray(transform_matrix).shape != (3, 3):
+        raise ValueError('render_mesh: intrinsic and transform_matrix are (3, 3)')
+    H, W = int(img_hw[0]), int(img_hw[1])
+    if H < 1 or W < 1 or H * W * min(rt.shape[0], _MAX_VIEWS) >= 2 ** 31:
+        raise ValueError('render_mesh: image size %d x %d' % (H, W))
+    cfg = binding.make_mesh_render_cfg((H, W), intrinsic, transform_matrix, normal_frame)
+    B, dev = rt.shape[0], v.device
+    ctx = _context(dev)
+    L = ctx.L
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    normal = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    zdepth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if details else None
+    face = torch.empty((B, H, W), dtype=torch.int32, device=dev) if details else None
+    bary = torch.empty((B, H, W, 2), dtype=torch.float32, device=dev) if details else None
+    ws = _workspace(L.distr_mesh_render_workspace_bytes(H, W, min(B, _MAX_VIEWS)), dev)
+    with torch.cuda.device(dev):
+        s = ctx.stream()
+        for b0 in range(0, B, _MAX_VIEWS):
+            n = min(_MAX_VIEWS, B - b0)
+            ctx.check(L.distr_mesh_render(ctx.h, C.byref(cfg), binding.ptr(v), v.shape[0], binding.ptr(f), f.shape[0], n, binding.ptr(rt[b0:]),
+                                          binding.ptr(depth[b0:]), binding.ptr(zdepth[b0:]) if details else None, binding.ptr(normal[b0:]),
+                                          binding.ptr(mask[b0:]), binding.ptr(face[b0:]) if details else None,
+                                          binding.ptr(bary[b0:]) if details else None, binding.ptr(ws), ws.numel(), s))
+    out = (depth, normal, mask) + ((zdepth, face.long(), bary) if details else ())
+    return tuple(o[0] for o in out) if single else out
 
 
 def write_sdf_npz(fname, samples):

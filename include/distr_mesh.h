@@ -2,7 +2,9 @@
  * distr_mesh.h -- C ABI of libdistr.so, part 2: shape evaluation (marching cubes, surface sampling, nearest-point distances for the
  * chamfer distance). Included by distr.h; the reference's counterpart is core/evaluation/ (create_mesh.py's marching cubes through
  * scikit-image, transforms.py's trimesh sampling, eval_func.py's scipy KD-tree chamfer). At the end, without a counterpart there:
- * signed distances to a triangle mesh and DeepSDF-style query points, the SDF samples a decoder is trained on.
+ * signed distances to a triangle mesh and DeepSDF-style query points, the SDF samples a decoder is trained on; and depth, normal and
+ * mask maps of a triangle mesh in the renderer's camera convention (distr_mesh_render), the observations the image losses and
+ * distr_samples.h consume -- the reference loads them from files its Blender pipeline (synthesis/) wrote.
  *
  * Same conventions as distr.h: caller-owned device buffers and workspaces, everything enqueued on `stream`, DISTR_OK or a negative
  * code with text in distr_last_error. These need a context (its device) but no decoder. Only distr_mc_count synchronises the stream:
@@ -74,6 +76,43 @@ int distr_mesh_sdf(distr_ctx* ctx, const float* verts_dev, int64_t nverts, const
  * every row is a function of (seed, its index) alone. */
 int distr_sdf_queries(distr_ctx* ctx, const float* surf_dev, int64_t ns, float sigma_a, float sigma_b, int64_t n_uniform,
                       float half_extent, uint64_t seed, float* q_out_dev, void* stream);
+
+/* Depth, normal and mask maps of a triangle mesh seen by nviews (1..DISTR_MAX_VIEWS) pinhole cameras of one image size, in the
+ * renderer's camera convention: RT_dev[v] (3, 4) row-major = [R | T], pixel centres at the integer (x, y), camera position
+ * c = -R^T T and ray d exactly as the march forms them, both moved to the mesh's frame with M^T. Brute force over all (ray, triangle)
+ * pairs, float32 throughout; the operation order is spelled out in csrc/distr_mesh.hpp (k_mesh_cast), a numpy float32 restatement
+ * gives the same bits. Not differentiable: the maps are observations.
+ *   Per triangle and view, with the corners relative to the camera (A, B, C): Na = C x B, Nb = A x C, Nc = B x A; per ray e the edge
+ *   functions U = e.Na, V = e.Nb, W = e.Nc. A hit: the signs of U, V, W are not mixed (zeros inclusive), det = (U + V) + W != 0,
+ *   t = (A.Ng) / (e.Ng) finite and > 0 with Ng = (B - A) x (C - A). The edge functions of an edge shared by two triangles of an indexed
+ *   mesh are exact negatives of each other: no ray passes between them. The nearest hit wins, the lowest face among equal t.
+ * Outputs, [nviews][H*W] each, any of them may be NULL:
+ *   zdepth_dev  t                          depth_dev  t * calib (what render returns for a valid pixel); a miss: 1e11 in both
+ *   normal_dev  [..][3] the geometric normal +-Ng / |Ng| oriented towards the camera whatever the winding;
+ *               DISTR_MESH_NORMAL_WORLD: M n (what distr_depth_samples_forward expects: it multiplies by M^T itself),
+ *               DISTR_MESH_NORMAL_IMAGE: R (M n) with its x component negated (render's autograd normals); a miss: 0
+ *   mask_dev    uint8, 1 for a hit         face_dev   int32, the triangle hit, -1 for a miss
+ *   bary_dev    [..][2] = (V / det, W / det), the weights of corners b and c; a miss: 0
+ * Triangles are skipped by the rule of distr_mesh_sdf (a vertex outside [0, nverts), a coordinate that is not finite, a float32 cross
+ * product (b - a) x (c - a) of exactly zero); a view whose RT holds a number that is not finite gives all misses.
+ * Determinism: the per-pixel minimum meets in an integer atomic min on (bits(t) << 32) | face; no float atomic. The same bytes on every
+ * run, and a view's maps do not depend on the other views of the call.
+ * Refused (DISTR_ERR_INVALID_ARG): nfaces < 1, more than 65535 * 1024 triangles, H * W * nviews >= 2^31, a wrong struct_size. */
+#define DISTR_MESH_NORMAL_WORLD 0
+#define DISTR_MESH_NORMAL_IMAGE 1
+
+typedef struct distr_mesh_render_cfg {
+  uint32_t struct_size; /* sizeof(distr_mesh_render_cfg): DISTR_INIT */
+  int32_t H, W;         /* img_hw */
+  float K_inv[9];       /* float32(inv(K)), row-major */
+  float M[9];           /* transform_matrix (3x3): mesh frame -> world, x_world = M x_mesh */
+  int32_t normal_frame; /* DISTR_MESH_NORMAL_* */
+} distr_mesh_render_cfg;
+
+size_t distr_mesh_render_workspace_bytes(int32_t H, int32_t W, int32_t nviews);
+int distr_mesh_render(distr_ctx* ctx, const distr_mesh_render_cfg* cfg, const float* verts_dev, int64_t nverts, const int32_t* faces_dev,
+                      int64_t nfaces, int32_t nviews, const float* RT_dev, float* depth_dev, float* zdepth_dev, float* normal_dev,
+                      uint8_t* mask_dev, int32_t* face_dev, float* bary_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
