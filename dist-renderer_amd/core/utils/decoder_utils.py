@@ -169,6 +169,33 @@ def decode_sdf_train(decoder, latent_vectors, points, counts=None, clamp_dist=0.
     return out.reshape(shape + (1,))
 
 
+def _gradient_train_layout(Cn, latent_vectors, points, counts):
+    """Shape logic of decode_sdf_gradient_train: decode_sdf_train's, under its own name in the refusal. Runs without a GPU."""
+    if latent_vectors is None:
+        raise NotImplementedError('latent_vectors=None (a code in every input row, decoder_utils.py:58-59) is not supported')
+    _refuse_point_grads('decode_sdf_gradient_train', points)
+    return _batch_layout(Cn, latent_vectors, points, counts)
+
+
+def decode_sdf_gradient_train(decoder, latent_vectors, points, counts=None, dropout_seed=None):
+    """(sdf, grad) = (f, grad_x f) of S shape codes, BOTH differentiable w.r.t. `decoder.parameters()` and the codes (not in the
+    reference, where such a loss takes torch's double backward through the torch Decoder): what a normal-supervised fit |grad - n|, an
+    Eikonal term (|grad| - 1)^2 or any other loss on the spatial gradient needs to train the decoder. The layer-wise path of
+    decode_sdf_train with the closed form of DESIGN.md section 8m; the ReLU's second derivative is zero, as in torch. Arguments, shapes
+    and ValueErrors as decode_sdf_train: points (S, N, 3) -> ((S, N, 1), (S, N, 3)), or the flat list (sum N, 3) with `counts` ->
+    ((sum N, 1), (sum N, 3)). `sdf` is the raw tanh output: there is NO clamp here, clamp it in torch. `grad` is the TRUE gradient: it
+    carries neither decode_sdf_gradient's legacy factor 3 nor its clamp mask (decode_sdf_gradient_batch(clamp_dist=None) / 3 has the
+    same values, detached). Points are data: points with requires_grad are refused. Dropout as decode_sdf_train (`dropout_seed`, the
+    counter-based mask of section 8g; the tangent and the deltas see the forward's mask and scale). Weight norm is folded on the
+    autograd graph. The workspace takes 40 KB per point; above DISTR_TRAIN_MAX_BYTES (default 32 GiB) the call is refused, not chunked.
+    The backward makes one pass for the upstream gradients of both outputs."""
+    from distr import decoder_pack
+    weights, x, counts, shape, dropout = _train_prologue('decode_sdf_gradient_train', decoder, points, dropout_seed, decoder_pack.effective_weights_torch,
+                                                         lambda Ws: _gradient_train_layout(Ws[0].shape[1] - 3, latent_vectors, points, counts))
+    sdf, grad = functions.decode_sdf_gradient_train_call(weights, latent_vectors, x, counts, dropout)
+    return sdf.reshape(shape + (1,)), grad.reshape(shape + (3,))
+
+
 def decode_sdf_gradient_batch(decoder, latent_vectors, points, counts=None, clamp_dist=0.1):
     """decode_sdf_gradient for S shape codes in one launch sequence; arguments as decode_sdf_batch, returns (S, N, 3) or (sum N, 3) with
     decode_sdf_gradient's value semantics (3 x the gradient, zero where |f| > clamp_dist), detached; byte for byte the single call per

@@ -2894,6 +2894,10 @@ struct TrainPlan {
   size_t bytes;              // what the carve takes
   train::DropArgs da;        // the call's dropout as the kernels take it (train_call)
   uint32_t drop_mask;
+  // the carve of the grad_x f calls (section 8m), behind everything above: the padded upstream u4, the row scalars c1 / c2 / Q, the
+  // row weights of k_train_colsum_w, the tangents tau_1..tau_8 (T[1] holds Delta_4 during the forward)
+  bool grad;
+  float *u4, *c1, *c2, *q, *rw, *T[9] /* 1..8 */;
 };
 
 void train_slab_plan(int64_t rows, int64_t* len, int* count) {
@@ -2942,14 +2946,21 @@ size_t train_carve(void* base, TrainPlan& p) {
   for (int i = 0; i < 3; ++i) p.colseg[i] = c.take<float>((size_t)p.nseg * 4 * HID);
   p.slabs = c.take<float>((size_t)p.nslab * HID * HID);
   p.blkpt0 = c.take<int32_t>((size_t)p.blocks);      // (last: the offsets of everything above are those of the path without dropout)
+  if (p.grad) {
+    p.u4 = c.take<float>(R * 4); p.rw = c.take<float>(R * 4);
+    p.c1 = c.take<float>(R); p.c2 = c.take<float>(R); p.q = c.take<float>(R);
+    for (int l = 1; l <= 8; ++l) p.T[l] = c.take<float>(R * HID);
+  }
   return c.bytes();
 }
 
 // plan and carve of a description (its pointers are not looked at): every size, offset and train call goes through here.
-// base == nullptr: sizes and offsets only.
-int train_layout(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts, void* base, TrainPlan& p) {
+// base == nullptr: sizes and offsets only. grad: the calls of section 8m (out_dim 1 only), with their larger carve.
+int train_layout(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts, void* base, TrainPlan& p, bool grad = false) {
   if (!net || net->struct_size != sizeof(distr_train_net)) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_net: struct_size (use DISTR_INIT)");
   if (int rc = train_plan(ctx, net->latent_size, net->lin3_rows, net->out_dim, nseg, counts, p)) return rc;
+  if (grad && p.nout != 1) return fail(ctx, DISTR_ERR_INVALID_ARG, "distr_train_grad: out_dim %d: the spatial gradient belongs to out_dim 1", p.nout);
+  p.grad = grad;
   p.bytes = train_carve(base, p);
   return DISTR_OK;
 }
@@ -3050,8 +3061,9 @@ int train_grads_ok(distr_ctx* ctx, const distr_train_grads* gr) {
 // passed its weights in. gr: the backward's gradients (backward = true). io: the per-point array, xyz or the upstream gradient.
 // Leaves the plan carved on the caller's workspace, with the dropout as the kernels take it.
 int train_call(distr_ctx* ctx, const distr_train_net* net, const char* name, int32_t nseg, const int64_t* counts, const float* latent, int64_t latent_stride,
-               const float* io, float clamp, void* ws, const distr_train_dropout* drop, bool backward, const distr_train_grads* gr, TrainPlan& p) {
-  if (int rc = train_layout(ctx, net, nseg, counts, ws, p)) return rc;
+               const float* io, float clamp, void* ws, const distr_train_dropout* drop, bool backward, const distr_train_grads* gr, TrainPlan& p,
+               bool grad = false) {
+  if (int rc = train_layout(ctx, net, nseg, counts, ws, p, grad)) return rc;
   if (int rc = train_pointers_ok(ctx, net, name)) return rc;
   if (int rc = train_drop_args(ctx, drop, nseg, p.da, p.drop_mask)) return rc;
   if (backward)
@@ -3099,20 +3111,23 @@ int train_forward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p,
   return DISTR_OK;
 }
 
+// an empty list: every gradient is zero
+int train_zero_grads(distr_ctx* ctx, const TrainPlan& p, const distr_train_grads* gr, float* g_latent, hipStream_t s) {
+  for (int l = 0; l < 9; ++l) {
+    const size_t in = l == 0 ? (size_t)p.C + 3 : l == 4 ? (size_t)p.ld4 : HID;
+    HIP_TRY(hipMemsetAsync(gr->g_W[l], 0, (size_t)p.out_w[l] * in * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(gr->g_b[l], 0, (size_t)p.out_w[l] * sizeof(float), s));
+  }
+  if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)p.nseg * p.C * sizeof(float), s));
+  return DISTR_OK;
+}
+
 // the backward's launch sequence on a checked call
 int train_backward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, const float* latent, int64_t latent_stride, const float* g_sdf, float clamp,
                           const distr_train_grads* gr, float* g_latent, void* stream) {
   const int C = p.C, nseg = p.nseg;
   hipStream_t s = (hipStream_t)stream;
-  if (p.rows == 0) {       // an empty list: every gradient is zero
-    for (int l = 0; l < 9; ++l) {
-      const size_t in = l == 0 ? (size_t)C + 3 : l == 4 ? (size_t)p.ld4 : HID;
-      HIP_TRY(hipMemsetAsync(gr->g_W[l], 0, (size_t)p.out_w[l] * in * sizeof(float), s));
-      HIP_TRY(hipMemsetAsync(gr->g_b[l], 0, (size_t)p.out_w[l] * sizeof(float), s));
-    }
-    if (g_latent) HIP_TRY(hipMemsetAsync(g_latent, 0, (size_t)nseg * C * sizeof(float), s));
-    return DISTR_OK;
-  }
+  if (p.rows == 0) return train_zero_grads(ctx, p, gr, g_latent, s);
   hipLaunchKernelGGL(train::k_train_dz, grid1((int64_t)p.rows * p.nout), dim3(256), 0, s, g_sdf, (const float*)p.th, (const int32_t*)p.rowpt, p.rows, p.nout, clamp, p.dz);
   LAUNCH_CHECK("k_train_dz");
   // lin8: its delta is dz, nout columns
@@ -3170,10 +3185,114 @@ int train_backward_entry(distr_ctx* ctx, const distr_train_net* net, const char*
   return train_backward_launch(ctx, net, p, latent, latent_stride, g_out, clamp, gr, g_latent, stream);
 }
 
+// ---- the spatial gradient g = grad_x f with gradients to the weights
+
+// one step of the unit-delta chain: Delta_(l-1) = G_(l-1) (Delta_l W_l) into `out`, lin4: its lin3 columns only (the delta GEMM of
+// train_backward_launch with an upstream of one)
+int train_unit_delta(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, int l, const float* delta, int ldd, float* out, hipStream_t s) {
+  train::GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = delta; g.lda = ldd; g.B = w->W[l]; g.ldb = l == 4 ? p.ld4 : HID; g.M = p.rows; g.N = p.in_w[l]; g.K = p.out_w[l];
+  g.Cout = out; g.ldc = HID; g.gate = p.X[l]; g.ldg = HID;
+  return train_gemm<true, false, train::EPI_GATE>(ctx, "k_train_gemm<delta>", g, 1, s, (p.drop_mask >> (l - 1) & 1u) ? &p.da : nullptr);
+}
+
+// f as train_forward_launch without a clamp, then the unit deltas 8 -> 0 (Delta_4 kept in T[1]) and k_train_gx
+int train_grad_forward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, const float* latent, int64_t latent_stride, const float* xyz,
+                              float* sdf, float* grad, void* stream) {
+  if (p.rows == 0) return DISTR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = train_forward_launch(ctx, w, p, latent, latent_stride, xyz, -1.f, sdf, stream)) return rc;
+  hipLaunchKernelGGL(train::k_train_unit, grid1(p.rows), dim3(256), 0, s, (const int32_t*)p.rowpt, p.rows, p.dz);
+  LAUNCH_CHECK("k_train_unit");
+  const float* delta = p.dz;
+  int ldd = 1, cur = 0;
+  for (int l = 8; l >= 1; --l) {
+    float* out = l == 5 ? p.T[1] : p.D[cur];      // l == 5: Delta_4, read again at the end
+    if (int rc = train_unit_delta(ctx, w, p, l, delta, ldd, out, s)) return rc;
+    delta = out; ldd = HID;
+    if (l != 5) cur ^= 1;
+  }
+  hipLaunchKernelGGL(train::k_train_gx, dim3((unsigned)p.blocks), dim3(256), 0, s, delta, (const float*)p.T[1], w->W[0], w->W[4], p.C, p.ld4, (const float*)p.th,
+                     (const int32_t*)p.rowpt, grad);
+  LAUNCH_CHECK("k_train_gx");
+  return DISTR_OK;
+}
+
+// weighted column sums of a unit delta (k_train_colsum_w on p.rw), then as train_bias_grad: g_b and, for lin0 / lin4, the xyz and
+// latent columns of g_W
+int train_bias_grad_w(distr_ctx* ctx, const TrainPlan& p, const float* delta, int ldd, int ncols, bool moments, float* seg, float* g_b, float* g_W, int ldw,
+                      int lat_col, int xyz_col, const float* latent, int64_t latent_stride, hipStream_t s) {
+  hipLaunchKernelGGL(train::k_train_colsum_w, dim3((unsigned)p.blocks), dim3(256), 0, s, delta, ldd, ncols, (const float*)p.rw, moments ? 1 : 0, p.colpart);
+  LAUNCH_CHECK("k_train_colsum_w");
+  hipLaunchKernelGGL(train::k_train_colsum_seg, dim3((unsigned)p.nseg, HID / 32, moments ? 4 : 1), dim3(256), 0, s, (const float*)p.colpart, p.sg, ncols, seg);
+  LAUNCH_CHECK("k_train_colsum_seg");
+  hipLaunchKernelGGL(train::k_train_bias, dim3((unsigned)ncols), dim3(256), 0, s, (const float*)seg, p.nseg, g_b, g_W, ldw, lat_col, xyz_col, g_W ? p.C : 0, latent,
+                     latent_stride);
+  LAUNCH_CHECK("k_train_bias");
+  return DISTR_OK;
+}
+
+// g_W's activation columns of lin m: the combined operand c2 X_m + c1 tau_m (in tau_m's buffer), then Delta_m^T times it
+int train_weight_grad_w(distr_ctx* ctx, const TrainPlan& p, int m, const float* delta, int ldd, float* g_W, hipStream_t s) {
+  hipLaunchKernelGGL(train::k_train_combine, grid1((int64_t)p.rows * (HID / 4)), dim3(256), 0, s, (const float*)p.X[m], (const float*)p.c1, (const float*)p.c2, p.rows,
+                     p.in_w[m], p.T[m]);
+  LAUNCH_CHECK("k_train_combine");
+  return train_weight_grad(ctx, p, delta, ldd, p.out_w[m], p.T[m], p.in_w[m], g_W, m == 4 ? p.ld4 : HID, s);
+}
+
+// the backward for the upstreams phi = dL/df (g_sdf) and u = dL/dg (g_grad), either may be null = 0, on the workspace of
+// train_grad_forward_launch: the tangents forward, the row scalars, then the walk 8 -> 1 with the unit deltas recomputed
+int train_grad_backward_launch(distr_ctx* ctx, const distr_train_net* w, TrainPlan& p, const float* latent, int64_t latent_stride, const float* g_sdf,
+                               const float* g_grad, const distr_train_grads* gr, float* g_latent, void* stream) {
+  const int C = p.C;
+  hipStream_t s = (hipStream_t)stream;
+  if (p.rows == 0) return train_zero_grads(ctx, p, gr, g_latent, s);
+  hipLaunchKernelGGL(train::k_train_tan0, dim3((unsigned)p.blocks), dim3(256), 0, s, g_grad, (const int32_t*)p.rowpt, w->W[0], C, (const float*)p.X[1],
+                     (p.drop_mask & 1u) ? p.da.scale : 1.f, p.T[1], p.u4);
+  LAUNCH_CHECK("k_train_tan0");
+  for (int l = 1; l <= 8; ++l) {      // tau_(l+1) = G_l (W_l tau_l), lin4 with u again behind its lin3 columns; l = 8: Q, no gate
+    train::GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = p.T[l]; g.lda = HID; g.B = w->W[l]; g.ldb = l == 4 ? p.ld4 : HID; g.M = p.rows; g.N = p.out_w[l]; g.K = p.in_w[l];
+    g.Cout = l < 8 ? p.T[l + 1] : p.q; g.ldc = l < 8 ? HID : 1;
+    if (l < 8) { g.gate = p.X[l + 1]; g.ldg = HID; }
+    if (l == 4) { g.tailW = w->W[4] + (p.ld4 - 3); g.tail_ld = p.ld4; g.xyz4 = p.u4; }
+    if (int rc = train_gemm<true, true, train::EPI_TAN>(ctx, "k_train_gemm<tangent>", g, 1, s, (l < 8 && (p.drop_mask >> l & 1u)) ? &p.da : nullptr)) return rc;
+  }
+  hipLaunchKernelGGL(train::k_train_rowscal, grid1(p.rows), dim3(256), 0, s, g_sdf, (const float*)p.th, (const float*)p.q, (const int32_t*)p.rowpt, (const float*)p.xyz4,
+                     (const float*)p.u4, p.rows, p.c1, p.c2, p.rw, p.dz);
+  LAUNCH_CHECK("k_train_rowscal");
+  // lin8: Delta_8 = p.dz, one column
+  if (int rc = train_weight_grad_w(ctx, p, 8, p.dz, 1, gr->g_W[8], s)) return rc;
+  if (int rc = train_bias_grad_w(ctx, p, p.dz, 1, 1, false, p.colseg[2], gr->g_b[8], nullptr, 0, 0, 0, latent, latent_stride, s)) return rc;
+  const float* delta = p.dz;
+  int ldd = 1, cur = 0;
+  for (int l = 8; l >= 1; --l) {
+    if (int rc = train_unit_delta(ctx, w, p, l, delta, ldd, p.D[cur], s)) return rc;
+    delta = p.D[cur]; ldd = HID; cur ^= 1;
+    const int m = l - 1;       // delta now belongs to lin m
+    if (m >= 1) {
+      if (int rc = train_weight_grad_w(ctx, p, m, delta, HID, gr->g_W[m], s)) return rc;
+      if (int rc = train_bias_grad_w(ctx, p, delta, HID, p.out_w[m], m == 4, p.colseg[m == 4 ? 1 : 2], gr->g_b[m], m == 4 ? gr->g_W[4] : nullptr, p.ld4, p.n3,
+                                     p.ld4 - 3, latent, latent_stride, s))
+        return rc;
+    } else {
+      if (int rc = train_bias_grad_w(ctx, p, delta, HID, HID, true, p.colseg[0], gr->g_b[0], gr->g_W[0], C + 3, 0, C, latent, latent_stride, s)) return rc;
+    }
+  }
+  if (g_latent) {
+    hipLaunchKernelGGL(train::k_train_glatent, dim3((unsigned)((C + 255) / 256), (unsigned)p.nseg), dim3(256), 0, s, (const float*)p.colseg[0], (const float*)p.colseg[1], w->W[0],
+                       w->W[4], C, p.ld4, p.n3, g_latent);
+    LAUNCH_CHECK("k_train_glatent");
+  }
+  return DISTR_OK;
+}
+
 // workspace bytes (layer 0) or the byte offset of X_layer (1..8) behind the aligned base; 0 for what the calls refuse
-size_t train_bytes_or_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts, int32_t layer) {
+size_t train_bytes_or_offset(const distr_train_net* net, int32_t nseg, const int64_t* counts, int32_t layer, bool grad = false) {
   TrainPlan p;
-  if (layer < 0 || layer > 8 || train_layout(nullptr, net, nseg, counts, nullptr, p) != DISTR_OK) return 0;
+  if (layer < 0 || layer > 8 || train_layout(nullptr, net, nseg, counts, nullptr, p, grad) != DISTR_OK) return 0;
   return layer ? (size_t)((uintptr_t)p.X[layer] - (uintptr_t)p.rowpt) : p.bytes;
 }
 
@@ -3251,6 +3370,32 @@ int distr_train_net_backward(distr_ctx* ctx, const distr_train_net* net, int32_t
                              const float* g_out, float clamp, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
                              const distr_train_dropout* drop) {
   return train_backward_entry(ctx, net, "distr_train_net", nseg, counts_host, latent, latent_stride, g_out, clamp, ws, gr, g_latent, stream, drop);
+}
+
+size_t distr_train_grad_workspace_bytes(const distr_train_net* net, int32_t nseg, const int64_t* counts_host) {
+  return train_bytes_or_offset(net, nseg, counts_host, 0, true);
+}
+
+int distr_train_grad_forward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                             const float* xyz, float* sdf, float* grad, void* ws, size_t ws_bytes, void* stream, const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  TrainPlan p;
+  if (int rc = train_call(ctx, net, "distr_train_net", nseg, counts_host, latent, latent_stride, xyz, -1.f, ws, drop, false, nullptr, p, true)) return rc;
+  if (p.n > 0 && (!sdf || !grad)) return fail(ctx, DISTR_ERR_INVALID_ARG, "null device pointer");
+  if (ws_bytes < p.bytes) return fail(ctx, DISTR_ERR_WORKSPACE, "layer-wise decoder: workspace too small");
+  return train_grad_forward_launch(ctx, net, p, latent, latent_stride, xyz, sdf, grad, stream);
+}
+
+int distr_train_grad_backward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent, int64_t latent_stride,
+                              const float* g_sdf, const float* g_grad, void* ws, const distr_train_grads* gr, float* g_latent, void* stream,
+                              const distr_train_dropout* drop) {
+  if (!ctx) return DISTR_ERR_INVALID_ARG;
+  EntryGuard guard_(ctx);
+  TrainPlan p;
+  const float* io = g_sdf ? g_sdf : g_grad ? g_grad : latent;      // (both upstreams null: all zero, no per-point array to check)
+  if (int rc = train_call(ctx, net, "distr_train_net", nseg, counts_host, latent, latent_stride, io, -1.f, ws, drop, true, gr, p, true)) return rc;
+  return train_grad_backward_launch(ctx, net, p, latent, latent_stride, g_sdf, g_grad, gr, g_latent, stream);
 }
 
 }  // extern "C"

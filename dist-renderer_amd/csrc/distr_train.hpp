@@ -12,6 +12,8 @@
 //   backward  k_train_dz, then per layer 8..1: k_train_gemm<DW> over K slabs + k_train_slab_sum (g_W), k_train_colsum +
 //             k_train_colsum_seg + k_train_bias (g_b and, for lin0 / lin4, the xyz and latent columns of g_W), k_train_gemm<DX> (the
 //             delta of the layer below, gated by the saved activation); k_train_glatent last.
+//   grad_x f  section 8m, at the end of this file: the unit-delta chain, k_train_gx, and the backward for losses on (f, grad_x f):
+//             k_train_tan0, k_train_gemm<TAN> x 8, k_train_rowscal, then the walk 8..1 on k_train_combine + k_train_colsum_w.
 //
 // One LDS-staged tile kernel serves the three GEMM forms; its template arguments are the orientation of the two operands in memory.
 // Every sum has a fixed order (k natural inside an MFMA chain, slabs in slab order, 64-row blocks in block order, segments in segment
@@ -142,8 +144,10 @@ DISTR_GLOBAL void __launch_bounds__(256) k_train_lin0_drop(const float* __restri
 //   forward  X W^T     A = X [row][k] (A_K)      B = W [out][in] (B_K)     EPI_FWD: init = bias[n] or ctab[seg(row)][n]; (+ xyz tail); relu
 //   delta    Delta W   A = Delta [row][out] (A_K) B = W [out][in] (!B_K)    EPI_GATE: init 0; times [gate[row][n] > 0]
 //   weights  Delta^T X A = Delta [row][out] (!A_K) B = X [row][in] (!B_K)   EPI_PART: init 0; blockIdx.z = K slab, its own output
+//   tangent  T W^T     A = T [row][k] (A_K)      B = W [out][in] (B_K)     EPI_TAN: init 0, no bias; (+ tail on u4); times [gate > 0]
+//                                                                          (section 8m: the forward form, linearised along u)
 // Elements outside M, N or K are read as zero and never stored, so no dimension needs to be a multiple of the tile.
-constexpr int EPI_FWD = 0, EPI_GATE = 1, EPI_PART = 2;
+constexpr int EPI_FWD = 0, EPI_GATE = 1, EPI_PART = 2, EPI_TAN = 3;
 
 struct GemmArgs {
   const float* A; const float* B; float* Cout;
@@ -154,8 +158,8 @@ struct GemmArgs {
   const float* bias;              // [N], or null with ctab
   const float* ctab; int ctab_stride; const int32_t* blkseg;    // init of row m = ctab[blkseg[m / 64] * ctab_stride + n]
   const float* tailW; int tail_ld; const float* xyz4;           // three more k behind K: B = tailW[n * tail_ld + d], A = xyz4[m][d]
-  int relu;
-  // EPI_GATE
+  int relu;                                                     // (EPI_TAN: the same tail, xyz4 = the padded upstream u4)
+  // EPI_GATE, EPI_TAN (null gate: none, lin8's tangent)
   const float* gate; int ldg;
   // EPI_PART
   int slab_len; size_t slab_stride;   // slab z covers k in [z * slab_len, min(K, (z + 1) * slab_len)); output at Cout + z * slab_stride
@@ -215,7 +219,7 @@ __device__ __forceinline__ void stage_store(float (*S)[TLD], const float4 (&r)[2
 }
 
 // DROP (section 8g): EPI_FWD drops behind the relu -- a lane's four consecutive rows (r & 3) are the points 4q .. 4q + 3 of one segment, one
-// Philox call serves them; EPI_GATE multiplies the gated delta by d.scale (the saved activation of a dropped unit is an exact zero).
+// Philox call serves them; EPI_GATE and EPI_TAN multiply the gated value by d.scale (the saved activation of a dropped unit is an exact zero).
 template <bool A_K, bool B_K, int EPI, bool DROP>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const DropArgs& d) {
   __shared__ __attribute__((aligned(16))) float As[TBK][TLD];
@@ -282,7 +286,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const DropArgs& d) 
       const int n = n0 + wn + j * 32 + l31;
       if (n >= g.N) continue;
       float tw0 = 0.f, tw1 = 0.f, tw2 = 0.f;
-      if (EPI == EPI_FWD && g.tailW) {
+      if ((EPI == EPI_FWD || EPI == EPI_TAN) && g.tailW) {
         const float* w = g.tailW + (size_t)n * g.tail_ld;
         tw0 = w[0]; tw1 = w[1]; tw2 = w[2];
       }
@@ -313,6 +317,18 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const DropArgs& d) 
         if (EPI == EPI_GATE) {
           if (DROP) v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v * d.scale : 0.f;
           else v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v : 0.f;
+        }
+        if (EPI == EPI_TAN) {
+          if (g.tailW) {
+            const float* q = g.xyz4 + (size_t)m * 4;
+            v = __builtin_fmaf(tw0, q[0], v);
+            v = __builtin_fmaf(tw1, q[1], v);
+            v = __builtin_fmaf(tw2, q[2], v);
+          }
+          if (g.gate) {
+            if (DROP) v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v * d.scale : 0.f;
+            else v = g.gate[(size_t)m * g.ldg + n] > 0.f ? v : 0.f;
+          }
         }
         out[(size_t)m * g.ldc + n] = v;
       }
@@ -449,6 +465,142 @@ DISTR_GLOBAL void __launch_bounds__(256) k_train_glatent(const float* __restrict
   for (int o = 0; o < HID; ++o) a = __builtin_fmaf(W0[(size_t)o * (C + 3) + c], s0[o], a);
   for (int o = 0; o < HID; ++o) a = __builtin_fmaf(W4[(size_t)o * ld4 + col4 + c], s4[o], a);
   g_latent[(size_t)s * C + c] = a;
+}
+
+// ---- the spatial gradient g = grad_x f and its weight gradients (include/distr_train.h).
+// Unit deltas Delta_l = d z / d (lin_l's output): the EPI_GATE chain from Delta_8 = 1 (0 on a padded row). Tangents tau_l = d in_l along
+// the upstream u = dL/dg: the EPI_TAN chain from tau_0 = [0 | u].
+
+// Delta_8: one[row] = 1 for a real row, 0 for a padded one
+DISTR_GLOBAL void __launch_bounds__(256) k_train_unit(const int32_t* __restrict__ rowpt, int rows, float* __restrict__ one) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row < rows) one[row] = rowpt[row] >= 0 ? 1.f : 0.f;
+}
+
+// g[pt][d] = (1 - f^2) (sum_o W0[o][C + d] Delta_0[row][o] + sum_o W4[o][ld4 - 3 + d] Delta_4[row][o]): one fmaf chain per (row, d), o in
+// natural order, lin0's chain then lin4's (the order of k_train_glatent). block = one 64-row block, 256 threads: thread t owns row
+// t & 63 and component t >> 6 (the fourth wave only stages); the deltas pass through LDS in tiles of 64 rows x 64 units.
+DISTR_GLOBAL void __launch_bounds__(256) k_train_gx(const float* __restrict__ D0, const float* __restrict__ D4, const float* __restrict__ W0,
+                                                  const float* __restrict__ W4, int C, int ld4, const float* __restrict__ th,
+                                                  const int32_t* __restrict__ rowpt, float* __restrict__ grad) {
+  __shared__ float ds[TROW][TROW + 1];
+  __shared__ float ws[TROW][4];
+  const int blk = blockIdx.x, t = threadIdx.x, r = t & (TROW - 1), d = t >> 6;
+  float acc = 0.f;
+  for (int half = 0; half < 2; ++half) {
+    const float* D = half ? D4 : D0;
+    const float* W = half ? W4 + (ld4 - 3) : W0 + C;
+    const int ldw = half ? ld4 : C + 3;
+    for (int o0 = 0; o0 < HID; o0 += TROW) {
+      for (int e = t; e < TROW * TROW; e += 256) ds[e >> 6][e & 63] = D[((size_t)blk * TROW + (e >> 6)) * HID + o0 + (e & 63)];
+      if (t < TROW * 3) ws[t / 3][t % 3] = W[(size_t)(o0 + t / 3) * ldw + t % 3];
+      __syncthreads();
+      if (d < 3)
+        for (int o = 0; o < TROW; ++o) acc = __builtin_fmaf(ws[o][d], ds[r][o], acc);
+      __syncthreads();
+    }
+  }
+  if (d < 3) {
+    const int row = blk * TROW + r, pt = rowpt[row];
+    if (pt >= 0) {
+      const float f = th[row];
+      grad[(size_t)pt * 3 + d] = (1.f - f * f) * acc;
+    }
+  }
+}
+
+// lin0's tangent: T1[row] = G_0 (W0[:, C:] u[row]) with G_0 = scale [X1 > 0] (scale = 1 without dropout), and the padded upstream
+// u4[row] = (u, 0), zero for a padded row and for g_grad == null. The thread layout of lin0_block.
+DISTR_GLOBAL void __launch_bounds__(256) k_train_tan0(const float* __restrict__ g_grad, const int32_t* __restrict__ rowpt, const float* __restrict__ W0, int C,
+                                                    const float* __restrict__ X1, float scale, float* __restrict__ T1, float* __restrict__ u4) {
+  __shared__ float p[TROW][4];
+  const int blk = blockIdx.x, t = threadIdx.x;
+  if (t < TROW) {
+    const int pt = rowpt[blk * TROW + t];
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (pt >= 0 && g_grad) { x = g_grad[(size_t)pt * 3]; y = g_grad[(size_t)pt * 3 + 1]; z = g_grad[(size_t)pt * 3 + 2]; }
+    p[t][0] = x; p[t][1] = y; p[t][2] = z; p[t][3] = 0.f;
+    float* q = u4 + ((size_t)blk * TROW + t) * 4;
+    q[0] = x; q[1] = y; q[2] = z; q[3] = 0.f;
+  }
+  __syncthreads();
+  for (int h = 0; h < 2; ++h) {
+    const int o = t + h * 256;
+    const float* w = W0 + (size_t)o * (C + 3) + C;
+    const float wx = w[0], wy = w[1], wz = w[2];
+    for (int r = 0; r < TROW; ++r) {
+      const size_t i = ((size_t)blk * TROW + r) * HID + o;
+      float a = wx * p[r][0];
+      a = __builtin_fmaf(wy, p[r][1], a);
+      a = __builtin_fmaf(wz, p[r][2], a);
+      T1[i] = X1[i] > 0.f ? a * scale : 0.f;
+    }
+  }
+}
+
+// The row scalars of the backward: f = th, t' = 1 - f^2, c1 = t', c2 = t' (phi - 2 f Q) with phi = g_sdf[pt] (null: 0) and Q = W8 tau_8;
+// rw[row] = (c2 x + c1 u_x, c2 y + c1 u_y, c2 z + c1 u_z, c2), the weights of k_train_colsum_w; one[row] = Delta_8. All 0 on a padded row.
+DISTR_GLOBAL void __launch_bounds__(256) k_train_rowscal(const float* __restrict__ g_sdf, const float* __restrict__ th, const float* __restrict__ Q,
+                                                       const int32_t* __restrict__ rowpt, const float* __restrict__ xyz4, const float* __restrict__ u4, int rows,
+                                                       float* __restrict__ c1, float* __restrict__ c2, float* __restrict__ rw, float* __restrict__ one) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= rows) return;
+  const int pt = rowpt[row];
+  float a1 = 0.f, a2 = 0.f;
+  if (pt >= 0) {
+    const float f = th[row], phi = g_sdf ? g_sdf[pt] : 0.f;
+    a1 = 1.f - f * f;
+    a2 = a1 * (phi - 2.f * f * Q[row]);
+  }
+  c1[row] = a1; c2[row] = a2; one[row] = pt >= 0 ? 1.f : 0.f;
+  const float4 x = *(const float4*)(xyz4 + (size_t)row * 4), u = *(const float4*)(u4 + (size_t)row * 4);
+  *(float4*)(rw + (size_t)row * 4) = make_float4(__builtin_fmaf(a2, x.x, a1 * u.x), __builtin_fmaf(a2, x.y, a1 * u.y), __builtin_fmaf(a2, x.z, a1 * u.z), a2);
+}
+
+// The combined operand of a weight gradient, in place: T[row][c] = c2[row] X[row][c] + c1[row] T[row][c] for c < ncols (rows of 512
+// floats; ncols = lin3's rows for X_4, whose other columns are not written). One thread per quad of columns.
+DISTR_GLOBAL void __launch_bounds__(256) k_train_combine(const float* __restrict__ X, const float* __restrict__ c1, const float* __restrict__ c2, int rows, int ncols,
+                                                       float* __restrict__ T) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)rows * (HID / 4)) return;
+  const int row = (int)(i / (HID / 4)), c = (int)(i % (HID / 4)) * 4;
+  if (c >= ncols) return;
+  const float a1 = c1[row], a2 = c2[row];
+  const size_t at = (size_t)row * HID + c;
+  const float4 x = *(const float4*)(X + at);
+  float4 v = *(const float4*)(T + at);
+  v.x = __builtin_fmaf(a2, x.x, a1 * v.x); v.y = __builtin_fmaf(a2, x.y, a1 * v.y);
+  v.z = __builtin_fmaf(a2, x.z, a1 * v.z); v.w = __builtin_fmaf(a2, x.w, a1 * v.w);
+  if (c + 3 < ncols) *(float4*)(T + at) = v;
+  else {
+    T[at] = v.x;
+    if (c + 1 < ncols) T[at + 1] = v.y;
+    if (c + 2 < ncols) T[at + 2] = v.z;
+  }
+}
+
+// k_train_colsum with a weight per row: part[blk][q][col] = sum_r D[r][col] rw[r][q == 0 ? 3 : q - 1], rows in row order; q = 0 (sum
+// c2 Delta: the bias, the latent columns, the code gradient) always, q = 1..3 (the xyz columns of g_W0 / g_W4) with `moments`.
+DISTR_GLOBAL void __launch_bounds__(256) k_train_colsum_w(const float* __restrict__ D, int ldd, int ncols, const float* __restrict__ rw, int moments,
+                                                        float* __restrict__ part) {
+  __shared__ float p[TROW][4];
+  const int blk = blockIdx.x, t = threadIdx.x;
+  if (t < TROW) *(float4*)p[t] = *(const float4*)(rw + ((size_t)blk * TROW + t) * 4);
+  __syncthreads();
+  for (int h = 0; h < 2; ++h) {
+    const int c = t + h * 256;
+    if (c >= ncols) continue;
+    float s = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
+    const float* d = D + (size_t)blk * TROW * ldd + c;
+    for (int r = 0; r < TROW; ++r) {
+      const float v = d[(size_t)r * ldd];
+      s = __builtin_fmaf(v, p[r][3], s);
+      if (moments) { sx = __builtin_fmaf(v, p[r][0], sx); sy = __builtin_fmaf(v, p[r][1], sy); sz = __builtin_fmaf(v, p[r][2], sz); }
+    }
+    float* o = part + (size_t)blk * 4 * HID + c;
+    o[0] = s;
+    if (moments) { o[HID] = sx; o[2 * HID] = sy; o[3 * HID] = sz; }
+  }
 }
 
 }  // namespace train

@@ -49,7 +49,9 @@ TRAIN_EXPORTS = ['distr_train_workspace_bytes', 'distr_train_activation_offset',
                  'distr_train_forward', 'distr_train_backward', 'distr_train_forward_dropout', 'distr_train_backward_dropout',
                  'distr_train_dropout_keep',
                  # the same path on a described network: the colour decoder
-                 'distr_train_net_workspace_bytes', 'distr_train_net_activation_offset', 'distr_train_net_forward', 'distr_train_net_backward']
+                 'distr_train_net_workspace_bytes', 'distr_train_net_activation_offset', 'distr_train_net_forward', 'distr_train_net_backward',
+                 # the spatial gradient grad_x f with weight gradients
+                 'distr_train_grad_workspace_bytes', 'distr_train_grad_forward', 'distr_train_grad_backward']
 # the ordered live list seen from outside (include/distr_live_order.h, included by distr.h): block enumeration, k-step counts, list read-back
 LIVE_ORDER_EXPORTS = ['distr_block_grid', 'distr_block_pixel', 'distr_get_kstep_stats', 'distr_debug_live_list', 'distr_get_kstep32_stats',
                       'distr_debug_mlp_layer32', 'distr_debug_tile_timing32']
@@ -484,6 +486,10 @@ def lib():
             L.distr_train_net_activation_offset.restype = C.c_size_t
             L.distr_train_net_forward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, C.c_float, fp, vp, C.c_size_t, vp, td]
             L.distr_train_net_backward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, C.c_float, vp, tg, fp, vp, td]
+            L.distr_train_grad_workspace_bytes.argtypes = [tn, i32, i64p]
+            L.distr_train_grad_workspace_bytes.restype = C.c_size_t
+            L.distr_train_grad_forward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, fp, fp, vp, C.c_size_t, vp, td]
+            L.distr_train_grad_backward.argtypes = [vp, tn, i32, i64p, fp, i64, fp, fp, vp, tg, fp, vp, td]
             L.distr_render_max_samples.argtypes = [C.POINTER(RenderCfg)]
             L.distr_render_max_samples.restype = i64
             L.distr_render_samples_export_batch.argtypes = [vp, C.POINTER(RenderCfg), i32, vp, C.c_size_t, vp, C.c_size_t, fp, fp, vp, i64, vp, vp]

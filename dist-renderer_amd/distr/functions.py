@@ -713,9 +713,10 @@ def _train_dropout_struct(dropout, chunk_base=0):
 class TrainSaved(object):
     """What train_forward keeps for train_backward: the workspace with the saved layer inputs, and the call it belongs to."""
 
-    def __init__(self, ctx, ws, net, counts, weights, lat, stride, clamp, dropout=None):
+    def __init__(self, ctx, ws, net, counts, weights, lat, stride, clamp, dropout=None, grad=False):
         self.ctx, self.ws, self.net, self.counts = ctx, ws, net, list(counts)       # net: (L, lin3_rows, out_dim), the SDF decoder's too
         self.weights, self.lat, self.stride, self.clamp, self.dropout = weights, lat, stride, clamp, dropout
+        self.grad = grad        # the workspace of train_grad_forward (section 8m): train_grad_backward follows, not train_backward
         self.latent_size, self.lin3_rows, self.out_dim = net
         self.seg_rows = train_segment_rows(counts)
 
@@ -755,7 +756,8 @@ def train_net_shapes(net):
     return W + [(o,) for o, _ in W]
 
 
-def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None, net=None, caller='train_forward'):
+def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=None, dropout=None, ws=None, out=None, net=None, caller='train_forward',
+                  grad=False):
     """Layer-wise decode of one segmented list of at most 64 segments (distr_train_net_forward): weights = [W0..W8, b0..b8] f32 device
     tensors, row-major; latents (S, C) or (1, C) shared; points (sum counts, 3). Returns (sdf (sum counts, 1), saved: TrainSaved).
     A workspace above DISTR_TRAIN_MAX_BYTES is refused (the message names `caller`). ws_bytes (tests): the workspace size to pass
@@ -765,7 +767,8 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     the saved activations are then those behind the dropout, and train_backward follows.
     net: (L, lin3_rows, out_dim), the described network (the colour decoder is (256 + cs, 253, 3)): the weights
     have train_net_shapes(net), latents are (S, L) or (1, L), the output is (sum counts, out_dim), and a clamp belongs to out_dim 1.
-    None = the SDF decoder, (C, 509 - C, 1) with the code length C of W0; a C outside 1..508 is refused here."""
+    None = the SDF decoder, (C, 509 - C, 1) with the code length C of W0; a C outside 1..508 is refused here.
+    grad: train_grad_forward's call (it documents it): no clamp, out = (sdf, grad), returns ((sdf, grad), saved)."""
     counts = [int(c) for c in counts]
     dev = points.device
     if dev.type != 'cuda':
@@ -793,16 +796,31 @@ def train_forward(weights, latents, points, counts, clamp_dist=None, ws_bytes=No
     if x.shape[0] != sum(counts):
         raise ValueError('counts sum to %d, but there are %d points' % (sum(counts), x.shape[0]))
     stride = 0 if lat.shape[0] == 1 else C_len
-    saved = TrainSaved(ctx, ws, net, counts, weights, lat, stride, clamp_dist, dropout)
-    need = ctx.L.distr_train_net_workspace_bytes(*saved.call_args())
+    if grad and (nout != 1 or clamp_dist is not None):
+        raise ValueError('%s: the spatial gradient belongs to a net with out_dim 1 (got %d) and takes no clamp (got %r)' % (caller, nout, clamp_dist))
+    saved = TrainSaved(ctx, ws, net, counts, weights, lat, stride, clamp_dist, dropout, grad)
+    need = (ctx.L.distr_train_grad_workspace_bytes if grad else ctx.L.distr_train_net_workspace_bytes)(*saved.call_args())
     if not need:
         raise ValueError('net (L, lin3_rows, out_dim) = %r: L >= 1, lin3_rows in 1..509, out_dim 1 or 3' % (net,))
+    if grad and need > train_max_bytes():
+        raise binding.DistrError('%s: %d points need a workspace of %d bytes (40 KB per point -- the layer inputs and the tangents -- and the slabs '
+                                 'of the weight gradients), more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient '
+                                 'follows the batch)' % (caller, x.shape[0], need, train_max_bytes()))
     if need > train_max_bytes():
         raise binding.DistrError('%s: %d points need a workspace of %d bytes (24 KB per point and the slabs of the weight gradients), '
                                  'more than DISTR_TRAIN_MAX_BYTES = %d; split the batch (the sum order of a gradient follows the batch)'
                                  % (caller, x.shape[0], need, train_max_bytes()))
     if ws is None:
         ws = saved.ws = torch.empty(need if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
+    if grad:
+        sdf, gx = (torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev), torch.empty(x.shape[0], 3, dtype=torch.float32, device=dev)) if out is None else out
+        if ws.dtype != torch.uint8 or not ws.is_contiguous() or any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.shape[0] * k
+                                                                    for t, k in ((sdf, 1), (gx, 3))):
+            raise ValueError('train_grad_forward: ws is a contiguous uint8 tensor, out contiguous f32 tensors of %d and %d values' % (x.shape[0], 3 * x.shape[0]))
+        td = _train_dropout_struct(dropout)
+        ctx.check(ctx.L.distr_train_grad_forward(*((ctx.h,) + saved.call_args() + (binding.ptr(lat), stride, binding.ptr(x), binding.ptr(sdf), binding.ptr(gx),
+                                                                                    binding.ptr(ws), ws.numel(), ctx.stream(), None if td is None else C.byref(td)))))
+        return (sdf, gx), saved
     if out is None:
         out = torch.empty(x.shape[0], nout, dtype=torch.float32, device=dev)
     if ws.dtype != torch.uint8 or not ws.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.shape[0] * nout:
@@ -819,9 +837,22 @@ def train_backward(saved, g_sdf, out=None):
     one row per segment, also for a shared code). out (tests): (the eighteen gradient tensors, g_latent) to write into instead of fresh
     ones."""
     ctx, dev = saved.ctx, saved.ws.device
+    if saved.grad:
+        raise ValueError('train_backward: this workspace belongs to train_grad_forward; its backward is train_grad_backward')
     gs = _f32c(g_sdf, dev).reshape(-1)
     if gs.numel() != sum(saved.counts) * saved.out_dim:
         raise ValueError('g_sdf has %d entries for %d points of %d channel(s)' % (gs.numel(), sum(saved.counts), saved.out_dim))
+    grads, g_lat, tg = _train_grad_tensors(saved, out, 'train_backward')
+    p = binding.ptr
+    td = _train_dropout_struct(saved.dropout)
+    ctx.check(ctx.L.distr_train_net_backward(*((ctx.h,) + saved.call_args() + (p(saved.lat), saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg),
+                                                                                p(g_lat), ctx.stream(), None if td is None else C.byref(td)))))
+    return grads, g_lat
+
+
+def _train_grad_tensors(saved, out, name):
+    """(the eighteen gradient tensors, g_latent (S, C), distr_train_grads on them) of a backward call: fresh ones, or `out` checked"""
+    dev = saved.ws.device
     if out is None:
         grads = [torch.empty_like(w) for w in saved.weights]
         g_lat = torch.empty(len(saved.counts), saved.latent_size, dtype=torch.float32, device=dev)
@@ -829,15 +860,41 @@ def train_backward(saved, g_sdf, out=None):
         grads, g_lat = out
         if [(g.shape, g.dtype, g.is_contiguous()) for g in grads] != [(w.shape, torch.float32, True) for w in saved.weights] \
                 or (g_lat.shape, g_lat.dtype, g_lat.is_contiguous()) != ((len(saved.counts), saved.latent_size), torch.float32, True):
-            raise ValueError('train_backward: out is (eighteen contiguous f32 tensors of the weights\' shapes, g_latent (S, C))')
+            raise ValueError('%s: out is (eighteen contiguous f32 tensors of the weights\' shapes, g_latent (S, C))' % name)
     tg = binding.TrainGrads()
     for l in range(9):
         tg.g_W[l] = grads[l].data_ptr()
         tg.g_b[l] = grads[9 + l].data_ptr()
-    p = binding.ptr
+    return grads, g_lat, tg
+
+
+def train_grad_forward(weights, latents, points, counts, ws_bytes=None, dropout=None, ws=None, out=None, caller='train_grad_forward'):
+    """f AND its spatial gradient g = grad_x f on the layer-wise path, for losses that reach the weights through g (DESIGN.md section
+    8m; distr_train_grad_forward): arguments as train_forward for the SDF decoder. Returns ((sdf (sum counts, 1), grad (sum counts, 3)),
+    saved). sdf is tanh(z) without a clamp, grad the true gradient (not decode_sdf_gradient's 3 x, no clamp mask). The workspace takes
+    40 KB per point; out (tests): (sdf, grad) tensors to write into."""
+    return train_forward(weights, latents, points, counts, None, ws_bytes=ws_bytes, dropout=dropout, ws=ws, out=out, caller=caller, grad=True)
+
+
+def train_grad_backward(saved, g_sdf, g_grad, out=None):
+    """Backward of train_grad_forward (distr_train_grad_backward), ONE pass for both upstreams: g_sdf = dL/df (sum counts, 1) and
+    g_grad = dL/dg (sum counts, 3), either may be None (zero) -> ([g_W0..g_W8, g_b0..g_b8], g_latent (S, C)) as train_backward. May be
+    called again on the same `saved`."""
+    ctx, dev = saved.ctx, saved.ws.device
+    if not saved.grad:
+        raise ValueError('train_grad_backward: this workspace belongs to train_forward; its backward is train_backward')
+    n = sum(saved.counts)
+    ups = []
+    for name, g, k in (('g_sdf', g_sdf, 1), ('g_grad', g_grad, 3)):
+        g = None if g is None else _f32c(g, dev).reshape(-1)
+        if g is not None and g.numel() != n * k:
+            raise ValueError('%s has %d entries for %d points of %d component(s)' % (name, g.numel(), n, k))
+        ups.append(g)
+    grads, g_lat, tg = _train_grad_tensors(saved, out, 'train_grad_backward')
+    p = lambda t: None if t is None else binding.ptr(t)
     td = _train_dropout_struct(saved.dropout)
-    ctx.check(ctx.L.distr_train_net_backward(*((ctx.h,) + saved.call_args() + (p(saved.lat), saved.stride, p(gs), _clamp_arg(saved.clamp), p(saved.ws), C.byref(tg),
-                                                                                p(g_lat), ctx.stream(), None if td is None else C.byref(td)))))
+    ctx.check(ctx.L.distr_train_grad_backward(*((ctx.h,) + saved.call_args() + (p(saved.lat), saved.stride, p(ups[0]), p(ups[1]), p(saved.ws), C.byref(tg), p(g_lat),
+                                                                                 ctx.stream(), None if td is None else C.byref(td)))))
     return grads, g_lat
 
 
@@ -855,28 +912,37 @@ def _eighteen(weights):
         raise ValueError('expected W0..W8, b0..b8: 18 tensors, got %d' % len(weights))
 
 
-def _train_chunks_forward(ctx, weights, lat, points, counts, clamp_dist, dropout, net, caller):
-    """The forward both train nodes share: code rows `lat` (S, L) or (1, L), more than 64 segments in chunks of 64 (a chunk's
-    segment_base is the dropout's + its first segment); keeps every chunk's TrainSaved on ctx for _train_chunks_backward."""
+def _train_chunks_forward(ctx, weights, lat, points, counts, clamp_dist, dropout, net, caller, grad=False):
+    """The forward the train nodes share: code rows `lat` (S, L) or (1, L), more than 64 segments in chunks of 64 (a chunk's
+    segment_base is the dropout's + its first segment); keeps every chunk's TrainSaved on ctx for _train_chunks_backward.
+    grad: train_grad_forward's chunks, -> (sdf, grad)."""
     counts = [int(c) for c in counts]
     x = points.detach().reshape(-1, 3)
     outs, ctx.saved_chunks = [], []
     for s0, ns, p0, row, stride in _multi_chunks(lat, segment_plan(counts)):
         n = sum(counts[s0:s0 + ns])
         drop = None if dropout is None else tuple(dropout[:4]) + (int(dropout[4]) + s0,)
-        out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist, dropout=drop, net=net, caller=caller)
+        out, saved = train_forward(weights, lat[row:row + (ns if stride else 1)], x[p0:p0 + n], counts[s0:s0 + ns], clamp_dist, dropout=drop, net=net, caller=caller,
+                                   grad=grad)
         outs.append(out)
         ctx.saved_chunks.append((saved, p0, n))
+    if grad:
+        return outs[0] if len(outs) == 1 else tuple(torch.cat(part) for part in zip(*outs))
     return outs[0] if len(outs) == 1 else torch.cat(outs)
 
 
-def _train_chunks_backward(ctx, g):
-    """The backward both train nodes share: the upstream gradient of the output -> (the eighteen weight gradients, the chunks' added in
-    chunk order; the code-gradient rows (S, L))"""
-    g = g.reshape(-1, ctx.saved_chunks[0][0].out_dim)
+def _train_chunks_backward(ctx, g, g_grad=None):
+    """The backward the train nodes share: the upstream gradient of the output -> (the eighteen weight gradients, the chunks' added in
+    chunk order; the code-gradient rows (S, L)). Chunks of train_grad_forward: g and g_grad are the upstreams of (sdf, grad), None = 0."""
+    grad = ctx.saved_chunks[0][0].grad
+    g = None if g is None else g.reshape(-1, ctx.saved_chunks[0][0].out_dim)
+    g_grad = None if g_grad is None else g_grad.reshape(-1, 3)
     total, rows = None, []
     for saved, p0, n in ctx.saved_chunks:
-        grads, g_lat = train_backward(saved, g[p0:p0 + n])
+        if grad:
+            grads, g_lat = train_grad_backward(saved, None if g is None else g[p0:p0 + n], None if g_grad is None else g_grad[p0:p0 + n])
+        else:
+            grads, g_lat = train_backward(saved, g[p0:p0 + n])
         rows.append(g_lat)
         total = _add_in_order(total, grads)
     return total, (rows[0] if len(rows) == 1 else torch.cat(rows))
@@ -904,6 +970,31 @@ class DecodeSdfTrainFunction(torch.autograd.Function):
 
 def decode_sdf_train_call(weights, codes, points, counts, clamp_dist=None, dropout=None):
     return DecodeSdfTrainFunction.apply(codes, points, counts, clamp_dist, dropout, *weights)
+
+
+class DecodeSdfGradientTrainFunction(torch.autograd.Function):
+    """(sdf, grad_x sdf) on the layer-wise path with autograd to the codes AND the eighteen weight tensors THROUGH BOTH outputs (DESIGN.md
+    section 8m): (codes (S, C) or (1, C), flat points (sum counts, 3), counts, dropout, W0..W8, b0..b8) -> ((sum counts, 1), (sum counts,
+    3)). The backward receives both upstreams and makes one pass for them (an output that no loss uses arrives as None: zero). Chunks,
+    dropout and points as DecodeSdfTrainFunction; no clamp. The ReLU's second derivative is zero, as in torch."""
+
+    @staticmethod
+    def forward(ctx, codes, points, counts, dropout, *weights):
+        _eighteen(weights)
+        lat = codes.detach().reshape(-1, weights[0].shape[1] - 3)
+        ctx.codes_shape, ctx.shared = codes.shape, lat.shape[0] == 1
+        ctx.set_materialize_grads(False)
+        return _train_chunks_forward(ctx, weights, lat, points, counts, None, dropout, None, 'decode_sdf_gradient_train', grad=True)
+
+    @staticmethod
+    def backward(ctx, g_f, g_g):
+        total, g_rows = _train_chunks_backward(ctx, g_f, g_g)
+        g_codes = (g_rows.sum(0) if ctx.shared and g_rows.shape[0] > 1 else g_rows).reshape(ctx.codes_shape)
+        return (g_codes, None, None, None) + tuple(total)
+
+
+def decode_sdf_gradient_train_call(weights, codes, points, counts, dropout=None):
+    return DecodeSdfGradientTrainFunction.apply(codes, points, counts, dropout, *weights)
 
 
 class _CodeLayout(object):

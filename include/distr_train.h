@@ -134,6 +134,27 @@ int distr_train_net_backward(distr_ctx* ctx, const distr_train_net* net, int32_t
                              int64_t latent_stride, const float* g_out, float clamp_dist, void* ws_dev, const distr_train_grads* grads,
                              float* g_latent, void* stream, const distr_train_dropout* drop);
 
+/* ---- the SPATIAL GRADIENT g = grad_x f of an out_dim == 1 net, with gradients to the weights and the codes:
+ * what a normal or an Eikonal term is made of. The forward returns f = tanh(z) WITHOUT a clamp (sdf_dev[sum counts]) and the true
+ * gradient g (grad_dev[sum counts][3]; not decode_sdf_gradient's 3 x, no clamp mask), in the caller's point order. The backward takes the
+ * upstreams g_sdf = dL/df [sum counts] and g_grad = dL/dg [sum counts][3] (either may be NULL = zero) and makes ONE pass for both:
+ * grads and g_latent as distr_train_net_backward. With g_grad == NULL the result is the gradient of distr_train_net_forward without a
+ * clamp (another sum order: the row scalar is applied to the operands, not to the delta). The ReLU's second derivative is taken as
+ * zero. Weights, list, codes, streams, padding and the dropout struct (the tangent and the deltas see the forward's mask and scale) as
+ * above; the backward runs on the workspace its forward filled and may be repeated. Workspace: the carve of
+ * distr_train_net_workspace_bytes, unchanged, and behind it eight tangent rows of 512 floats, the padded upstream and the row scalars:
+ * 40 KB + 44 bytes per padded row against 24 KB. Sum orders: those of the calls above; g itself is one fmaf chain per component, the
+ * hidden units in natural order, lin0's 512 then lin4's 512. Same bytes on every run; a segment's sdf / grad slices and its g_latent
+ * row are those of a call on that segment alone. Refused as above, and out_dim != 1 (DISTR_ERR_INVALID_ARG: the colour net has no such
+ * gradient); distr_train_grad_workspace_bytes returns 0 for what the calls refuse. */
+size_t distr_train_grad_workspace_bytes(const distr_train_net* net, int32_t nseg, const int64_t* counts_host);
+int distr_train_grad_forward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent_dev,
+                             int64_t latent_stride, const float* xyz_dev, float* sdf_dev, float* grad_dev, void* ws_dev, size_t ws_bytes,
+                             void* stream, const distr_train_dropout* drop);
+int distr_train_grad_backward(distr_ctx* ctx, const distr_train_net* net, int32_t nseg, const int64_t* counts_host, const float* latent_dev,
+                              int64_t latent_stride, const float* g_sdf, const float* g_grad, void* ws_dev, const distr_train_grads* grads,
+                              float* g_latent, void* stream, const distr_train_dropout* drop);
+
 #ifdef __cplusplus
 }
 #endif
